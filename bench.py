@@ -15,9 +15,16 @@ ranking and top-60% aggregation (configs[2] shape).  Metric: poses/sec (one pose
 whole-job aggregate over all ranks; weak scaling (every rank owns its own B clouds; the only collective is the final
 all-gather of the results over RCCL).
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize() on both sides and
-reduced with MAX over ranks.  The K-step block is repeated until >= 1 s has been timed (`--repeats` fixes the count); `value` and
-`ms_per_step` come from the MEDIAN block, the spread is reported next to them.
+Timing: W warm-up steps, then ONE block of EXACTLY K timed steps, bracketed by barrier + torch.cuda.synchronize() on both sides and
+reduced with MAX over ranks; `value` and `ms_per_step` come from it.  `--repeats R` times R such blocks and reports the MEDIAN block
+(0 = repeat until >= 1 s has been timed), the spread next to it.  The inputs are seeded: the same arguments give the same inputs.
+
+A plain run measures the headline only.  `--full` adds the side measurements: the roofline of the dominant kernel, the same workload with
+one batch per launch, ODE-100, configs[2], the drop-in call sequence, configs[0], the energy model's PC step, the CPU baseline (the last
+two groups can be left out with --no-secondary / --no-cpu-baseline) and, with --tracking, the one-sequence latency legs.
+
+`--dump-outputs DIR` writes what the timed path returned for its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all),
+so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -57,6 +64,10 @@ PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 dens
 # its own batch-global coupling and gets its stand-alone result).  Measured on MI355X: 1 -> 17.0 k, 5 -> 24.9 k, 10 -> 26.4 k, 20 -> 27.0 k
 # poses/s (32 000 rows = 250 128-row workgroups of the chain-form sampler, one per CU; the encoder's persistent kernels amortise over 640 clouds).
 DEFAULT_BATCHES_PER_LAUNCH = 10
+# Distinct input batches per rank: a run of K steps walks min(K, POOL_BATCHES) batches in order (the default run, K = 20, sees 20 distinct
+# batches); synthesising a batch costs ~0.2 s of host time, which a long run must not pay per step.
+POOL_BATCHES = 20
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse():
@@ -64,7 +75,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=0, help="timed K-step blocks (0 = as many as it takes to time >= 1 s, at most 64)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed K-step blocks, the median one reported (default 1: exactly --steps timed steps; 0 = as many as it takes to time "
+                         ">= 1 s, at most 64)")
     ap.add_argument("--batch", type=int, default=64, help="clouds per GPU per step")
     ap.add_argument("--cand", type=int, default=50)
     ap.add_argument("--sde-steps", type=int, default=100)
@@ -94,6 +107,11 @@ def parse():
                          "sampler from T0 = 0.15, energy ranking, aggregation per frame); a step = one frame of every sequence")
     ap.add_argument("--sequences", type=int, default=64, help="tracking: concurrent sequences per GPU")
     ap.add_argument("--objects", type=int, default=5, help="tracking: objects per frame")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (roofline, one batch per launch, ODE-100, configs[0] / [2], drop-in, energy model, CPU "
+                         "baseline; with --tracking the one-sequence legs); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -252,6 +270,7 @@ def main():
     from genpose_amd.posenet_agent import PoseNet
     from genpose_amd.weights_synth import make_state_dict
 
+    torch.manual_seed(rank)  # the host-side prior draws and the device-side sampler noise: the same arguments give the same inputs
     if args.only_drop_in:
         print(json.dumps({"drop_in_eval_single": drop_in_leg(torch, str(dev), args.cand)}), flush=True)
         return
@@ -270,9 +289,9 @@ def main():
         energy_agent = PoseNet(get_config(device=str(dev), posenet_mode="energy"))
         energy_agent.load_state_dict(make_state_dict(0, "energy"))
 
-    # inputs resident in HBM before the timed region (weak scaling: distinct clouds per rank).  Every batch of a timed block is a
-    # DIFFERENT set of clouds (ball-query early exits are data dependent): a pool of `steps` batches, walked in order.
-    npool = max(1, args.steps)
+    # inputs resident in HBM before the timed region (weak scaling: distinct clouds per rank).  The batches of a timed block are
+    # DIFFERENT sets of clouds (ball-query early exits are data dependent): a pool of min(steps, POOL_BATCHES) batches, walked in order.
+    npool = max(1, min(args.steps, POOL_BATCHES))
     pool = [torch.from_numpy(synth.make_batch(B, start=(rank * npool + j) * B)).to(dev) for j in range(npool)]
     pts = pool[0]
     centre = pts.mean(dim=1)
@@ -291,18 +310,20 @@ def main():
             dist.all_gather(outs, o)
 
     def step(pts=pts):
+        """One batch through the agent API -> the arrays a caller receives (name -> tensor)."""
         if full_pred is not None:
-            out = full_pred.run(pts)["avg_pose"]
-            gather(out)
+            out = full_pred.run(pts)
+            gather(out["avg_pose"])
             return out
         data = {"pts": pts, "pts_center": pts.mean(dim=1)}
         pred = score_agent.pred_func(data, repeat_num=K, save_path=None, T0=T0)
-        out = pred
-        if energy_agent is not None:
-            energy = energy_agent.get_energy(data=data, pose_samples=pred, T=1e-5)  # same dict: the grouping ticket is taken over
-            out = reward.rank_aggregate(pred, energy, ratio=0.6)["avg_pose"]
-        gather(out)
-        return out
+        if energy_agent is None:
+            gather(pred)
+            return {"pred_pose": pred}
+        energy = energy_agent.get_energy(data=data, pose_samples=pred, T=1e-5)  # same dict: the grouping ticket is taken over
+        out = reward.rank_aggregate(pred, energy, ratio=0.6)
+        gather(out["avg_pose"])
+        return dict(out, pred_pose=pred, energy=energy)
 
     def barrier():
         if dist is not None:
@@ -325,20 +346,26 @@ def main():
     G = args.batches_per_launch if (pipelined or ode_grouped) else (full_pred.G if full_pred is not None else 1)
 
     def run_steps(count):
+        """`count` steps; returns the outputs of the last one (name -> tensor)."""
+        last = None
         if full_pred is not None:
             for o in full_pred.run_many(batches_of(count)):
                 gather(o["avg_pose"])
-            return
+                last = o
+            return last
         if ode_grouped:
             for o in ode_pred.run(batches_of(count)):
                 gather(o)
-            return
+                last = {"pred_pose": o}
+            return last
         if not pipelined:
             for j in range(count):
-                step(pool[j % npool])
-            return
+                last = step(pool[j % npool])
+            return last
         for o in pipe.run(batches_of(count)):
             gather(o)
+            last = {"pred_pose": o}
+        return last
 
     step()  # builds samplers / captures graphs outside the timed region
     if pipelined or ode_grouped or full_pred is not None:
@@ -347,14 +374,14 @@ def main():
     run_steps(args.warmup)
     barrier()
     if pipe is not None:
-        pipe.timing = True
+        pipe.timing = args.full  # HIP events around every sampler graph replay: the in-situ launch time of the --full roofline
 
     def timed_block():
         barrier()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         ev0.record()
-        run_steps(args.steps)
+        last = run_steps(args.steps)
         ev1.record()
         barrier()
         elapsed = time.perf_counter() - t0
@@ -362,7 +389,7 @@ def main():
             tt = torch.tensor([elapsed], device="cpu" if one_dev else dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
-        return elapsed, ev0.elapsed_time(ev1)
+        return elapsed, ev0.elapsed_time(ev1), last
 
     blocks = [timed_block()]
     reps = args.repeats if args.repeats > 0 else max(1, min(64, math.ceil(1.0 / blocks[0][0])))  # identical on every rank (MAX-reduced time)
@@ -373,11 +400,13 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
     gpu_event_ms = statistics.median(b[1] for b in blocks) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, blocks[-1][2])
 
     # ---- roofline of the dominant kernel (pc_step: fused PC update + score network), HIP events on the launch stream
     roofline = None
     nfev = n
-    if args.sampler == "pc" and full_pred is None:
+    if args.full and args.sampler == "pc" and full_pred is None:
         smp = pipe._sampler(0, G) if pipe is not None else score_agent.net.last_sampler
         roofline = pc_roofline(torch, smp, G * B * K, n)
         in_situ = pipe.sampler_launch_seconds() if pipe is not None else None
@@ -394,7 +423,7 @@ def main():
                           "encoder_and_sampler_split_bf16": split_bf16_leg(torch, score_agent, pool, B, K, n, G, str(dev), True)}), flush=True)
         return
     side = {}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # the same workload with ONE batch per launch (no request batching), reported next to the headline for comparison
         if pipelined and G > 1:
             side["one_batch_per_launch"] = one_batch_leg(torch, score_agent, pool, B, K, n)
@@ -508,7 +537,7 @@ def tracking_bench(torch, args, dist, dev, world, rank, one_dev, backend):
             tt = torch.tensor([elapsed], device="cpu" if one_dev else dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
-        return elapsed, [int(r["nfev"]) for r in out]
+        return elapsed, [int(r["nfev"]) for r in out], out
 
     blocks = [timed_block()]
     reps = args.repeats if args.repeats > 0 else max(1, min(16, math.ceil(1.0 / blocks[0][0])))
@@ -517,8 +546,12 @@ def tracking_bench(torch, args, dist, dev, world, rank, one_dev, backend):
     times = sorted(b[0] for b in blocks)
     elapsed = statistics.median(times)
     nfev = statistics.median(blocks[-1][1])
+    if args.dump_outputs and rank == 0:
+        # one frame of every sequence: each field stacked over the sequences (every sequence has the same number of objects)
+        last = blocks[-1][2]
+        dump_outputs(args.dump_outputs, {k: torch.stack([torch.as_tensor(r[k]) for r in last]) for k in last[0]})
     single = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         # latency of ONE sequence processed frame by frame (runner.TrackingRunner: a frame = two hipGraphs around the adaptive solve, the
         # energy model's encoder underneath the solve) - what evaluation_tracking.py's loop does, one call per frame
         from genpose_amd.runner import TrackingRunner
@@ -612,6 +645,29 @@ def single_sequence_trained(torch, dev, K, T0, n_obj):
             "frames_per_repeat": nfr, "statistic": "median of the repeats", "mean_nfev_per_frame_by_repeat": [round(v, 1) for v in nfe],
             "median_translation_error_cm_at_the_last_frame": round(statistics.median(terr), 2), "objects_per_frame": n_obj,
             "weights": "trained on synthetic posed clouds (tests/golden/trained)", "workload": "synth.posed_sequence(11): 30 frames, one TrackingRunner.step per frame"}
+
+
+def dump_outputs(d, arrays):
+    """arrays: name -> tensor (or array / number) -> d/<name>.npy, float64 where the source is float64 or an integer, else float32 (integers
+    up to 2^53 are exact in float64).  Above DUMP_LIMIT_BYTES in all, every array is cut to its share of the limit by a fixed, seeded sample
+    of its leading-axis entries (kept in order), so two runs with the same arguments write the same sample."""
+    import numpy as np
+    import torch
+    out = {}
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        a = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.as_tensor(v)
+        a = a.to(torch.float64 if a.dtype == torch.float64 or not a.is_floating_point() else torch.float32)
+        out[name] = np.ascontiguousarray(a.numpy())
+    total = sum(a.nbytes for a in out.values())
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0:
+            share = DUMP_LIMIT_BYTES * a.nbytes // total
+            keep = max(1, min(a.shape[0], share // max(1, a.nbytes // a.shape[0])))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(d, f"{name}.npy"), a)
 
 
 def pc_roofline(torch, smp, rows, n, flop_row=FLOP_SCORE_ROW):

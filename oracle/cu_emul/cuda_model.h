@@ -2,8 +2,9 @@
  * ORACLE — TEST INFRASTRUCTURE ONLY, build container only, DIAGNOSTIC ONLY (not a parity pin).
  *
  * A CPU execution model for the TEXT of the reference's CUDA kernels (sampling_gpu.cu, ball_query_gpu.cu, interpolate_gpu.cu).
- * tests/test_cu_text_emulation.py extracts the kernel bodies from /root/reference at test time into a temporary directory
- * (nothing of the reference is committed or shipped), compiles them with the host compilers against this header and runs them:
+ * oracle/gen_cu_text_golden.py extracts the kernel bodies from the reference tree into a temporary directory (nothing of the
+ * reference is committed or shipped), compiles them with the host compilers against this header, runs them and stores their outputs
+ * in tests/golden/g17_cu_text.npz, which tests/test_cu_text_emulation.py compares against the oracle:
  *   - every CUDA thread of a block is a cooperative fiber; __syncthreads() yields to a round-robin scheduler that resumes the
  *     block's fibers in threadIdx order until all of them have arrived (or returned); blocks run one after another;
  *   - __shared__ is `static` (one block at a time), threadIdx / blockIdx / blockDim / gridDim are globals set by the scheduler;

@@ -1,6 +1,6 @@
 /*
  * ORACLE — TEST INFRASTRUCTURE ONLY, build container only, DIAGNOSTIC ONLY (see cuda_model.h).
- * The four `*.inc` files are the kernel bodies of the reference, extracted at test time by tests/test_cu_text_emulation.py
+ * The four `*.inc` files are the kernel bodies of the reference, extracted at generation time by oracle/gen_cu_text_golden.py
  * (EMU_INC_DIR is a temporary directory; nothing from /root/reference is committed).  The launch dispatch below restates the
  * launchers (which are `<<< >>>` syntax and cannot be compiled by a host compiler): sampling_gpu.cu:211-253 (block size =
  * opt_n_threads(n), one block per cloud), ball_query_gpu.cu:48-67 and interpolate_gpu.cu:55-74,99-117 (THREADS_PER_BLOCK

@@ -6,17 +6,17 @@ if [ "$1" != "noprof_tests" ]; then
 timeout 1500 python -m pytest tests -x -q -m gpu -p no:cacheprovider --durations=15 > $O/pytest_gpu.log 2>&1; tail -22 $O/pytest_gpu.log
 timeout 200 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 fi
-timeout 500 python bench.py > $O/bench_line.json 2> $O/bench.err; cut -c1-400 $O/bench_line.json
+timeout 500 python bench.py --full > $O/bench_line.json 2> $O/bench.err; cut -c1-400 $O/bench_line.json
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -o bench -- python bench.py --no-cpu-baseline --no-secondary > $O/bench_line_under_rocprof.json 2> $O/prof_bench.err
 find /tmp/prof_bench -name "*kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_dropin -o dropin -- python bench.py --only-drop-in > $O/drop_in_under_rocprof.json 2> $O/prof_dropin.err
 find /tmp/prof_dropin -name "*kernel_stats.csv" -exec cp {} $O/drop_in_kernel_stats.csv \;
 {
 for v in "--batches-per-launch 1" "--batches-per-launch 5" "--batches-per-launch 20" "--sampler ode" "--pipeline full --batch 256" "--tracking --sequences 64 --steps 10 --warmup 3" "--tracking --sequences 1 --steps 20 --warmup 8"; do
-  echo "== bench.py --no-cpu-baseline --no-secondary $v"; timeout 300 python bench.py --no-cpu-baseline $( [[ "$v" == *"sequences 1 "* ]] || echo --no-secondary ) $v 2>/dev/null
+  echo "== bench.py --no-cpu-baseline --no-secondary $v"; timeout 300 python bench.py --full --no-cpu-baseline $( [[ "$v" == *"sequences 1 "* ]] || echo --no-secondary ) $v 2>/dev/null
 done
-echo "== GP_BENCH_ONE_DEVICE=1 bench.py --gpus 8 --no-cpu-baseline --no-secondary (eight ranks sharing the one device, collectives on gloo)"; GP_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --gpus 8 --no-cpu-baseline --no-secondary 2>$O/bench_8ranks.err
-echo "== GP_BENCH_ONE_DEVICE=1 bench.py --gpus 8 --pipeline full --batch 256 --steps 4 --warmup 2 --no-cpu-baseline --no-secondary"; GP_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --gpus 8 --pipeline full --batch 256 --steps 4 --warmup 2 --no-cpu-baseline --no-secondary 2>>$O/bench_8ranks.err
+echo "== GP_BENCH_ONE_DEVICE=1 bench.py --gpus 8 --no-cpu-baseline --no-secondary (eight ranks sharing the one device, collectives on gloo)"; GP_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --full --gpus 8 --no-cpu-baseline --no-secondary 2>$O/bench_8ranks.err
+echo "== GP_BENCH_ONE_DEVICE=1 bench.py --gpus 8 --pipeline full --batch 256 --steps 4 --warmup 2 --no-cpu-baseline --no-secondary"; GP_BENCH_ONE_DEVICE=1 timeout 600 python bench.py --full --gpus 8 --pipeline full --batch 256 --steps 4 --warmup 2 --no-cpu-baseline --no-secondary 2>>$O/bench_8ranks.err
 } > $O/bench_variants.txt
 timeout 300 python scratch/bench_tracking.py 16 64 128 > $O/tracking.txt 2>/dev/null
 timeout 200 python scratch/chain_check.py > $O/plans.txt 2>&1

@@ -10,4 +10,4 @@ GP_PROXY_REPORT=$O/accuracy_proxy.txt GP_PROXY_INSTANCES=512 timeout 1200 python
 if [ "$1" != "notests" ]; then
 timeout 1500 python -m pytest tests -q -m gpu -p no:cacheprovider --durations=15 > $O/pytest_gpu.log 2>&1; tail -25 $O/pytest_gpu.log
 fi
-timeout 500 python bench.py > $O/bench_line.json 2> $O/bench.err; cut -c1-600 $O/bench_line.json
+timeout 500 python bench.py --full > $O/bench_line.json 2> $O/bench.err; cut -c1-600 $O/bench_line.json

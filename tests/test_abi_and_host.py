@@ -413,3 +413,25 @@ def test_shape_cache_evicts_least_recently_used_and_skips_pins():
     from genpose_amd.posenet_agent import PoseNet
     net = PoseNet(get_config(device="cpu")).net
     assert isinstance(net._samplers, ShapeCache) and net._samplers.capacity == net.MAX_SAMPLERS == 8
+
+
+def test_bench_dump_outputs_types_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 stays float32, float64 and integers become float64, None is left out; above the size limit every
+    array keeps a fixed, seeded, ordered sample of its leading-axis entries (the same sample in every run)."""
+    import bench
+    pose = torch.arange(40 * 3, dtype=torch.float32).reshape(40, 3)
+    arrays = {"pose": pose, "pose64": pose.double(), "order": torch.arange(40), "none": None}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert set(got) == {"pose", "pose64", "order"}
+    assert got["pose"].dtype == np.float32 and got["pose64"].dtype == np.float64 and got["order"].dtype == np.float64
+    assert np.array_equal(got["pose"], pose.numpy()) and np.array_equal(got["order"], np.arange(40))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1024)
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    b = {f.stem: np.load(f) for f in (tmp_path / "b").iterdir()}
+    c = {f.stem: np.load(f) for f in (tmp_path / "c").iterdir()}
+    assert sum(a.nbytes for a in b.values()) <= 1024
+    rows = b["order"].astype(np.int64)
+    assert len(rows) < 40 and np.all(np.diff(rows) > 0) and np.array_equal(b["pose"], pose.numpy()[rows])
+    assert all(np.array_equal(b[k], c[k]) for k in b)

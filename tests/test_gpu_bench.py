@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -39,14 +40,30 @@ def test_two_ranks_self_launched_on_one_device():
 
 
 def test_one_rank_direct_and_through_the_launcher_agree():
-    direct = _run(["--gpus", "1"])
-    spawned = _run(["--gpus", "1"], {"GP_BENCH_FORCE_LAUNCH": "1"})
+    direct = _run(["--gpus", "1", "--full"])  # (--full: the roofline compared below)
+    spawned = _run(["--gpus", "1", "--full"], {"GP_BENCH_FORCE_LAUNCH": "1"})
     assert direct["launch"]["mode"] == "direct" and spawned["launch"]["mode"] == "self"
     assert set(direct) == set(spawned) and REQUIRED <= set(direct)
     for k in ("metric", "unit", "n_gpus", "steps", "warmup", "scaling", "dtype", "data", "config", "higher_is_better"):
         assert direct[k] == spawned[k], k
     assert direct["roofline"]["kernel"] == spawned["roofline"]["kernel"]
     assert direct["roofline"]["flops_per_launch"] == spawned["roofline"]["flops_per_launch"]
+
+
+def test_plain_line_times_exactly_the_steps_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run times ONE block of exactly --steps steps, leaves the --full measurements out, and --dump-outputs writes the last step's
+    outputs: with the same arguments the inputs are the same, and so are the outputs (the path is deterministic)."""
+    dumps = []
+    for j in range(2):
+        d = tmp_path / f"run{j}"
+        line = _run(["--gpus", "1", "--dump-outputs", str(d)])
+        assert line["steps"] == 2 and line["timing"]["blocks"] == 1 and line["timing"]["steps_per_block"] == 2
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["ms_per_step"] > 0
+        assert abs(line["value"] - 8 * 2 / (line["ms_per_step"] * 2e-3)) <= 0.01 * line["value"]
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert set(dumps[0]) == {"pred_pose.npy"} and dumps[0]["pred_pose.npy"].shape == (8, 10, 9)
+    assert dumps[0]["pred_pose.npy"].dtype == np.float32 and np.isfinite(dumps[0]["pred_pose.npy"]).all()
+    assert np.array_equal(dumps[0]["pred_pose.npy"], dumps[1]["pred_pose.npy"])
 
 
 def test_config3_full_pipeline_two_ranks_on_one_device():
