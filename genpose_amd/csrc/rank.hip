@@ -131,15 +131,21 @@ __global__ __launch_bounds__(64) void rank_aggregate_kernel(int k, int sel, cons
     energy += (size_t)b * k * 2;
     for (int i = tid; i < 2 * k; i += 64) e[i] = energy[i];
     __syncthreads();
-    // stable descending rank by counting (torch.sort(descending=True); ties keep candidate order)
+    // stable descending rank by counting (torch.sort(descending=True, stable=True); ties keep candidate order).  The order is
+    // torch's: every NaN ranks above +inf and NaNs tie with each other, -0.0 ties with +0.0.  With the plain `>` / `==` a NaN
+    // compares false both ways, two candidates share a rank and some ord slots stay unwritten (read below as pose indices).
     for (int i = tid; i < k; i += 64) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const float ei = e[2 * i + c];
+            const bool ni = isnan(ei);
             int r = 0;
             for (int j = 0; j < k; ++j) {
                 const float ej = e[2 * j + c];
-                r += (ej > ei) || (ej == ei && j < i);
+                const bool nj = isnan(ej);
+                const bool above = (nj && !ni) || (ej > ei);
+                const bool tie = (nj && ni) || (ej == ei);
+                r += above || (tie && j < i);
             }
             ord[2 * r + c] = i;
         }
