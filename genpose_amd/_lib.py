@@ -70,6 +70,7 @@ SIGNATURES = {
     "gp_score_eval_plan": [c_int, c_int, c_int, NETP, P, P, P, P, c_int, P, P],
     "gp_pc_layout_bf16x3": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "gp_pc_step_bf16x3": [c_int] * 5 + [P] * 18 + [P],
+    "gp_pc_step_bf16x9": [c_int] * 5 + [NETP] + [P] * 12 + [c_int] + [P] * 3 + [P],
     "gp_pc_step_grouped": [c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 11 + [P],
     "gp_pc_step_coupled": [c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 12 + [P],
     "gp_rk45_state_bytes": [],

@@ -1,0 +1,57 @@
+// Exact-product split-bf16 ("bf16x9") arithmetic for the BF16 matrix pipe: an fp32 value is the sum of three bf16 terms,
+//     x = hi + mid + lo,   hi = bf16(x),  mid = bf16(x - hi),  lo = bf16((x - hi) - mid)     (round to nearest even at every stage)
+// which is exact for a normal fp32 x: 24 significand bits = 8 + 8 + 8, and both differences are exact in fp32 (each drops the leading
+// eight bits of a value that has at most 24).  A product a_i . b_j of two bf16 terms has at most 16 significand bits, so it is exact in
+// fp32; v_mfma_f32_16x16x32_bf16 forms all of them exactly and only its fp32 accumulation rounds - the error class of the fp32 MFMA path,
+// at 16 / 9 of its work rate (the BF16 pipe runs at 16x the fp32 one).  Unlike bf16x3.h (three of the nine products, hi / lo pairs),
+// nothing is dropped.
+#pragma once
+#include "gp_common.h"
+
+namespace gp_bf16x9 {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// the three terms of eight values: t[0] = hi, t[1] = mid, t[2] = lo
+struct Split8 {
+    bf16x8 t[3];
+};
+
+// (a, b) = eight fp32 values of a lane (two D fragments: chunks 2m and 2m+1) -> the lane's eight k-values of k-block m as hi / mid / lo.
+// Per two values: three v_cvt_pk_bf16_f32, two widenings back to fp32 (shifts), four subtractions - all exact but the conversions.
+__device__ __forceinline__ Split8 split8(const f32x4 a, const f32x4 b) {
+    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    Split8 s;
+#pragma unroll
+    for (int i = 0; i < 8; i += 2) {
+        const bf16x2 h = __builtin_convertvector(f32x2{x[i], x[i + 1]}, bf16x2);
+        const f32x2 hf = __builtin_convertvector(h, f32x2);
+        const float r0 = x[i] - hf.x, r1 = x[i + 1] - hf.y;  // exact
+        const bf16x2 m = __builtin_convertvector(f32x2{r0, r1}, bf16x2);
+        const f32x2 mf = __builtin_convertvector(m, f32x2);
+        const bf16x2 l = __builtin_convertvector(f32x2{r0 - mf.x, r1 - mf.y}, bf16x2);  // r - mid is exact and has <= 8 bits: l == r - mid
+        s.t[0][i] = h.x, s.t[0][i + 1] = h.y;
+        s.t[1][i] = m.x, s.t[1][i + 1] = m.y;
+        s.t[2][i] = l.x, s.t[2][i + 1] = l.y;
+    }
+    return s;
+}
+
+// acc[p] += W . X[p] for NT B tiles sharing one A operand W = (hi, mid, lo): the nine exact products of each tile, SMALLEST TERMS FIRST
+// (lo.lo; lo.mid, mid.lo; lo.hi, mid.mid, hi.lo; mid.hi, hi.mid; hi.hi), so the small terms meet the accumulator before the large
+// ones; the tiles are interleaved product by product (independent accumulation chains for the pipe).
+template <int NT>
+__device__ __forceinline__ void mma9(const bf16x8 (&w)[3], const Split8 (&x)[NT], f32x4 (&acc)[NT]) {
+    constexpr int WA[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0};  // term of W
+    constexpr int XB[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0};  // term of X
+#pragma unroll
+    for (int q = 0; q < 9; ++q)
+#pragma unroll
+        for (int p = 0; p < NT; ++p) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[WA[q]], x[p].t[XB[q]], acc[p], 0, 0, 0);
+}
+
+__device__ __forceinline__ f32x4 relu4(const f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
+
+}  // namespace gp_bf16x9

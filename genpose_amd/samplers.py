@@ -26,7 +26,7 @@ class PCSampler:
     """Predictor-corrector sampler state for a fixed (B, K, num_steps): buffers + optional hipGraph of the whole loop."""
 
     def __init__(self, net, B, K, num_steps, device, use_graph=True, record_traj=False, groups=1, coupling_group=None, tile=0, model="score",
-                 precision="f32"):
+                 precision="f32", trunk=None):
         """B clouds in `groups` independent batches of B/groups clouds laid out back to back: one launch chain serves all of
         them, the batch-mean gradient norm (samplers.py:130-132) stays per batch (gp_pc_step_grouped).
 
@@ -74,8 +74,20 @@ class PCSampler:
         # the latency regime (three workgroups per 16-row tile, one head of the network each - GP_PLAN_HEADSPLIT)
         self.plan, self.nparts = t_out.value, n_out.value
         self.tile, self.hsplit = self.plan & ~_lib.PLAN_HEADSPLIT, (3 if self.plan & _lib.PLAN_HEADSPLIT else 1)
+        # trunk: the arithmetic of the score model's chain plan (128 rows per workgroup) - 'bf16x9' (the default: csrc/trunk_bf16x9.hip,
+        # every fp32 product as the nine exact products of hi / mid / lo bf16 terms on the BF16 matrix pipe, fp32 accumulation) or
+        # 'f32mfma' (pc_step_chain_kernel<2>: fp32 MFMA; A/B runs and tests).  Every other plan, model and precision ignores it.
+        if trunk not in (None, "bf16x9", "f32mfma"):
+            raise ValueError(f"trunk {trunk!r}: 'bf16x9' or 'f32mfma'")
+        self.trunk = None
+        if precision == "f32" and self.model == 0 and self.tile == 128:
+            self.trunk = trunk or "bf16x9"
+            if self.trunk == "bf16x9":
+                self._x9 = net.w.bf16x9_packs()
         if precision == "bf16x3":
             self.kernel_name = "pc_step_bf16x3_kernel"
+        elif self.trunk == "bf16x9":
+            self.kernel_name = "pc_step_chain_kernel<bf16x9>"
         elif self.tile in (16, 32, 64):
             self.kernel_name = ("pc_step_kernel<16,0,split>" if self.hsplit == 3 else f"pc_step_kernel<{self.tile}>" if self.model == 0
                                 else f"pc_step_kernel<{self.tile},energy>")
@@ -110,6 +122,11 @@ class PCSampler:
                       ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x), ptr(self.score), ptr(self.partials), ptr(self.traj),
                       ptr(self._bf[0]), ptr(self._bf[1]), ptr(self._bf[2]), ptr(t["b_pose0"]), ptr(t["b_pose2"]), ptr(t["w_out"]), ptr(t["b_out"]),
                       stream_ptr())
+            return
+        if self.trunk == "bf16x9":
+            _lib.call("gp_pc_step_bf16x9", self.groups, self.B // self.groups, self.K, i, self.n, self.net.w.ref(), ptr(self.cvec), ptr(self.tvec_all),
+                      ptr(self.sched), ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x), ptr(self.score), ptr(self.partials),
+                      ptr(self.traj), ptr(self.gn_ext), self.gn_rows, ptr(self._x9[0]), ptr(self._x9[1]), ptr(self._x9[2]), stream_ptr())
             return
         _lib.call("gp_pc_step_plan", self.model, self.plan, self.groups, self.B // self.groups, self.K, i, self.n, self.net.w.ref(), ptr(self.cvec), ptr(self.tvec_all),
                   ptr(self.sched), ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x), ptr(self.score), ptr(self.partials),

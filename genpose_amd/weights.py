@@ -152,6 +152,46 @@ def pack_bf16x3(W, n_chunks, k_blocks, chain=True):
     return out.contiguous()
 
 
+def split_bf16x9(W):
+    """W f32 -> (hi, mid, lo) bf16 with hi + mid + lo == W exactly: hi = bf16(W), mid = bf16(W - hi), lo = bf16((W - hi) - mid), each
+    rounded to nearest even; both differences are exact in fp32.  Raises ValueError where the three terms do not give W back bit for bit
+    or a nonzero term lies below the normal range (the matrix pipe may flush it), and for non-finite weights."""
+    W = W.detach().float().cpu()
+    hi = W.to(torch.bfloat16)
+    r = W - hi.float()
+    mid = r.to(torch.bfloat16)
+    lo = (r - mid.float()).to(torch.bfloat16)
+    back = (hi.double() + mid.double()) + lo.double()
+    tiny = torch.finfo(torch.float32).tiny
+    bad = ~torch.isfinite(W) | (back != W.double())
+    for t in (hi, mid, lo):
+        bad |= (t.float() != 0) & (t.float().abs() < tiny)
+    if bool(bad.any()):
+        raise ValueError(f"{int(bad.sum())} weight(s) do not split exactly into three normal bf16 terms "
+                         f"(first at index {tuple(bad.nonzero()[0].tolist())})")
+    return hi, mid, lo
+
+
+def pack_bf16x9(W, n_chunks, k_blocks, chain=True):
+    """W [n_out, k_in] f32 -> int16 [k_blocks][n_chunks][3 = hi, mid, lo][64 lanes][8]: pack_bf16x3's fragment order and k order with the
+    three exact terms of split_bf16x9 (checked there: hi + mid + lo == W for every weight).  Out-of-range outputs / inputs are zero."""
+    W = W.detach().float().cpu()
+    n_out, k_in = W.shape
+    Wp = torch.zeros(16 * n_chunks, 32 * k_blocks)
+    Wp[:n_out, :k_in] = W
+    terms = torch.stack([t.view(torch.int16) for t in split_bf16x9(Wp)], dim=0)  # [3][16 n_chunks][32 k_blocks]
+    lanes = torch.arange(64)
+    n, g = lanes % 16, lanes // 16
+    e = torch.arange(8)
+    if chain:
+        koff = torch.where(e < 4, 4 * g[:, None] + e[None, :], 16 + 4 * g[:, None] + (e[None, :] - 4))  # [64, 8]
+    else:
+        koff = 8 * g[:, None] + e[None, :]
+    rows = (16 * torch.arange(n_chunks)[None, :, None, None] + n[None, None, :, None]).expand(k_blocks, n_chunks, 64, 8)
+    cols = (32 * torch.arange(k_blocks)[:, None, None, None] + koff[None, None]).expand(k_blocks, n_chunks, 64, 8)
+    return terms[:, rows, cols].permute(1, 2, 0, 3, 4).contiguous()  # [3][kb][nc][64][8] -> [kb][nc][3][64][8]
+
+
 class EncoderWeights:
     def __init__(self, sd, device, params="light", prefix="pts_encoder."):
         if params not in ENCODER_CFGS:
@@ -207,6 +247,7 @@ class ScoreNetWeights:
         self._raw = {"pose0": g("pose_encoder.0.weight"), "pose2": g("pose_encoder.2.weight"), "headx": W1[:, 1152:1408].contiguous()}
         self._device = device
         self._bf16x3 = None
+        self._bf16x9 = None
 
     def bf16x3_packs(self):
         """Operands of the opt-in split-bf16 PC step (csrc/trunk_bf16x3.hip): the three dense layers of the trunk as hi / lo bf16 pairs in
@@ -216,6 +257,16 @@ class ScoreNetWeights:
             self._bf16x3 = (pack_bf16x3(r["pose0"], 16, 1, chain=False).to(self._device), pack_bf16x3(r["pose2"], 16, 8).to(self._device),
                             pack_bf16x3(r["headx"], 48, 8).to(self._device))
         return self._bf16x3
+
+    def bf16x9_packs(self):
+        """Operands of the default chain-plan PC step (csrc/trunk_bf16x9.hip): the three dense layers of the trunk as exact hi / mid / lo
+        bf16 triples in the fragment order of v_mfma_f32_16x16x32_bf16 (pack_bf16x9)
+        -> (w_pose0 [1][16][3][64][8], w_pose2 [8][16][3][64][8], w_headx [8][48][3][64][8]) as int16 device tensors."""
+        if self._bf16x9 is None:
+            r = self._raw
+            self._bf16x9 = (pack_bf16x9(r["pose0"], 16, 1, chain=False).to(self._device), pack_bf16x9(r["pose2"], 16, 8).to(self._device),
+                            pack_bf16x9(r["headx"], 48, 8).to(self._device))
+        return self._bf16x9
 
     def ref(self):
         return ctypes.byref(self.struct)

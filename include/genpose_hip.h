@@ -281,6 +281,17 @@ int gp_pc_step_grouped(int ngroups, int nclouds_per_group, int k, int step, int 
  * [1][16][2][64][8] in natural k order, pose_encoder.2 [8][16]..., stacked heads [8][48]... in the register chain's k order); b_*, w_out [9][256],
  * b_out [9] fp32.  PC sampler of the score model only (the RK45 driver and every default path keep the fp32 trunk). */
 int gp_pc_layout_bf16x3(int ngroups, int nclouds_per_group, int k, int *nparts_out);
+/* The chain plan (128 rows per workgroup) of gp_pc_step_plan for the score model (model 0), with the network's three dense layers as
+ * EXACT-PRODUCT split bf16 (csrc/trunk_bf16x9.hip: every fp32 operand = hi + mid + lo, all nine bf16 cross products on
+ * v_mfma_f32_16x16x32_bf16, fp32 accumulation).  gp_pc_step_plan's contract with tile = 128: the same buffers, gn_ext / gn_rows_total
+ * coupling, partials [nsteps][*nparts_out of gp_pc_layout(0, 128, ...)]; GP_EINVAL where that plan does not apply.  w_*_x9: hi / mid / lo
+ * bf16 triples in the fragment order of v_mfma_f32_16x16x32_bf16 (genpose_amd/weights.py: pack_bf16x9 - pose_encoder.0 [1][16][3][64][8]
+ * in natural k order, pose_encoder.2 [8][16]..., stacked heads [8][48]... in the register chain's k order); biases and output layers
+ * from `net`.  The default for that plan (genpose_amd/samplers.py); gp_pc_step_plan keeps the fp32-MFMA chain kernel. */
+int gp_pc_step_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec, const float *tvec_all,
+                      const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score,
+                      float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
+                      const void *w_headx_x9, gp_stream_t s);
 int gp_pc_step_bf16x3(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const float *cvec, const float *tvec_all, const float *sched,
                       const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score, float *partials,
                       float *traj, const void *w_pose0_split, const void *w_pose2_split, const void *w_headx_split, const float *b_pose0, const float *b_pose2,
