@@ -1,0 +1,88 @@
+// What the two split-bf16 score trunks of the PC step (trunk_bf16x9.hip: hi / mid / lo, trunk_bf16x3.hip: hi / lo) share around their
+// arithmetic (bf16x9.h, bf16x3.h): the vector types, the weight stream's slice addresses, the fp32 operands staged in LDS, the first
+// layer's pose fragment and the fp32 Linear(256, 3) head epilogue.  NTERM = bf16 terms per weight (3 / 2).  Rings, barriers and launch
+// geometry stay with each kernel.
+#pragma once
+#include "score_trunk.h"
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+namespace gp_split {
+
+using namespace gp_trunk;
+
+// packed weights (weights.pack_bf16x9 / pack_bf16x3) and the fp32 operands of the epilogues
+struct SplitNet {
+    const bf16x8 *w0;  // pose_encoder.0 [1][16][NTERM][64]   k = component index (natural order, zero padded to 32)
+    const bf16x8 *w2;  // pose_encoder.2 [8][16][NTERM][64]   k order of the register chain
+    const bf16x8 *wh;  // stacked heads  [8][48][NTERM][64]
+    const float *b0, *b2, *w_out, *b_out;  // fp32: biases [256], [256]; output layers [9][256], [9]
+};
+
+constexpr int NSLICES = 33;  // pose_encoder.0 (1), pose_encoder.2 (8), three heads (8 each)
+constexpr int NCL = 4;       // clouds a workgroup's 128 rows may span (gp_pc_layout)
+
+// LDS (floats): ring [SLOTS][SLICE] bf16x8 | w_out [9][256] | b0 [256] | b2 [256] | cvt [NCL][768] = cvec[cloud] + tvec
+template <int NTERM, int SLOTS>
+struct SplitLds {
+    static constexpr int SLICE = 16 * NTERM * 64;  // bf16x8 (16 B) per slice = (one 32-wide k-block) x (16 output chunks) x NTERM terms
+    static constexpr int OFF_WOUT = SLOTS * SLICE * 4, OFF_B0 = OFF_WOUT + POSE * HID, OFF_B2 = OFF_B0 + HID, OFF_CVT = OFF_B2 + HID,
+                         TOTAL = OFF_CVT + NCL * HEADS;
+    static constexpr size_t BYTES = (size_t)TOTAL * sizeof(float);
+    static_assert(BYTES <= 160 * 1024, "LDS");
+};
+
+template <int NTERM>
+__device__ __forceinline__ const bf16x8 *split_slice(const SplitNet &w, int s) {
+    s = s < NSLICES ? s : NSLICES - 1;  // the ring runs ahead: requests past the end re-read the last slice (never used)
+    if (s == 0) return w.w0;
+    if (s <= 8) return w.w2 + (size_t)(s - 1) * (16 * NTERM * 64);
+    const int h = (s - 9) >> 3, kb = (s - 9) & 7;
+    return w.wh + ((size_t)kb * 48 + 16 * h) * NTERM * 64;
+}
+
+// w_out, the two hidden biases and cvec[cloud] + tvec of step i for the workgroup's (up to NCL) clouds -> LDS, by NT threads
+template <int NT, typename L>
+__device__ __forceinline__ void split_stage(float *lds, const SplitNet &w, const float *cvec, const float *tvec, int wg_row0, int nrows, int kcand) {
+    const int tid = threadIdx.x;
+    float *woutl = lds + L::OFF_WOUT, *b0l = lds + L::OFF_B0, *b2l = lds + L::OFF_B2, *cvtl = lds + L::OFF_CVT;
+    for (int e = tid; e < POSE * HID; e += NT) woutl[e] = w.w_out[e];
+    for (int e = tid; e < HID; e += NT) b0l[e] = w.b0[e], b2l[e] = w.b2[e];
+    const int cloud0 = wg_row0 / kcand, last_cloud = (nrows - 1) / kcand;
+    for (int e = tid; e < NCL * HEADS; e += NT) {
+        const int c = e / HEADS, o = e - c * HEADS;
+        const int cl = cloud0 + c < last_cloud ? cloud0 + c : last_cloud;
+        cvtl[e] = cvec[(size_t)cl * HEADS + o] + tvec[o];
+    }
+}
+
+// pose_encoder.0's B operand: the row's nine components as the one (zero-padded) k-block, natural k order: lane group g holds
+// k = 8g .. 8g+7
+__device__ __forceinline__ void split_pose_fragment(const float (&xv)[9], int g, f32x4 &pa, f32x4 &pb) {
+    pa = f32x4{0.f, 0.f, 0.f, 0.f}, pb = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (g == 0) pa = f32x4{xv[0], xv[1], xv[2], xv[3]}, pb = f32x4{xv[4], xv[5], xv[6], xv[7]};
+    if (g == 1) pa = f32x4{xv[8], 0.f, 0.f, 0.f};
+}
+
+// Head h's Linear(256, 3) output layer as fp32 dot products on the accumulator fragments: out[c] = relu(acc + cvt) . w_out[3 h + c]
+// (cvt: the row's cloud's row of the staged cvec + tvec).  The four lane groups hold the four channel quarters: fixed order, every
+// lane gets the sum.
+__device__ __forceinline__ void split_head_out(const f32x4 (&acc)[16], const float *cvt, const float *woutl, int h, int g, float (&out)[3]) {
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+#pragma unroll
+    for (int n = 0; n < 16; ++n) {
+        const int ch = 16 * n + 4 * g;
+        const f32x4 v = relu4(acc[n] + *reinterpret_cast<const f32x4 *>(cvt + 256 * h + ch));
+        const f32x4 w0 = *reinterpret_cast<const f32x4 *>(woutl + (3 * h + 0) * HID + ch);
+        const f32x4 w1 = *reinterpret_cast<const f32x4 *>(woutl + (3 * h + 1) * HID + ch);
+        const f32x4 w2 = *reinterpret_cast<const f32x4 *>(woutl + (3 * h + 2) * HID + ch);
+        o0 += v.x * w0.x + v.y * w0.y + v.z * w0.z + v.w * w0.w;
+        o1 += v.x * w1.x + v.y * w1.y + v.z * w1.z + v.w * w1.w;
+        o2 += v.x * w2.x + v.y * w2.y + v.z * w2.z + v.w * w2.w;
+    }
+    out[0] = lane_groups_sum(o0), out[1] = lane_groups_sum(o1), out[2] = lane_groups_sum(o2);
+}
+
+}  // namespace gp_split

@@ -1,13 +1,9 @@
 // Shared pieces of the OPT-IN split-bf16 kernels (sa_bf16x3.hip, trunk_bf16x3.hip): three bf16 matrix products with fp32 accumulation
 // stand in for one fp32 product,  a . b ~= a_hi . b_hi + a_lo . b_hi + a_hi . b_lo,  x_hi = bf16(x), x_lo = bf16(x - x_hi).
 #pragma once
-#include "gp_common.h"
+#include "bf16_split_common.h"
 
 namespace gp_bf16x3 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // (a, b) = eight fp32 values of a lane (two D fragments: chunks 2m and 2m+1) -> the lane's eight k-values of k-block m as hi / lo vectors.
 // Five VALU instructions per two values: v_cvt_pk_bf16_f32 (round to nearest even), shift / mask back to fp32, v_pk_add_f32 (x - hi is exact),
@@ -22,8 +18,6 @@ __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, bf16x8 &hi,
         hi[i] = h.x, hi[i + 1] = h.y, lo[i] = l.x, lo[i + 1] = l.y;
     }
 }
-
-__device__ __forceinline__ f32x4 relu4(const f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
 
 // acc += W . X with W = (wh, wl) as the A operand and X = (xh, xl) as the B operand: D lane (point, g) holds output channels 4g .. 4g+3
 __device__ __forceinline__ f32x4 mma3(const bf16x8 wh, const bf16x8 wl, const bf16x8 xh, const bf16x8 xl, f32x4 acc) {

@@ -6,13 +6,9 @@
 // at 16 / 9 of its work rate (the BF16 pipe runs at 16x the fp32 one).  Unlike bf16x3.h (three of the nine products, hi / lo pairs),
 // nothing is dropped.
 #pragma once
-#include "gp_common.h"
+#include "bf16_split_common.h"
 
 namespace gp_bf16x9 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // the three terms of eight values: t[0] = hi, t[1] = mid, t[2] = lo
 struct Split8 {
@@ -51,7 +47,5 @@ __device__ __forceinline__ void mma9(const bf16x8 (&w)[3], const Split8 (&x)[NT]
 #pragma unroll
         for (int p = 0; p < NT; ++p) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[WA[q]], x[p].t[XB[q]], acc[p], 0, 0, 0);
 }
-
-__device__ __forceinline__ f32x4 relu4(const f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
 
 }  // namespace gp_bf16x9

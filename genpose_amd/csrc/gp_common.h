@@ -7,6 +7,12 @@
 
 static inline int gp_launch_status() { return hipGetLastError() == hipSuccess ? GP_OK : GP_ELAUNCH; }
 
+// Lets a kernel use `bytes` of dynamic LDS (above the 64 KB default); callers do it once per kernel.
+template <typename K>
+static inline int set_lds(K kern, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? GP_OK : GP_ELAUNCH;
+}
+
 // Compute units of the CURRENT device (MI355X: 256 in 8 XCDs), queried once per device ordinal: persistent grids are sized from it.
 // (Per device, not per process: a process may hold partitioned and unpartitioned devices side by side.  The table is filled with plain
 // stores of an idempotent value - two threads racing on one slot write the same number.)
@@ -25,6 +31,7 @@ static inline int gp_num_cus() {
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 relu4(const f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
 
 // Keeps an early-requested value where it was requested: without it hipcc sinks the load next to its first use.
 __device__ __forceinline__ void gp_pin(float &v) { asm volatile("" : "+v"(v)); }

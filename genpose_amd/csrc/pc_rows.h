@@ -1,0 +1,174 @@
+// The predictor-corrector (PC) sampler step's contract (cond_pc_sampler, samplers.py:102-160), in ONE place for the three kernels in
+// which a WAVE owns its rows from the sampler update to the score (128 rows per workgroup):
+//     pc_step_chain_kernel<2, MODEL>  (scorenet.hip, fp32 MFMA)    PT = 2 row tiles per wave, NW = 4 waves
+//     pc_step_chain_kernel_bf16x9     (trunk_bf16x9.hip)           PT = 2, NW = 4
+//     pc_step_bf16x3_kernel           (trunk_bf16x3.hip)           PT = 1, NW = 8
+// The launch for step i (0 <= i <= nsteps): i > 0 finishes step i-1 for the wave's rows (Langevin corrector + Euler-Maruyama
+// predictor) using score_{i-1} and the batch-mean gradient norm; i < nsteps evaluates score_i and writes one partial sum of |score_i|
+// per WAVE; i == nsteps finishes only and post-processes mean_x.  What lives here and nowhere else: the argument block, the clamped
+// ragged rows, the fixed order of the gradient-norm sum (results are bit-reproducible across plans), the statistic from outside
+// (gn_ext), the trajectory's centre offset, and the score / partial stores.  Each kernel keeps its own matrix core and weight ring.
+// The tile kernel pc_step_kernel<P, MODEL, SPLIT> (row work on tid < P, the norm through LDS) is a different shape: it shares PcArgs
+// and pc_update_row only.
+#pragma once
+#include "score_trunk.h"
+
+namespace gp_trunk {
+
+struct PcArgs {
+    int nrows, kcand, step, nsteps;
+    int nparts, ppg, rows_per_group;  // partial sums of |score| per step / per batch (group): the batch-mean gradient norm is per group
+    int wgpg;                         // workgroups per group
+    const float *cvec, *tvec_all;    // tvec_all [nsteps][768]
+    const float *sched;              // [nsteps][4]: sigma(t_i), g(t_i), step_size, sqrt(step_size)  (f32, host schedule)
+    const float *z_lang, *z_pred;    // [nsteps][R][9]
+    const float *centre;             // [R/k... per cloud][3]
+    float *x, *mean_x, *score, *partials, *traj;  // x,mean_x,score [R,9]; partials [nsteps][nparts]; traj [nsteps][R][9] or null
+    const float *gn_ext;             // [nsteps][ngroups] or null: the batch's gradient-norm statistic supplied from outside (a batch that is
+    int ngroups;                     //   sharded over several GPUs, all-reduced between the launches): the SUM of |score| over all its
+    float gn_rows;                   //   rows when gn_rows > 0 (= that row count), else the mean itself
+    // head-split plan (GP_PLAN_HEADSPLIT): workgroup 3 t + h evaluates head h of 16-row tile t and owns components 3 h .. 3 h + 2 of the
+    // score.  THREE workgroups read a tile's state and score and each writes a part of them, so nothing a launch reads may be written by
+    // the same launch: every step keeps its own copies in its row of `partials` (nparts = 21 * nrows floats per step):
+    //     [0, 3R)     sum of squares of row r's three components of head h at 3 r + h (a row's norm needs all nine: the NEXT launch puts
+    //                 sqrt(p[3r] + p[3r+1] + p[3r+2]) together and reduces it over its batch's rows)
+    //     [3R, 12R)   score_i [R][9], read by launch i + 1
+    //     [12R, 21R)  the state after launch i's update [R][9], read by launch i + 1 (launch 1 reads the initial state from `x`, which
+    //                 this plan never writes)
+    // (wgpg counts TILES per group.)
+};
+
+// The arguments every plan shares (wgpg = workgroups, or head-split tiles, per group of rg rows).
+static inline PcArgs pc_args(int ngroups, int rg, int k, int step, int nsteps, int nparts, int wgpg, const float *cvec, const float *tvec_all,
+                             const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x,
+                             float *score, float *partials, float *traj, const float *gn_ext, int gn_rows_total) {
+    PcArgs a;
+    a.nrows = ngroups * rg, a.kcand = k, a.step = step, a.nsteps = nsteps;
+    a.nparts = nparts, a.ppg = nparts / ngroups, a.rows_per_group = rg, a.wgpg = wgpg;
+    a.cvec = cvec, a.tvec_all = tvec_all, a.sched = sched, a.z_lang = z_langevin, a.z_pred = z_predictor, a.centre = centre;
+    a.x = x, a.mean_x = mean_x, a.score = score, a.partials = partials, a.traj = traj;
+    a.gn_ext = gn_ext, a.ngroups = ngroups, a.gn_rows = (float)gn_rows_total;
+    return a;
+}
+
+// A wave's rows through one launch: lane (pt, g) = (lane & 15, lane >> 4) carries row 16 * (wave * PT + p) + pt of the workgroup for
+// each tile p.  Every lane of a row's four lane groups carries the row's 9-vector (the update is ~150 VALU instructions per wave,
+// computed redundantly by the four groups - cheaper than any exchange), lane group 0 stores.  The three phases keep one issue order
+// on purpose (memory returns in order): request() asks for what the sampler update needs, the caller issues its ring prologue behind
+// it, finish_previous() then runs the update while the weights are still on their way.
+template <int PT>
+struct PcRows {
+    int row[PT];
+    float xv[PT][9], gr[PT][9], zz1[PT][9], zz2[PT][9], cen[PT][3];
+    float gdiff, dt, sqdt, gn, sigma;
+    float psum[4];    // the batch's first 256 partial sums, one per lane and quarter
+    const float *pp;  // the batch's partial sums of step i-1
+
+    // (1) the rows' operands, then the schedule and the batch's partial sums (or the statistic from outside), then sigma(t_i)
+    template <int NW>
+    __device__ __forceinline__ void request(const PcArgs &a, int wave, int lane) {
+        const int i = a.step, pt = lane & 15, wg_row0 = blockIdx.x * (16 * PT * NW);
+#pragma unroll
+        for (int p = 0; p < PT; ++p) row[p] = wg_row0 + (wave * PT + p) * 16 + pt;
+#pragma unroll
+        for (int p = 0; p < PT; ++p) {
+            const int r = row[p] < a.nrows ? row[p] : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
+#pragma unroll
+            for (int j = 0; j < 9; ++j) xv[p][j] = a.x[(size_t)r * 9 + j];
+            if (i > 0) {
+                const float *z1 = a.z_lang + ((size_t)(i - 1) * a.nrows + r) * 9;
+                const float *z2 = a.z_pred + ((size_t)(i - 1) * a.nrows + r) * 9;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    gr[p][j] = a.score[(size_t)r * 9 + j];
+                    zz1[p][j] = z1[j];
+                    zz2[p][j] = z2[j];
+                }
+                const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
+                cen[p][0] = cp[0], cen[p][1] = cp[1], cen[p][2] = cp[2];
+            }
+        }
+        const int grp = blockIdx.x / a.wgpg;
+        pp = a.partials + (size_t)(i > 0 ? i - 1 : 0) * a.nparts + (size_t)grp * a.ppg;
+        // (locals, assigned to the members once: two branches that store to different members of one object keep it out of registers)
+        float gdiff_ = 0.f, dt_ = 0.f, sqdt_ = 0.f, gn_ = 1.f, sigma_ = 1.f, psum_[4] = {0.f, 0.f, 0.f, 0.f};
+        if (i > 0) {
+            const float *sc = a.sched + (size_t)(i - 1) * 4;
+            gdiff_ = sc[1], dt_ = sc[2], sqdt_ = sc[3];
+            if (a.gn_ext) {
+                gn_ = a.gn_ext[(size_t)(i - 1) * a.ngroups + grp];
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) psum_[u] = lane + 64 * u < a.ppg ? pp[lane + 64 * u] : 0.f;
+            }
+        }
+        if (i < a.nsteps) sigma_ = a.sched[(size_t)i * 4 + 0];
+        gdiff = gdiff_, dt = dt_, sqdt = sqdt_, gn = gn_, sigma = sigma_;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) psum[u] = psum_[u];
+    }
+
+    // (3) finish step i-1: the batch mean of |score_{i-1}| - every wave reduces its batch's partial sums in the same fixed order
+    // (identical in all waves: deterministic) - then the update and the stores.  True when the launch is the finish-only one: the
+    // caller returns.
+    __device__ __forceinline__ bool finish_previous(const PcArgs &a, int lane) {
+        const int i = a.step, g = lane >> 4;
+        if (i == 0) return false;
+        if (a.gn_ext) {
+            if (a.gn_rows > 0.f) gn = gn / a.gn_rows;
+        } else {
+            float s = ((psum[0] + psum[1]) + psum[2]) + psum[3];  // the order of `for (q = lane; q < ppg; q += 64) s += pp[q]`
+            for (int q = lane + 256; q < a.ppg; q += 64) s += pp[q];
+            gn = wave_sum_f32(s) / (float)a.rows_per_group;
+        }
+#pragma unroll
+        for (int p = 0; p < PT; ++p) {
+            float mx[9];
+            pc_update_row(xv[p], gr[p], zz1[p], zz2[p], gn, gdiff, dt, sqdt, mx);
+            if (row[p] < a.nrows && g == 0) {
+                const int r = row[p];
+                if (a.traj) {
+                    float *tr = a.traj + ((size_t)(i - 1) * a.nrows + r) * 9;
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) tr[j] = xv[p][j];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) tr[6 + j] = xv[p][6 + j] + cen[p][j];
+                }
+#pragma unroll
+                for (int j = 0; j < 9; ++j) a.x[(size_t)r * 9 + j] = xv[p][j];
+                if (i == a.nsteps) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) mx[6 + j] += cen[p][j];
+                    normalize_rot6(mx);
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) a.mean_x[(size_t)r * 9 + j] = mx[j];
+                }
+            }
+        }
+        return i == a.nsteps;
+    }
+};
+
+// Components j0 .. j0 + N - 1 of a row's score are final: stored by lane group 0, their squares summed into q in component order.
+template <int N>
+__device__ __forceinline__ void pc_store_score(const PcArgs &a, int row, int lane, int j0, const float (&sc)[N], float &q) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) q += sc[c] * sc[c];
+    if (row < a.nrows && lane < 16) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) a.score[(size_t)row * 9 + j0 + c] = sc[c];
+    }
+}
+
+// The wave's partial sum of |score_i| over its live rows (q: the rows' sums of squares).
+template <int PT, int NW>
+__device__ __forceinline__ void pc_store_partial(const PcArgs &a, const int (&row)[PT], const float (&q)[PT], int wave, int lane) {
+    float nsum = 0.f;
+#pragma unroll
+    for (int p = 0; p < PT; ++p)
+        if (row[p] < a.nrows && lane < 16) nsum += sqrtf(q[p]);
+    nsum = wave_sum_f32(nsum);
+    if (lane == 0) a.partials[(size_t)a.step * a.nparts + (size_t)blockIdx.x * NW + wave] = nsum;
+}
+
+}  // namespace gp_trunk

@@ -8,6 +8,7 @@
 //                + W1x . pose_feat (per row, per evaluation: here, on fp32 MFMA)
 // The three heads are stacked into one 768-wide layer; their 256->3 output layers are applied in the
 // accumulator epilogue (no 768-wide activation ever reaches LDS).
+#include "pc_rows.h"
 #include "score_bwd.h"
 #include "trunk_chain_vjp.h"
 
@@ -159,28 +160,7 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void score_eval_chain_kernel(int n
 }
 
 // ---------------------------------------------------------------------------------------------- PC sampler
-struct PcArgs {
-    int nrows, kcand, step, nsteps;
-    int nparts, ppg, rows_per_group;  // partial sums of |score| per step / per batch (group): the batch-mean gradient norm is per group
-    int wgpg;                         // workgroups per group
-    const float *cvec, *tvec_all;    // tvec_all [nsteps][768]
-    const float *sched;              // [nsteps][4]: sigma(t_i), g(t_i), step_size, sqrt(step_size)  (f32, host schedule)
-    const float *z_lang, *z_pred;    // [nsteps][R][9]
-    const float *centre;             // [R/k... per cloud][3]
-    float *x, *mean_x, *score, *partials, *traj;  // x,mean_x,score [R,9]; partials [nsteps][nparts]; traj [nsteps][R][9] or null
-    const float *gn_ext;             // [nsteps][ngroups] or null: the batch's gradient-norm statistic supplied from outside (a batch that is
-    int ngroups;                     //   sharded over several GPUs, all-reduced between the launches): the SUM of |score| over all its
-    float gn_rows;                   //   rows when gn_rows > 0 (= that row count), else the mean itself
-    // head-split plan (GP_PLAN_HEADSPLIT): workgroup 3 t + h evaluates head h of 16-row tile t and owns components 3 h .. 3 h + 2 of the
-    // score.  THREE workgroups read a tile's state and score and each writes a part of them, so nothing a launch reads may be written by
-    // the same launch: every step keeps its own copies in its row of `partials` (nparts = 21 * nrows floats per step):
-    //     [0, 3R)     sum of squares of row r's three components of head h at 3 r + h (a row's norm needs all nine: the NEXT launch puts
-    //                 sqrt(p[3r] + p[3r+1] + p[3r+2]) together and reduces it over its batch's rows)
-    //     [3R, 12R)   score_i [R][9], read by launch i + 1
-    //     [12R, 21R)  the state after launch i's update [R][9], read by launch i + 1 (launch 1 reads the initial state from `x`, which
-    //                 this plan never writes)
-    // (wgpg counts TILES per group.)
-};
+// PcArgs: pc_rows.h (the argument block of every plan; the wave-level front and back end of the chain plans live there too)
 
 // Kernel for step i (0 <= i <= nsteps):
 //   i > 0      : finish step i-1 for the tile's rows (Langevin corrector + Euler-Maruyama predictor, samplers.py:129-152)
@@ -354,90 +334,18 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_kernel(PcArgs a
     const int wg_row0 = blockIdx.x * C::ROWS;
     gp_chain::State<PT> st;
     const float *tvec = a.tvec_all + (size_t)(i < a.nsteps ? i : 0) * HEADS;
-    int row[PT];
-#pragma unroll
-    for (int p = 0; p < PT; ++p) row[p] = wg_row0 + (wave * PT + p) * 16 + pt;
-    // ---- the rows' operands are requested first, the ring prologue behind them: one memory round trip covers both
-    float xv[PT][9], gr[PT][9], zz1[PT][9], zz2[PT][9], cen[PT][3];
-    float gdiff = 0.f, dt = 0.f, sqdt = 0.f, gn = 1.f, sigma = 1.f;
-#pragma unroll
-    for (int p = 0; p < PT; ++p) {
-        const int r = row[p] < a.nrows ? row[p] : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
-#pragma unroll
-        for (int j = 0; j < 9; ++j) xv[p][j] = a.x[(size_t)r * 9 + j];
-        if (i > 0) {
-            const float *z1 = a.z_lang + ((size_t)(i - 1) * a.nrows + r) * 9;
-            const float *z2 = a.z_pred + ((size_t)(i - 1) * a.nrows + r) * 9;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                gr[p][j] = a.score[(size_t)r * 9 + j];
-                zz1[p][j] = z1[j];
-                zz2[p][j] = z2[j];
-            }
-            const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
-            cen[p][0] = cp[0], cen[p][1] = cp[1], cen[p][2] = cp[2];
-        }
-    }
-    // memory returns in order: what the sampler update needs (row operands above, schedule, the batch's partial sums) is asked for
-    // first, the ring start-up behind it - the update then runs while the weights are still on their way
-    float psum[4] = {0.f, 0.f, 0.f, 0.f};
-    const int grp = blockIdx.x / a.wgpg;
-    const float *pp = a.partials + (size_t)(i > 0 ? i - 1 : 0) * a.nparts + (size_t)grp * a.ppg;
-    if (i > 0) {
-        const float *sc = a.sched + (size_t)(i - 1) * 4;
-        gdiff = sc[1], dt = sc[2], sqdt = sc[3];
-        if (a.gn_ext) {
-            gn = a.gn_ext[(size_t)(i - 1) * a.ngroups + grp];
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) psum[u] = lane + 64 * u < a.ppg ? pp[lane + 64 * u] : 0.f;
-        }
-    }
+    // ---- the rows' operands are requested first, the ring prologue behind them: one memory round trip covers both (PcRows, pc_rows.h)
+    PcRows<PT> rs;
+    rs.template request<gp_chain::NW>(a, wave, lane);
+    auto &xv = rs.xv;
+    const float sigma = rs.sigma;
     gp_chain::Staged<PT> sg;
-    if (i < a.nsteps) {
-        sigma = a.sched[(size_t)i * 4 + 0];
-        gp_chain::begin_request<PT>(st, sg, net, a.cvec, tvec, wg_row0, a.nrows, a.kcand);
-    }
+    if (i < a.nsteps) gp_chain::begin_request<PT>(st, sg, net, a.cvec, tvec, wg_row0, a.nrows, a.kcand);
     __builtin_amdgcn_sched_barrier(0);
-    if (i > 0) {
-        if (a.gn_ext) {
-            if (a.gn_rows > 0.f) gn = gn / a.gn_rows;
-        } else {
-            float s = ((psum[0] + psum[1]) + psum[2]) + psum[3];  // the order of `for (q = lane; q < ppg; q += 64) s += pp[q]`
-            for (int q = lane + 256; q < a.ppg; q += 64) s += pp[q];
-            gn = wave_sum_f32(s) / (float)a.rows_per_group;
-        }
-    }
-    f32x4 xf[PT];
-    if (i > 0) {
-#pragma unroll
-        for (int p = 0; p < PT; ++p) {
-            float mx[9];
-            pc_update_row(xv[p], gr[p], zz1[p], zz2[p], gn, gdiff, dt, sqdt, mx);
-            if (row[p] < a.nrows && g == 0) {
-                const int r = row[p];
-                if (a.traj) {
-                    float *tr = a.traj + ((size_t)(i - 1) * a.nrows + r) * 9;
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) tr[j] = xv[p][j];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) tr[6 + j] = xv[p][6 + j] + cen[p][j];
-                }
-#pragma unroll
-                for (int j = 0; j < 9; ++j) a.x[(size_t)r * 9 + j] = xv[p][j];
-                if (i == a.nsteps) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) mx[6 + j] += cen[p][j];
-                    normalize_rot6(mx);
-#pragma unroll
-                    for (int j = 0; j < 9; ++j) a.mean_x[(size_t)r * 9 + j] = mx[j];
-                }
-            }
-        }
-        if (i == a.nsteps) return;
-    }
+    if (rs.finish_previous(a, lane)) return;
     __builtin_amdgcn_sched_barrier(0);
     gp_chain::begin_deposit<PT>(sg, lds);
+    f32x4 xf[PT];
 #pragma unroll
     for (int p = 0; p < PT; ++p) xf[p] = gp_chain::pose_fragment(xv[p], g);
     float f[PT][POSE];
@@ -459,6 +367,8 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_kernel(PcArgs a
 #pragma unroll
             for (int j = 0; j < POSE; ++j) gx9[p][j] = __shfl(gx[p][j & 3], pt + 16 * (j >> 2), 64);
     }
+    // (pc_rows.h's pc_store_score / pc_store_partial written out, in their order: through the helpers this kernel allocates one more
+    // accumulator register and spills one more)
     float nsum = 0.f;
 #pragma unroll
     for (int p = 0; p < PT; ++p) {
@@ -468,19 +378,14 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_kernel(PcArgs a
             sc9[j] = MODEL == 0 ? f[p][j] / (sigma + 1e-7f) : f[p][j] / sigma + gx9[p][j];
             q += sc9[j] * sc9[j];
         }
-        if (row[p] < a.nrows && g == 0) {
+        if (rs.row[p] < a.nrows && g == 0) {
 #pragma unroll
-            for (int j = 0; j < 9; ++j) a.score[(size_t)row[p] * 9 + j] = sc9[j];
+            for (int j = 0; j < 9; ++j) a.score[(size_t)rs.row[p] * 9 + j] = sc9[j];
             nsum += sqrtf(q);
         }
     }
     nsum = wave_sum_f32(nsum);
     if (lane == 0) a.partials[(size_t)i * a.nparts + (size_t)blockIdx.x * gp_chain::NW + wave] = nsum;
-}
-
-template <typename K>
-int set_lds(K kern, size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? GP_OK : GP_ELAUNCH;
 }
 
 }  // namespace
@@ -631,13 +536,9 @@ int gp_pc_step_plan(int model, int tile, int ngroups, int nclouds_per_group, int
         if (gn_ext) return GP_EINVAL;  // a sharded batch's callers sum whole-tile partials between the launches: tile plans only
         P = 16;
     }
-    PcArgs a;
-    a.nrows = R, a.kcand = k, a.step = step, a.nsteps = nsteps;
-    a.nparts = nparts, a.ppg = nparts / ngroups, a.rows_per_group = rg;
-    a.wgpg = (rg + pc_rows_per_wg(P) - 1) / pc_rows_per_wg(P);
-    a.cvec = cvec, a.tvec_all = tvec_all, a.sched = sched, a.z_lang = z_langevin, a.z_pred = z_predictor, a.centre = centre;
-    a.x = x, a.mean_x = mean_x, a.score = score, a.partials = partials, a.traj = traj;
-    a.gn_ext = gn_ext, a.ngroups = ngroups, a.gn_rows = (float)gn_rows_total;
+    const int wgpg = (rg + pc_rows_per_wg(P) - 1) / pc_rows_per_wg(P);
+    const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, wgpg, cvec, tvec_all, sched, z_langevin, z_predictor, centre, x, mean_x, score, partials,
+                             traj, gn_ext, gn_rows_total);
     hipStream_t st = (hipStream_t)s;
     const int nwg = a.wgpg * ngroups;
     if (P == 128) return model == 1 ? launch_pc_chain<2, 1>(a, net, nwg, st) : launch_pc_chain<2, 0>(a, net, nwg, st);

@@ -2,7 +2,7 @@
 // network's three dense layers as EXACT-PRODUCT split-bf16 on the BF16 matrix pipe (bf16x9.h): every fp32 operand is hi + mid + lo,
 // all nine cross products are exact in fp32 and only the fp32 accumulation rounds - the error class of pc_step_chain_kernel<2, 0>
 // (trunk_chain.h), which stays selectable (PCSampler(trunk="f32mfma")).  Same job, inputs and partials contract as that kernel:
-// sampler update -> pose encoder -> three 256-wide heads -> fp32 Linear(256, 3) outputs on the accumulators -> one partial sum of
+// sampler update (PcRows, pc_rows.h: the sampler contract is there) -> pose encoder -> three 256-wide heads -> fp32 Linear(256, 3) outputs on the accumulators -> one partial sum of
 // |score| per WAVE (gp_pc_layout's plan 128: four per workgroup) -> x / mean_x / trajectory; cross-rank coupling (gn_ext) and ragged
 // last workgroups as there.
 //
@@ -20,46 +20,19 @@
 // Measured (MI355X, 32 000 rows, rocprofv3): 118.0 us per launch against 142.7 us for pc_step_chain_kernel<2, 0>; the rest of the gap to
 // the 63 us floor is barrier drains (one wave per SIMD), the head epilogues (not overlapped with MFMAs) and a few spilled registers.
 #include "bf16x9.h"
-#include "score_trunk.h"
+#include "pc_rows.h"
 #include "trunk_chain.h"
 
 namespace {
 
 using namespace gp_trunk;
 using namespace gp_bf16x9;
+using namespace gp_split;
 
-struct PcX9Args {
-    int nrows, kcand, step, nsteps;
-    int nparts, ppg, rows_per_group, wgpg;  // as PcArgs (scorenet.hip): one partial per wave, nparts from gp_pc_layout(0, 128, ...)
-    const float *cvec, *tvec_all, *sched, *z_lang, *z_pred, *centre;
-    float *x, *mean_x, *score, *partials, *traj;
-    const float *gn_ext;  // [nsteps][ngroups] or null: the batch's statistic from outside (sum over gn_rows rows when gn_rows > 0)
-    int ngroups;
-    float gn_rows;
-    const bf16x8 *w0;  // pose_encoder.0 [1][16][3][64]   k = component index (natural order, zero padded to 32)
-    const bf16x8 *w2;  // pose_encoder.2 [8][16][3][64]   k order of the register chain (weights.pack_bf16x9)
-    const bf16x8 *wh;  // stacked heads  [8][48][3][64]
-    const float *b0, *b2, *w_out, *b_out;  // fp32: biases [256], [256]; output layers [9][256], [9]
-};
-
-constexpr int X9_NW = 4, X9_NT = 64 * X9_NW, X9_RT = 2, X9_ROWS = 16 * X9_RT * X9_NW, X9_NCL = 4;
-constexpr int X9_SLICE = 16 * 3 * 64;  // bf16x8 (16 B) per slice = 48 KB
-constexpr int X9_PER_T = X9_SLICE / X9_NT;
-constexpr int X9_NSLICES = 33;
+constexpr int X9_NW = 4, X9_NT = 64 * X9_NW, X9_RT = 2, X9_ROWS = 16 * X9_RT * X9_NW;
+using X9Lds = SplitLds<3, 2>;  // 2 slots of 48 KB
+constexpr int X9_SLICE = X9Lds::SLICE, X9_PER_T = X9_SLICE / X9_NT;
 static_assert(X9_ROWS == 128 && X9_PER_T <= 16, "one slice element per thread and output chunk at most");
-// LDS (floats): ring [2][SLICE] bf16x8 | w_out [9][256] | b0 [256] | b2 [256] | cvt [NCL][768] = cvec[cloud] + tvec
-constexpr int X9_OFF_WOUT = 2 * X9_SLICE * 4, X9_OFF_B0 = X9_OFF_WOUT + POSE * HID, X9_OFF_B2 = X9_OFF_B0 + HID, X9_OFF_CVT = X9_OFF_B2 + HID,
-              X9_TOTAL = X9_OFF_CVT + X9_NCL * HEADS;
-constexpr size_t X9_LDS_BYTES = (size_t)X9_TOTAL * sizeof(float);
-static_assert(X9_LDS_BYTES <= 160 * 1024, "LDS");
-
-__device__ __forceinline__ const bf16x8 *x9_slice(const PcX9Args &a, int s) {
-    s = s < X9_NSLICES ? s : X9_NSLICES - 1;  // the ring runs ahead: requests past the end re-read the last slice (never used)
-    if (s == 0) return a.w0;
-    if (s <= 8) return a.w2 + (size_t)(s - 1) * X9_SLICE;
-    const int h = (s - 9) >> 3, kb = (s - 9) & 7;
-    return a.wh + ((size_t)kb * 48 + 16 * h) * 3 * 64;
-}
 
 // End of a ring step: this wave's LDS writes of the step have completed (lgkmcnt), then the bare barrier.  No vmcnt wait: the
 // slice in flight to the registers may stay in flight across it.  The empty asm statements keep LDS accesses on their side.
@@ -69,104 +42,26 @@ __device__ __forceinline__ void x9_barrier() {
     asm volatile("" ::: "memory");
 }
 
-__global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcX9Args a) {
+__global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a, SplitNet w) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     bf16x8 *ring = reinterpret_cast<bf16x8 *>(lds);
-    float *woutl = lds + X9_OFF_WOUT, *b0l = lds + X9_OFF_B0, *b2l = lds + X9_OFF_B2, *cvtl = lds + X9_OFF_CVT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), pt = lane & 15, g = lane >> 4, i = a.step;
+    const float *woutl = lds + X9Lds::OFF_WOUT, *b0l = lds + X9Lds::OFF_B0, *b2l = lds + X9Lds::OFF_B2, *cvtl = lds + X9Lds::OFF_CVT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, i = a.step;
     const int wg_row0 = blockIdx.x * X9_ROWS;
-    int row[X9_RT];
-#pragma unroll
-    for (int p = 0; p < X9_RT; ++p) row[p] = wg_row0 + (wave * X9_RT + p) * 16 + pt;
     // ---- the rows' operands first, the ring prologue behind them (memory returns in order)
-    float xv[X9_RT][9], gr[X9_RT][9], zz1[X9_RT][9], zz2[X9_RT][9], cen[X9_RT][3];
-    float gdiff = 0.f, dt = 0.f, sqdt = 0.f, gn = 1.f, sigma = 1.f;
-#pragma unroll
-    for (int p = 0; p < X9_RT; ++p) {
-        const int r = row[p] < a.nrows ? row[p] : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
-#pragma unroll
-        for (int j = 0; j < 9; ++j) xv[p][j] = a.x[(size_t)r * 9 + j];
-        if (i > 0) {
-            const float *z1 = a.z_lang + ((size_t)(i - 1) * a.nrows + r) * 9;
-            const float *z2 = a.z_pred + ((size_t)(i - 1) * a.nrows + r) * 9;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                gr[p][j] = a.score[(size_t)r * 9 + j];
-                zz1[p][j] = z1[j];
-                zz2[p][j] = z2[j];
-            }
-            const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
-            cen[p][0] = cp[0], cen[p][1] = cp[1], cen[p][2] = cp[2];
-        }
-    }
-    float psum[4] = {0.f, 0.f, 0.f, 0.f};
-    const int grp = blockIdx.x / a.wgpg;
-    const float *pp = a.partials + (size_t)(i > 0 ? i - 1 : 0) * a.nparts + (size_t)grp * a.ppg;
-    if (i > 0) {
-        const float *sc = a.sched + (size_t)(i - 1) * 4;
-        gdiff = sc[1], dt = sc[2], sqdt = sc[3];
-        if (a.gn_ext) {
-            gn = a.gn_ext[(size_t)(i - 1) * a.ngroups + grp];
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) psum[u] = lane + 64 * u < a.ppg ? pp[lane + 64 * u] : 0.f;
-        }
-    }
+    PcRows<X9_RT> rs;
+    rs.request<X9_NW>(a, wave, lane);
     // slice 0 (-> slot 0 below) and slice 1 (-> registers, written during step 0)
     bf16x8 first[X9_PER_T], hold[X9_PER_T];
     if (i < a.nsteps) {
-        sigma = a.sched[(size_t)i * 4 + 0];
 #pragma unroll
-        for (int u = 0; u < X9_PER_T; ++u) first[u] = x9_slice(a, 0)[tid + u * X9_NT];
+        for (int u = 0; u < X9_PER_T; ++u) first[u] = split_slice<3>(w, 0)[tid + u * X9_NT];
 #pragma unroll
-        for (int u = 0; u < X9_PER_T; ++u) hold[u] = x9_slice(a, 1)[tid + u * X9_NT];
+        for (int u = 0; u < X9_PER_T; ++u) hold[u] = split_slice<3>(w, 1)[tid + u * X9_NT];
     }
-    if (i > 0) {
-        if (a.gn_ext) {
-            if (a.gn_rows > 0.f) gn = gn / a.gn_rows;
-        } else {
-            float s = ((psum[0] + psum[1]) + psum[2]) + psum[3];  // pc_step_chain_kernel's order
-            for (int q = lane + 256; q < a.ppg; q += 64) s += pp[q];
-            gn = wave_sum_f32(s) / (float)a.rows_per_group;
-        }
-#pragma unroll
-        for (int p = 0; p < X9_RT; ++p) {
-            float mx[9];
-            pc_update_row(xv[p], gr[p], zz1[p], zz2[p], gn, gdiff, dt, sqdt, mx);
-            if (row[p] < a.nrows && g == 0) {
-                const int r = row[p];
-                if (a.traj) {
-                    float *tr = a.traj + ((size_t)(i - 1) * a.nrows + r) * 9;
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) tr[j] = xv[p][j];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) tr[6 + j] = xv[p][6 + j] + cen[p][j];
-                }
-#pragma unroll
-                for (int j = 0; j < 9; ++j) a.x[(size_t)r * 9 + j] = xv[p][j];
-                if (i == a.nsteps) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) mx[6 + j] += cen[p][j];
-                    normalize_rot6(mx);
-#pragma unroll
-                    for (int j = 0; j < 9; ++j) a.mean_x[(size_t)r * 9 + j] = mx[j];
-                }
-            }
-        }
-        if (i == a.nsteps) return;
-    }
+    if (rs.finish_previous(a, lane)) return;
     // ---- staged epilogue operands and slot 0
-    for (int e = tid; e < POSE * HID; e += X9_NT) woutl[e] = a.w_out[e];
-    for (int e = tid; e < HID; e += X9_NT) b0l[e] = a.b0[e], b2l[e] = a.b2[e];
-    {
-        const float *tvec = a.tvec_all + (size_t)i * HEADS;
-        const int cloud0 = wg_row0 / a.kcand, last_cloud = (a.nrows - 1) / a.kcand;
-        for (int e = tid; e < X9_NCL * HEADS; e += X9_NT) {
-            const int c = e / HEADS, o = e - c * HEADS;
-            const int cl = cloud0 + c < last_cloud ? cloud0 + c : last_cloud;
-            cvtl[e] = a.cvec[(size_t)cl * HEADS + o] + tvec[o];
-        }
-    }
+    split_stage<X9_NT, X9Lds>(lds, w, a.cvec, a.tvec_all + (size_t)i * HEADS, wg_row0, a.nrows, a.kcand);
 #pragma unroll
     for (int u = 0; u < X9_PER_T; ++u) ring[tid + u * X9_NT] = first[u];
     __syncthreads();
@@ -178,15 +73,15 @@ __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcX9Args
     auto ring_step = [&](const Split8 (&xs)[X9_RT]) {
         const bf16x8 *slot = ring + (gstep & 1) * X9_SLICE;
         bf16x8 *dst = ring + ((gstep + 1) & 1) * X9_SLICE;
-        const bf16x8 *src = x9_slice(a, gstep + 2);
-        bf16x8 w[2][3];
+        const bf16x8 *src = split_slice<3>(w, gstep + 2);
+        bf16x8 wf[2][3];
 #pragma unroll
-        for (int t = 0; t < 3; ++t) w[0][t] = slot[t * 64 + lane];
+        for (int t = 0; t < 3; ++t) wf[0][t] = slot[t * 64 + lane];
 #pragma unroll
         for (int n = 0; n < 16; ++n) {
             if (n + 1 < 16) {
 #pragma unroll
-                for (int t = 0; t < 3; ++t) w[(n + 1) & 1][t] = slot[((n + 1) * 3 + t) * 64 + lane];
+                for (int t = 0; t < 3; ++t) wf[(n + 1) & 1][t] = slot[((n + 1) * 3 + t) * 64 + lane];
             }
             if (n < X9_PER_T) {
                 dst[tid + n * X9_NT] = hold[n];
@@ -195,7 +90,7 @@ __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcX9Args
             f32x4 an[X9_RT];
 #pragma unroll
             for (int p = 0; p < X9_RT; ++p) an[p] = acc[p][n];
-            mma9<X9_RT>(w[n & 1], xs, an);
+            mma9<X9_RT>(wf[n & 1], xs, an);
 #pragma unroll
             for (int p = 0; p < X9_RT; ++p) acc[p][n] = an[p];
             __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the step
@@ -229,14 +124,13 @@ __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcX9Args
             ring_step(xs);
         }
     };
-    // ---- pose_encoder.0: the row's nine components as the one (zero-padded) k-block, natural k order: lane group g holds k = 8g .. 8g+7
+    // ---- pose_encoder.0
     {
         Split8 xs[X9_RT];
 #pragma unroll
         for (int p = 0; p < X9_RT; ++p) {
-            f32x4 pa = {0.f, 0.f, 0.f, 0.f}, pb = {0.f, 0.f, 0.f, 0.f};
-            if (g == 0) pa = f32x4{xv[p][0], xv[p][1], xv[p][2], xv[p][3]}, pb = f32x4{xv[p][4], xv[p][5], xv[p][6], xv[p][7]};
-            if (g == 1) pa = f32x4{xv[p][8], 0.f, 0.f, 0.f};
+            f32x4 pa, pb;
+            split_pose_fragment(rs.xv[p], g, pa, pb);
             xs[p] = split8(pa, pb);
         }
         zero_acc();
@@ -250,17 +144,19 @@ __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcX9Args
     int cl[X9_RT];
 #pragma unroll
     for (int p = 0; p < X9_RT; ++p) {
-        const int r = row[p] < a.nrows ? row[p] : a.nrows - 1;
+        const int r = rs.row[p] < a.nrows ? rs.row[p] : a.nrows - 1;
         cl[p] = r / a.kcand - wg_row0 / a.kcand;  // < NCL (gp_pc_layout admits k only when a workgroup's rows span <= NCL clouds)
     }
     // each head's three score components are final once its epilogue is done: stored there, their squares summed in component order
-    const float sden = sigma + 1e-7f;
+    const float sden = rs.sigma + 1e-7f;
     float q[X9_RT] = {};
 #pragma unroll 1
     for (int h = 0; h < 3; ++h) {
         layer();
 #pragma unroll
         for (int p = 0; p < X9_RT; ++p) {
+            // (bf16_split_common.h's split_head_out written out: through the helper this kernel, which sits on the register cliff,
+            // compiles to 168 spilled registers instead of 27)
             float o0 = 0.f, o1 = 0.f, o2 = 0.f;
 #pragma unroll
             for (int n = 0; n < 16; ++n) {
@@ -274,22 +170,12 @@ __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcX9Args
                 o2 += v.x * w2.x + v.y * w2.y + v.z * w2.z + v.w * w2.w;
             }
             // the four lane groups hold the four channel quarters: fixed order, every lane gets the sum
-            const float sc[3] = {(lane_groups_sum(o0) + a.b_out[3 * h + 0]) / sden, (lane_groups_sum(o1) + a.b_out[3 * h + 1]) / sden,
-                                 (lane_groups_sum(o2) + a.b_out[3 * h + 2]) / sden};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) q[p] += sc[c] * sc[c];
-            if (row[p] < a.nrows && g == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) a.score[(size_t)row[p] * 9 + 3 * h + c] = sc[c];
-            }
+            const float sc[3] = {(lane_groups_sum(o0) + w.b_out[3 * h + 0]) / sden, (lane_groups_sum(o1) + w.b_out[3 * h + 1]) / sden,
+                                 (lane_groups_sum(o2) + w.b_out[3 * h + 2]) / sden};
+            pc_store_score(a, rs.row[p], lane, 3 * h, sc, q[p]);
         }
     }
-    float nsum = 0.f;
-#pragma unroll
-    for (int p = 0; p < X9_RT; ++p)
-        if (row[p] < a.nrows && g == 0) nsum += sqrtf(q[p]);
-    nsum = wave_sum_f32(nsum);
-    if (lane == 0) a.partials[(size_t)i * a.nparts + (size_t)blockIdx.x * X9_NW + wave] = nsum;
+    pc_store_partial<X9_RT, X9_NW>(a, rs.row, q, wave, lane);
 }
 
 }  // namespace
@@ -309,23 +195,16 @@ int gp_pc_step_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int n
     const int rc = gp_pc_layout(0, X9_ROWS, ngroups, nclouds_per_group, k, &P, &nparts);  // the chain plan's rules and partials size
     if (rc != GP_OK) return rc;
     if (P != X9_ROWS || !gp_chain::Cfg<2>::fits(k)) return GP_EINVAL;
-    PcX9Args a;
-    a.nrows = ngroups * rg, a.kcand = k, a.step = step, a.nsteps = nsteps;
-    a.wgpg = (rg + X9_ROWS - 1) / X9_ROWS, a.nparts = nparts, a.ppg = nparts / ngroups, a.rows_per_group = rg;
-    a.cvec = cvec, a.tvec_all = tvec_all, a.sched = sched, a.z_lang = z_langevin, a.z_pred = z_predictor, a.centre = centre;
-    a.x = x, a.mean_x = mean_x, a.score = score, a.partials = partials, a.traj = traj;
-    a.gn_ext = gn_ext, a.ngroups = ngroups, a.gn_rows = (float)gn_rows_total;
-    a.w0 = reinterpret_cast<const bf16x8 *>(w_pose0_x9), a.w2 = reinterpret_cast<const bf16x8 *>(w_pose2_x9),
-    a.wh = reinterpret_cast<const bf16x8 *>(w_headx_x9);
-    a.b0 = net->b_pose0, a.b2 = net->b_pose2, a.w_out = net->w_out, a.b_out = net->b_out;
+    const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, (rg + X9_ROWS - 1) / X9_ROWS, cvec, tvec_all, sched, z_langevin, z_predictor, centre, x,
+                             mean_x, score, partials, traj, gn_ext, gn_rows_total);
+    const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
+                        reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
     static bool done = false;
     if (!done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pc_step_chain_kernel_bf16x9), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)X9_LDS_BYTES) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(pc_step_chain_kernel_bf16x9, X9Lds::BYTES)) return GP_ELAUNCH;
         done = true;
     }
-    hipLaunchKernelGGL(pc_step_chain_kernel_bf16x9, dim3(a.wgpg * ngroups), dim3(X9_NT), X9_LDS_BYTES, (hipStream_t)s, a);
+    hipLaunchKernelGGL(pc_step_chain_kernel_bf16x9, dim3(a.wgpg * ngroups), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
     return gp_launch_status();
 }
 

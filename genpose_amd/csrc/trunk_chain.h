@@ -195,7 +195,6 @@ __device__ __forceinline__ void ring_barrier() {
     asm volatile("" ::: "memory");
 }
 
-__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
 __device__ __forceinline__ float dot4(const f32x4 &v, const f32x4 &w) { return v.x * w.x + v.y * w.y + v.z * w.z + v.w * w.w; }
 
 // operands of a head epilogue in flight between the slots of a ring step

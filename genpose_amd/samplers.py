@@ -116,21 +116,18 @@ class PCSampler:
 
     def launch_step(self, i):
         """Launch i of the chain (0 <= i <= n) on the current stream: finishes step i-1 and, for i < n, evaluates the score at t_i."""
+        shape = (self.groups, self.B // self.groups, self.K, i, self.n)
+        bufs = (ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x),
+                ptr(self.score), ptr(self.partials), ptr(self.traj))
+        gn = (ptr(self.gn_ext), self.gn_rows)
         if self.precision == "bf16x3":
             t = self.net.w.tensors
-            _lib.call("gp_pc_step_bf16x3", self.groups, self.B // self.groups, self.K, i, self.n, ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched),
-                      ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x), ptr(self.score), ptr(self.partials), ptr(self.traj),
-                      ptr(self._bf[0]), ptr(self._bf[1]), ptr(self._bf[2]), ptr(t["b_pose0"]), ptr(t["b_pose2"]), ptr(t["w_out"]), ptr(t["b_out"]),
-                      stream_ptr())
-            return
-        if self.trunk == "bf16x9":
-            _lib.call("gp_pc_step_bf16x9", self.groups, self.B // self.groups, self.K, i, self.n, self.net.w.ref(), ptr(self.cvec), ptr(self.tvec_all),
-                      ptr(self.sched), ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x), ptr(self.score), ptr(self.partials),
-                      ptr(self.traj), ptr(self.gn_ext), self.gn_rows, ptr(self._x9[0]), ptr(self._x9[1]), ptr(self._x9[2]), stream_ptr())
-            return
-        _lib.call("gp_pc_step_plan", self.model, self.plan, self.groups, self.B // self.groups, self.K, i, self.n, self.net.w.ref(), ptr(self.cvec), ptr(self.tvec_all),
-                  ptr(self.sched), ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x), ptr(self.score), ptr(self.partials),
-                  ptr(self.traj), ptr(self.gn_ext), self.gn_rows, stream_ptr())
+            _lib.call("gp_pc_step_bf16x3", *shape, *bufs, *(ptr(w) for w in self._bf), ptr(t["b_pose0"]), ptr(t["b_pose2"]), ptr(t["w_out"]),
+                      ptr(t["b_out"]), stream_ptr())
+        elif self.trunk == "bf16x9":
+            _lib.call("gp_pc_step_bf16x9", *shape, self.net.w.ref(), *bufs, *gn, *(ptr(w) for w in self._x9), stream_ptr())
+        else:
+            _lib.call("gp_pc_step_plan", self.model, self.plan, *shape, self.net.w.ref(), *bufs, *gn, stream_ptr())
 
     def _launch_all(self):
         for i in range(self.n + 1):

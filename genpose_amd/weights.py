@@ -129,12 +129,22 @@ def pack_bf16x3(W, n_chunks, k_blocks, chain=True):
     input channel 32 kb + (4 g + e if e < 4 else 16 + 4 g + e - 4) - two consecutive D fragments of the previous layer, as the register
     chain of csrc/sa_bf16x3.hip holds them (chain=False: the natural order 32 kb + 8 g + e, for a layer whose input is not a D fragment).
     Out-of-range outputs / inputs are zero."""
-    W = W.detach().float().cpu()
-    n_out, k_in = W.shape
-    Wp = torch.zeros(16 * n_chunks, 32 * k_blocks)
-    Wp[:n_out, :k_in] = W
+    Wp = _pad_for_fragments(W, n_chunks, k_blocks)
     hi = Wp.to(torch.bfloat16)
     lo = (Wp - hi.float()).to(torch.bfloat16)
+    return _gather_fragments((hi, lo), n_chunks, k_blocks, chain)
+
+
+def _pad_for_fragments(W, n_chunks, k_blocks):
+    W = W.detach().float().cpu()
+    Wp = torch.zeros(16 * n_chunks, 32 * k_blocks)
+    Wp[:W.shape[0], :W.shape[1]] = W
+    return Wp
+
+
+def _gather_fragments(terms, n_chunks, k_blocks, chain):
+    """bf16 terms, each [16 n_chunks, 32 k_blocks] -> int16 [k_blocks][n_chunks][len(terms)][64][8] in pack_bf16x3's fragment order."""
+    terms = torch.stack([t.view(torch.int16) for t in terms], dim=0)
     lanes = torch.arange(64)
     n, g = lanes % 16, lanes // 16
     e = torch.arange(8)
@@ -142,14 +152,9 @@ def pack_bf16x3(W, n_chunks, k_blocks, chain=True):
         koff = torch.where(e < 4, 4 * g[:, None] + e[None, :], 16 + 4 * g[:, None] + (e[None, :] - 4))  # [64, 8]
     else:
         koff = 8 * g[:, None] + e[None, :]
-    out = torch.empty(k_blocks, n_chunks, 2, 64, 8, dtype=torch.int16)
-    for kb in range(k_blocks):
-        for nc in range(n_chunks):
-            rows = (16 * nc + n)[:, None].expand(64, 8)
-            cols = 32 * kb + koff
-            out[kb, nc, 0] = hi[rows, cols].view(torch.int16)
-            out[kb, nc, 1] = lo[rows, cols].view(torch.int16)
-    return out.contiguous()
+    rows = (16 * torch.arange(n_chunks)[None, :, None, None] + n[None, None, :, None]).expand(k_blocks, n_chunks, 64, 8)
+    cols = (32 * torch.arange(k_blocks)[:, None, None, None] + koff[None, None]).expand(k_blocks, n_chunks, 64, 8)
+    return terms[:, rows, cols].permute(1, 2, 0, 3, 4).contiguous()  # [terms][kb][nc][64][8] -> [kb][nc][terms][64][8]
 
 
 def split_bf16x9(W):
@@ -175,21 +180,7 @@ def split_bf16x9(W):
 def pack_bf16x9(W, n_chunks, k_blocks, chain=True):
     """W [n_out, k_in] f32 -> int16 [k_blocks][n_chunks][3 = hi, mid, lo][64 lanes][8]: pack_bf16x3's fragment order and k order with the
     three exact terms of split_bf16x9 (checked there: hi + mid + lo == W for every weight).  Out-of-range outputs / inputs are zero."""
-    W = W.detach().float().cpu()
-    n_out, k_in = W.shape
-    Wp = torch.zeros(16 * n_chunks, 32 * k_blocks)
-    Wp[:n_out, :k_in] = W
-    terms = torch.stack([t.view(torch.int16) for t in split_bf16x9(Wp)], dim=0)  # [3][16 n_chunks][32 k_blocks]
-    lanes = torch.arange(64)
-    n, g = lanes % 16, lanes // 16
-    e = torch.arange(8)
-    if chain:
-        koff = torch.where(e < 4, 4 * g[:, None] + e[None, :], 16 + 4 * g[:, None] + (e[None, :] - 4))  # [64, 8]
-    else:
-        koff = 8 * g[:, None] + e[None, :]
-    rows = (16 * torch.arange(n_chunks)[None, :, None, None] + n[None, None, :, None]).expand(k_blocks, n_chunks, 64, 8)
-    cols = (32 * torch.arange(k_blocks)[:, None, None, None] + koff[None, None]).expand(k_blocks, n_chunks, 64, 8)
-    return terms[:, rows, cols].permute(1, 2, 0, 3, 4).contiguous()  # [3][kb][nc][64][8] -> [kb][nc][3][64][8]
+    return _gather_fragments(split_bf16x9(_pad_for_fragments(W, n_chunks, k_blocks)), n_chunks, k_blocks, chain)
 
 
 class EncoderWeights:

@@ -56,3 +56,35 @@ def test_split_refuses_what_it_cannot_represent():
         Wb[3, 5] = bad
         with pytest.raises(ValueError):
             pack_bf16x9(Wb, 2, 1)
+
+
+def _slow_pack(terms, n_out, k_in, n_chunks, k_blocks, chain):
+    """The docstrings' definition, one element at a time: out[kb][nc][t][lane][e] = term t of W[16 nc + n][32 kb + koff(g, e)] with
+    lane = (n = lane % 16, g = lane // 16), koff = 4 g + e (e < 4) or 16 + 4 g + e - 4 for the register chain's k order, 8 g + e for
+    the natural one; zero outside W."""
+    out = torch.zeros(k_blocks, n_chunks, len(terms), 64, 8, dtype=torch.int16)
+    for kb in range(k_blocks):
+        for nc in range(n_chunks):
+            for lane in range(64):
+                n, g = lane % 16, lane // 16
+                for e in range(8):
+                    koff = (4 * g + e if e < 4 else 16 + 4 * g + e - 4) if chain else 8 * g + e
+                    r, c = 16 * nc + n, 32 * kb + koff
+                    if r < n_out and c < k_in:
+                        for t, term in enumerate(terms):
+                            out[kb, nc, t, lane, e] = term[r, c]
+    return out
+
+
+@pytest.mark.parametrize("shape,nc,kb,chain", [((768, 256), 48, 8, True), ((256, 9), 16, 1, False), ((37, 70), 3, 3, True)])
+def test_packs_match_the_per_element_definition(shape, nc, kb, chain):
+    from genpose_amd.weights import pack_bf16x3, pack_bf16x9, split_bf16x9
+    W = torch.randn(*shape, generator=torch.Generator().manual_seed(7))
+    hi = W.to(torch.bfloat16)
+    lo = (W - hi.float()).to(torch.bfloat16)
+    p3 = pack_bf16x3(W, nc, kb, chain=chain)
+    assert p3.shape == (kb, nc, 2, 64, 8) and p3.dtype == torch.int16 and p3.is_contiguous()
+    assert torch.equal(p3, _slow_pack([t.view(torch.int16) for t in (hi, lo)], *shape, nc, kb, chain))
+    p9 = pack_bf16x9(W, nc, kb, chain=chain)
+    assert p9.shape == (kb, nc, 3, 64, 8) and p9.dtype == torch.int16 and p9.is_contiguous()
+    assert torch.equal(p9, _slow_pack([t.view(torch.int16) for t in split_bf16x9(W)], *shape, nc, kb, chain))

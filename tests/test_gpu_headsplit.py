@@ -173,7 +173,7 @@ def test_split_plan_under_contention_is_bit_stable(nets):
     """Three workgroups serve a tile: each reads the tile's whole state and score and writes a part.  Nothing a launch reads may be
     written by the same launch (a sibling dispatched late - other streams own the CUs - would read what another has already written;
     an in-place version of this plan passed every quiet test and failed next to a busy encoder stream).  Every step therefore keeps
-    its own copies (PcArgs, csrc/scorenet.hip).  Here: the sampler's graph replayed while an encoder pass of 256 clouds hammers the chip
+    its own copies (PcArgs, csrc/pc_rows.h).  Here: the sampler's graph replayed while an encoder pass of 256 clouds hammers the chip
     on another stream, 20 times - every replay must give the bits of the undisturbed run; the RK45 driver likewise."""
     from genpose_amd import synth
     from genpose_amd.encoder import Pointnet2EncoderHIP
