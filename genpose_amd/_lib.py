@@ -71,6 +71,10 @@ SIGNATURES = {
     "gp_pc_layout_bf16x3": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "gp_pc_step_bf16x3": [c_int] * 5 + [P] * 18 + [P],
     "gp_pc_step_bf16x9": [c_int] * 5 + [NETP] + [P] * 12 + [c_int] + [P] * 3 + [P],
+    "gp_pc_step_plan_seeded": [c_int] * 6 + [NETP] + [P] * 11 + [c_int, P],
+    "gp_pc_step_bf16x9_seeded": [c_int] * 5 + [NETP] + [P] * 11 + [c_int] + [P] * 3 + [P],
+    "gp_pc_noise_fill": [P, c_int, c_int, c_int64, c_int64, P, P, P],
+    "gp_philox_raw": [c_int64, P, P, P, P],
     "gp_pc_step_grouped": [c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 11 + [P],
     "gp_pc_step_coupled": [c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 12 + [P],
     "gp_rk45_state_bytes": [],

@@ -11,6 +11,9 @@
 // The tile kernel pc_step_kernel<P, MODEL, SPLIT> (row work on tid < P, the norm through LDS) is a different shape: it shares PcArgs
 // and pc_update_row only.
 #pragma once
+#include <type_traits>
+
+#include "philox.h"
 #include "score_trunk.h"
 
 namespace gp_trunk {
@@ -21,7 +24,8 @@ struct PcArgs {
     int wgpg;                         // workgroups per group
     const float *cvec, *tvec_all;    // tvec_all [nsteps][768]
     const float *sched;              // [nsteps][4]: sigma(t_i), g(t_i), step_size, sqrt(step_size)  (f32, host schedule)
-    const float *z_lang, *z_pred;    // [nsteps][R][9]
+    const float *z_lang, *z_pred;    // [nsteps][R][9]; the SEEDED instantiations (philox.h) draw in registers instead and find their seed
+                                     //   state (gp_philox::SEED_WORDS words) behind z_lang, z_pred is null
     const float *centre;             // [R/k... per cloud][3]
     float *x, *mean_x, *score, *partials, *traj;  // x,mean_x,score [R,9]; partials [nsteps][nparts]; traj [nsteps][R][9] or null
     const float *gn_ext;             // [nsteps][ngroups] or null: the batch's gradient-norm statistic supplied from outside (a batch that is
@@ -56,10 +60,14 @@ static inline PcArgs pc_args(int ngroups, int rg, int k, int step, int nsteps, i
 // computed redundantly by the four groups - cheaper than any exchange), lane group 0 stores.  The three phases keep one issue order
 // on purpose (memory returns in order): request() asks for what the sampler update needs, the caller issues its ring prologue behind
 // it, finish_previous() then runs the update while the weights are still on their way.
-template <int PT>
+// SEEDED: the two 9-vectors of noise are not loaded but drawn (gp_philox::draw9: seed state behind a.z_lang, global row = its row base
+// + the row of the launch) right before the update - the same values gp_pc_noise_fill writes, the same update expression after them.
+struct PcNoSeed {};
+template <int PT, bool SEEDED = false>
 struct PcRows {
     int row[PT];
     float xv[PT][9], gr[PT][9], zz1[PT][9], zz2[PT][9], cen[PT][3];
+    typename std::conditional<SEEDED, gp_philox::Seed, PcNoSeed>::type seed;
     float gdiff, dt, sqdt, gn, sigma;
     float psum[4];    // the batch's first 256 partial sums, one per lane and quarter
     const float *pp;  // the batch's partial sums of step i-1
@@ -76,17 +84,25 @@ struct PcRows {
 #pragma unroll
             for (int j = 0; j < 9; ++j) xv[p][j] = a.x[(size_t)r * 9 + j];
             if (i > 0) {
-                const float *z1 = a.z_lang + ((size_t)(i - 1) * a.nrows + r) * 9;
-                const float *z2 = a.z_pred + ((size_t)(i - 1) * a.nrows + r) * 9;
+                if constexpr (SEEDED) {
 #pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    gr[p][j] = a.score[(size_t)r * 9 + j];
-                    zz1[p][j] = z1[j];
-                    zz2[p][j] = z2[j];
+                    for (int j = 0; j < 9; ++j) gr[p][j] = a.score[(size_t)r * 9 + j];
+                } else {
+                    const float *z1 = a.z_lang + ((size_t)(i - 1) * a.nrows + r) * 9;
+                    const float *z2 = a.z_pred + ((size_t)(i - 1) * a.nrows + r) * 9;
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) {
+                        gr[p][j] = a.score[(size_t)r * 9 + j];
+                        zz1[p][j] = z1[j];
+                        zz2[p][j] = z2[j];
+                    }
                 }
                 const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
                 cen[p][0] = cp[0], cen[p][1] = cp[1], cen[p][2] = cp[2];
             }
+        }
+        if constexpr (SEEDED) {
+            if (i > 0) seed = gp_philox::load_seed(reinterpret_cast<const uint32_t *>(a.z_lang));
         }
         const int grp = blockIdx.x / a.wgpg;
         pp = a.partials + (size_t)(i > 0 ? i - 1 : 0) * a.nparts + (size_t)grp * a.ppg;
@@ -124,6 +140,11 @@ struct PcRows {
 #pragma unroll
         for (int p = 0; p < PT; ++p) {
             float mx[9];
+            if constexpr (SEEDED) {
+                const uint64_t grow = seed.row_base + (uint64_t)(row[p] < a.nrows ? row[p] : a.nrows - 1);
+                gp_philox::draw9(seed, (uint32_t)(i - 1), gp_philox::STREAM_LANGEVIN, grow, zz1[p]);
+                gp_philox::draw9(seed, (uint32_t)(i - 1), gp_philox::STREAM_PREDICTOR, grow, zz2[p]);
+            }
             pc_update_row(xv[p], gr[p], zz1[p], zz2[p], gn, gdiff, dt, sqdt, mx);
             if (row[p] < a.nrows && g == 0) {
                 const int r = row[p];

@@ -172,8 +172,10 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void score_eval_chain_kernel(int n
 // tiles only.  The same kernel otherwise: sampling from the energy model is the same captured launch chain.
 // SPLIT: the head-split plan (see PcArgs): three workgroups per tile.  Each finishes step i-1 for all 16 rows (the update is row-local
 // and cheap; identical in the three, workgroup h = 0 stores) and evaluates ONE head of the score at t_i.
-template <int P, int MODEL, bool SPLIT = false>
-__global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_kernel(PcArgs a, gp_scorenet net) {
+// SEEDED (pc_step_seeded_kernel below): the rows' noise is not loaded from z_lang / z_pred but drawn in registers (philox.h; the seed
+// state sits behind a.z_lang) - everything after the draw is the same expression.
+template <int P, int MODEL, bool SPLIT, bool SEEDED>
+__device__ __forceinline__ void pc_step_tile(const PcArgs &a, const gp_scorenet &net) {
     static_assert(MODEL == 0 || P == gp_bwd::DP, "the backward pass runs on 16-row tiles");
     static_assert(!SPLIT || (MODEL == 0 && P == 16), "head-split: score model, 16-row tiles");
     using L = TrunkLds<P, MODEL == 1>;
@@ -207,14 +209,25 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_kernel(PcArgs a, gp_s
         if (tid < P) {
             const float *sc = a.sched + (size_t)(i - 1) * 4;
             g = sc[1], dt = sc[2], sqdt = sc[3];
-            const float *z1 = a.z_lang + ((size_t)(i - 1) * a.nrows + r) * 9;
-            const float *z2 = a.z_pred + ((size_t)(i - 1) * a.nrows + r) * 9;
+            if constexpr (SEEDED) {
 #pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                xv[j] = x_in[(size_t)r * 9 + j];
-                gr[j] = score_in[(size_t)r * 9 + j];
-                zz1[j] = z1[j];
-                zz2[j] = z2[j];
+                for (int j = 0; j < 9; ++j) {
+                    xv[j] = x_in[(size_t)r * 9 + j];
+                    gr[j] = score_in[(size_t)r * 9 + j];
+                }
+                const gp_philox::Seed sd = gp_philox::load_seed(reinterpret_cast<const uint32_t *>(a.z_lang));
+                gp_philox::draw9(sd, (uint32_t)(i - 1), gp_philox::STREAM_LANGEVIN, sd.row_base + (uint64_t)r, zz1);
+                gp_philox::draw9(sd, (uint32_t)(i - 1), gp_philox::STREAM_PREDICTOR, sd.row_base + (uint64_t)r, zz2);
+            } else {
+                const float *z1 = a.z_lang + ((size_t)(i - 1) * a.nrows + r) * 9;
+                const float *z2 = a.z_pred + ((size_t)(i - 1) * a.nrows + r) * 9;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    xv[j] = x_in[(size_t)r * 9 + j];
+                    gr[j] = score_in[(size_t)r * 9 + j];
+                    zz1[j] = z1[j];
+                    zz2[j] = z2[j];
+                }
             }
             const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
             cen[0] = cp[0], cen[1] = cp[1], cen[2] = cp[2];
@@ -319,6 +332,15 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_kernel(PcArgs a, gp_s
     }
 }
 
+template <int P, int MODEL, bool SPLIT = false>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_kernel(PcArgs a, gp_scorenet net) {
+    pc_step_tile<P, MODEL, SPLIT, false>(a, net);
+}
+template <int P, bool SPLIT = false>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_seeded_kernel(PcArgs a, gp_scorenet net) {
+    pc_step_tile<P, 0, SPLIT, true>(a, net);
+}
+
 // The same launch in the chain form (trunk_chain.h).  A wave owns 16 * PT rows from the sampler update to the score: every lane
 // of a row's four lane groups carries the row's 9-vector (the update is ~150 VALU instructions per wave, computed redundantly by
 // the four groups - cheaper than any exchange), lane group 0 stores.  One partial sum of |score| per WAVE; the batch-mean
@@ -326,8 +348,9 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_kernel(PcArgs a, gp_s
 // MODEL 1: the ENERGY network - its score, the gradient of the inner-product energy, from the forward + vector-Jacobian chain of
 // trunk_chain_vjp.h (cotangent u = x / sigma; score = f / sigma + J_f^T u, energynet.py:200-222) - what pc_step_kernel<16, 1> computes
 // per 16-row tile through LDS.
-template <int PT, int MODEL>
-__global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_kernel(PcArgs a, gp_scorenet net) {
+// SEEDED (pc_step_chain_seeded_kernel): PcRows draws the noise (pc_rows.h).
+template <int PT, int MODEL, bool SEEDED>
+__device__ __forceinline__ void pc_step_chain(const PcArgs &a, const gp_scorenet &net) {
     using C = gp_chain::Cfg<PT>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), pt = lane & 15, g = lane >> 4, i = a.step;
@@ -335,7 +358,7 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_kernel(PcArgs a
     gp_chain::State<PT> st;
     const float *tvec = a.tvec_all + (size_t)(i < a.nsteps ? i : 0) * HEADS;
     // ---- the rows' operands are requested first, the ring prologue behind them: one memory round trip covers both (PcRows, pc_rows.h)
-    PcRows<PT> rs;
+    PcRows<PT, SEEDED> rs;
     rs.template request<gp_chain::NW>(a, wave, lane);
     auto &xv = rs.xv;
     const float sigma = rs.sigma;
@@ -388,6 +411,15 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_kernel(PcArgs a
     if (lane == 0) a.partials[(size_t)i * a.nparts + (size_t)blockIdx.x * gp_chain::NW + wave] = nsum;
 }
 
+template <int PT, int MODEL>
+__global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_kernel(PcArgs a, gp_scorenet net) {
+    pc_step_chain<PT, MODEL, false>(a, net);
+}
+template <int PT>
+__global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_seeded_kernel(PcArgs a, gp_scorenet net) {
+    pc_step_chain<PT, 0, true>(a, net);
+}
+
 }  // namespace
 
 template <int PT>
@@ -401,6 +433,18 @@ static int launch_eval_chain(int R, int k, const gp_scorenet *net, const float *
     }
     hipLaunchKernelGGL((score_eval_chain_kernel<PT>), dim3((R + C::ROWS - 1) / C::ROWS), dim3(gp_chain::NT), C::LDS_BYTES, st, R, k, *net, cvec, tvec, x,
                        sigma_dev, mode, out);
+    return gp_launch_status();
+}
+
+template <int PT>
+static int launch_pc_chain_seeded(const PcArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
+    const size_t lds = gp_chain::Cfg<PT>::LDS_BYTES;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(pc_step_chain_seeded_kernel<PT>, lds)) return GP_ELAUNCH;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((pc_step_chain_seeded_kernel<PT>), dim3(nwg), dim3(gp_chain::NT), lds, st, a, *net);
     return gp_launch_status();
 }
 
@@ -561,6 +605,47 @@ int gp_pc_step_plan(int model, int tile, int ngroups, int nclouds_per_group, int
         hipLaunchKernelGGL((pc_step_kernel<64, 0>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
     else
         hipLaunchKernelGGL((pc_step_kernel<32, 0>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
+    return gp_launch_status();
+}
+
+int gp_pc_step_plan_seeded(int tile, int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
+                           const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
+                           float *partials, float *traj, const float *gn_ext, int gn_rows_total, gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || step < 0 || step > nsteps || (uint32_t)nsteps >= gp_philox::MAX_STEPS || !net || !cvec ||
+        !tvec_all || !sched || !seed_state || !centre || !x || !mean_x || !score || !partials || gn_rows_total < 0)
+        return GP_EINVAL;
+    const int rg = nclouds_per_group * k, R = ngroups * rg;
+    if (R == 0) return GP_OK;
+    int P = 0, nparts = 0;
+    const int rc = gp_pc_layout(0, tile, ngroups, nclouds_per_group, k, &P, &nparts);
+    if (rc != GP_OK) return rc;
+    const bool split = P == (16 | GP_PLAN_HEADSPLIT);
+    if (split) {
+        if (gn_ext) return GP_EINVAL;  // as gp_pc_step_plan
+        P = 16;
+    }
+    const int wgpg = (rg + pc_rows_per_wg(P) - 1) / pc_rows_per_wg(P);
+    // (the seed state travels in the argument block's z_lang slot: PcArgs)
+    const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, wgpg, cvec, tvec_all, sched, reinterpret_cast<const float *>(seed_state), nullptr, centre, x,
+                             mean_x, score, partials, traj, gn_ext, gn_rows_total);
+    hipStream_t st = (hipStream_t)s;
+    const int nwg = a.wgpg * ngroups;
+    if (P == 128) return launch_pc_chain_seeded<2>(a, net, nwg, st);
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(pc_step_seeded_kernel<16>, trunk_lds_bytes<16>()) || set_lds(pc_step_seeded_kernel<16, true>, trunk_lds_bytes<16>()) ||
+            set_lds(pc_step_seeded_kernel<32>, trunk_lds_bytes<32>()) || set_lds(pc_step_seeded_kernel<64>, trunk_lds_bytes<64>()))
+            return GP_ELAUNCH;
+        attr_done = true;
+    }
+    if (split)
+        hipLaunchKernelGGL((pc_step_seeded_kernel<16, true>), dim3(3 * nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
+    else if (P == 16)
+        hipLaunchKernelGGL((pc_step_seeded_kernel<16>), dim3(nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
+    else if (P == 64)
+        hipLaunchKernelGGL((pc_step_seeded_kernel<64>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
+    else
+        hipLaunchKernelGGL((pc_step_seeded_kernel<32>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
     return gp_launch_status();
 }
 

@@ -42,15 +42,17 @@ __device__ __forceinline__ void x9_barrier() {
     asm volatile("" ::: "memory");
 }
 
-__global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a, SplitNet w) {
+// SEEDED (pc_step_chain_seeded_kernel_bf16x9): PcRows draws the noise (pc_rows.h); the rest is the same text.
+template <bool SEEDED>
+__device__ __forceinline__ void pc_step_chain_bf16x9(const PcArgs &a, const SplitNet &w) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     bf16x8 *ring = reinterpret_cast<bf16x8 *>(lds);
     const float *woutl = lds + X9Lds::OFF_WOUT, *b0l = lds + X9Lds::OFF_B0, *b2l = lds + X9Lds::OFF_B2, *cvtl = lds + X9Lds::OFF_CVT;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, i = a.step;
     const int wg_row0 = blockIdx.x * X9_ROWS;
     // ---- the rows' operands first, the ring prologue behind them (memory returns in order)
-    PcRows<X9_RT> rs;
-    rs.request<X9_NW>(a, wave, lane);
+    PcRows<X9_RT, SEEDED> rs;
+    rs.template request<X9_NW>(a, wave, lane);
     // slice 0 (-> slot 0 below) and slice 1 (-> registers, written during step 0)
     bf16x8 first[X9_PER_T], hold[X9_PER_T];
     if (i < a.nsteps) {
@@ -178,6 +180,9 @@ __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a
     pc_store_partial<X9_RT, X9_NW>(a, rs.row, q, wave, lane);
 }
 
+__global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<false>(a, w); }
+__global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_seeded_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<true>(a, w); }
+
 }  // namespace
 
 extern "C" {
@@ -205,6 +210,34 @@ int gp_pc_step_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int n
         done = true;
     }
     hipLaunchKernelGGL(pc_step_chain_kernel_bf16x9, dim3(a.wgpg * ngroups), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
+    return gp_launch_status();
+}
+
+int gp_pc_step_bf16x9_seeded(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
+                             const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
+                             float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
+                             const void *w_headx_x9, gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || step < 0 || step > nsteps || (uint32_t)nsteps >= gp_philox::MAX_STEPS || !net || !cvec ||
+        !tvec_all || !sched || !seed_state || !centre || !x || !mean_x || !score || !partials || gn_rows_total < 0 || !w_pose0_x9 || !w_pose2_x9 ||
+        !w_headx_x9)
+        return GP_EINVAL;
+    const int rg = nclouds_per_group * k;
+    if (ngroups * rg == 0) return GP_OK;
+    int P = 0, nparts = 0;
+    const int rc = gp_pc_layout(0, X9_ROWS, ngroups, nclouds_per_group, k, &P, &nparts);
+    if (rc != GP_OK) return rc;
+    if (P != X9_ROWS || !gp_chain::Cfg<2>::fits(k)) return GP_EINVAL;
+    // (the seed state travels in the argument block's z_lang slot: PcArgs)
+    const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, (rg + X9_ROWS - 1) / X9_ROWS, cvec, tvec_all, sched,
+                             reinterpret_cast<const float *>(seed_state), nullptr, centre, x, mean_x, score, partials, traj, gn_ext, gn_rows_total);
+    const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
+                        reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
+    static bool done = false;
+    if (!done) {
+        if (set_lds(pc_step_chain_seeded_kernel_bf16x9, X9Lds::BYTES)) return GP_ELAUNCH;
+        done = true;
+    }
+    hipLaunchKernelGGL(pc_step_chain_seeded_kernel_bf16x9, dim3(a.wgpg * ngroups), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
     return gp_launch_status();
 }
 

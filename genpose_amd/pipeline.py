@@ -54,8 +54,12 @@ class PipelinedPCPredictor:
         # (sampler_streams > 1 puts several sampler chains in flight; measured SLOWER at the bench configuration:
         #  13.1 k vs 14.2 k poses/s - the chains contend for the same MFMA pipes and each step boundary gets longer)
         self.s_smp = [torch.cuda.Stream(self.dev, priority=-1) for _ in range(sampler_streams)] if overlap else [self.s_enc]
+        # cfg.sampler_seed (opt-in): noise drawn inside the step kernels.  Batch i of the run() call number c draws as global rows
+        # i * B*K .. with run index c - whatever launch it shares with other batches (PCSampler(seed=), run(row_base=))
+        self.seed = getattr(self.net.cfg, "sampler_seed", None)
+        self.runs = 0
         self.smp = [{self.G: PCSampler(self.net.pose_score_net, B, K, num_steps, self.dev, use_graph=True, record_traj=False, groups=self.G,
-                                       precision=self.net._pc_precision(B, K, groups=self.G))}
+                                       precision=self.net._pc_precision(B, K, groups=self.G), seed=self.seed)}
                     for _ in range(sampler_streams)]
         # furthest point sampling of the NEXT launch group runs on a side stream while the MFMA stages of the current group
         # own the chip: it is a latency-bound chain of 893 block-wide argmax steps per cloud (one workgroup per cloud, tiny
@@ -80,7 +84,7 @@ class PipelinedPCPredictor:
     def _sampler(self, j, g):
         if g not in self.smp[j]:  # ragged tail of a run: fewer batches in the last launch
             self.smp[j][g] = PCSampler(self.net.pose_score_net, self.B1 * g, self.K, self.n, self.dev, use_graph=True, record_traj=False, groups=g,
-                                       precision=self.net._pc_precision(self.B1 * g, self.K, groups=g))
+                                       precision=self.net._pc_precision(self.B1 * g, self.K, groups=g), seed=self.seed)
         return self.smp[j][g]
 
     def run(self, batches, prior_noise=None, noise=None, out=None):
@@ -88,6 +92,8 @@ class PipelinedPCPredictor:
         (scaled by sigma(1) here); noise: optional per-batch (z_langevin, z_predictor) draws (tests).
         Returns a list of pred_pose [B,K,9] float32 tensors (one per batch; written into `out[i]` when given)."""
         results = []
+        run_index = self.runs
+        self.runs += 1
         cur = torch.cuda.current_stream(self.dev)
         self.s_enc.wait_stream(cur)
         for st in self.s_smp:
@@ -158,8 +164,9 @@ class PipelinedPCPredictor:
                 else:
                     z1 = z2 = None
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if self.timing else None
+                seeded = {} if self.seed is None else dict(run_index=run_index, row_base=i0 * B1 * K)
                 _, mean_x = self._sampler(j, g).run(self.cvec[slot][:nb], self.centre[slot][:nb], x0, z1, z2, slot_free_event=self.ev_free[slot],
-                                                    graph_events=ev)
+                                                    graph_events=ev, **seeded)
                 mean_x = mean_x.reshape(g, B1, K, 9)
                 for q in range(g):
                     res = out[i0 + q] if out is not None else torch.empty(B1, K, 9, device=self.dev)
@@ -282,7 +289,10 @@ class FullPipelinePredictor:
 
     def _sampler(self, g):
         if g not in self._smp:
-            self._smp[g] = PCSampler(self.snet.pose_score_net, g * self.B, self.K, self.n, self.dev, use_graph=True, record_traj=False, groups=g)
+            # cfg.sampler_seed of the score agent (opt-in): noise drawn inside the step kernels; batch i of call number c draws as global
+            # rows i * B*K .. with run index c, whatever launch it shares (as PipelinedPCPredictor)
+            self._smp[g] = PCSampler(self.snet.pose_score_net, g * self.B, self.K, self.n, self.dev, use_graph=True, record_traj=False, groups=g,
+                                     seed=getattr(self.snet.cfg, "sampler_seed", None))
         return self._smp[g]
 
     def run(self, pts, prior_noise=None, noise=None):
@@ -290,25 +300,27 @@ class FullPipelinePredictor:
         prior_noise (tests): standard-normal draws [B*K,9]; noise (tests): (z_langevin, z_predictor) [n,B*K,9]."""
         if pts.shape[0] != self.B:
             raise ValueError(f"predictor built for {self.B} clouds got {pts.shape[0]}")
-        return self._run_group(pts, 1, prior_noise, noise)
+        self._runs = getattr(self, "_runs", 0) + 1
+        return self._run_group(pts, 1, prior_noise, noise, self._runs - 1, 0)
 
     def run_many(self, batches, prior_noise=None, noise=None):
         """batches: sequence of device tensors [B,1024,3] -> one result dict per batch (views into the launch group's tensors);
         `batches_per_launch` of them share every launch.  prior_noise / noise (tests): per-batch draws as in run()."""
         out = []
+        self._runs = getattr(self, "_runs", 0) + 1
         for i0 in range(0, len(batches), self.G):
             grp = list(batches[i0:i0 + self.G])
             g = len(grp)
             pts = grp[0] if g == 1 else torch.cat(grp, dim=0)
             pn = None if prior_noise is None else torch.cat([prior_noise[i0 + q].reshape(self.B * self.K, 9) for q in range(g)], dim=0)
             nz = None if noise is None else (torch.cat([noise[i0 + q][0] for q in range(g)], dim=1), torch.cat([noise[i0 + q][1] for q in range(g)], dim=1))
-            res = self._run_group(pts, g, pn, nz)
+            res = self._run_group(pts, g, pn, nz, self._runs - 1, i0 * self.B * self.K)
             for q in range(g):
                 sl = slice(q * self.B, (q + 1) * self.B)
                 out.append({k: (v[sl] if v is not None else None) for k, v in res.items()})
         return out
 
-    def _run_group(self, pts, g, prior_noise, noise):
+    def _run_group(self, pts, g, prior_noise, noise, run_index=0, row_base=0):
         from . import reward
         B, K = g * self.B, self.K
         cur = torch.cuda.current_stream(self.dev)
@@ -337,7 +349,9 @@ class FullPipelinePredictor:
             x0.copy_(prior_noise.reshape(B * K, 9))
         x0.mul_(SIGMA_MAX)
         z1, z2 = noise if noise is not None else (None, None)
-        _, mean_x = self._sampler(g).run(cvec, centre, x0, z1, z2)
+        smp = self._sampler(g)
+        seeded = {} if smp.seed is None else dict(run_index=run_index, row_base=row_base)
+        _, mean_x = smp.run(cvec, centre, x0, z1, z2, **seeded)
         pred = mean_x.reshape(B, K, 9).clone()
         # ---- energy of every candidate (posenet_agent.py:471-527: translations relative to the cloud centre), ranking, aggregation
         if self.side is not None:

@@ -138,13 +138,16 @@ class GFObjectPose:
                 raise ValueError("the PC sampler needs cfg.sampling_steps")
             x0 = self._prior_to_device((R, 9)) if init_x is None else init_x.float()
             coupling = getattr(self, "coupling_group", None)
-            key = ("pc", B, K, n, return_process, id(coupling) if coupling is not None else None)  # a coupled sampler is a different sampler
+            seed = getattr(self.cfg, "sampler_seed", None)  # opt-in: noise drawn inside the step kernels (PCSampler(seed=))
+            if seed is not None and noise is not None:
+                raise ValueError("cfg.sampler_seed and explicit noise= exclude each other")
+            key = ("pc", B, K, n, return_process, id(coupling) if coupling is not None else None, seed)  # a coupled sampler is a different sampler
             smp = self._samplers.get(key)
             if smp is None:
                 # self.coupling_group (optional, set by the caller): the batch is sharded over the ranks of that process group and
                 # the Langevin step size is taken over ALL of its rows (PCSampler, "faithful" multi-GPU mode)
                 smp = self._samplers[key] = PCSampler(self.pose_score_net, B, K, n, self.device, record_traj=return_process,
-                                                      coupling_group=coupling, precision=self._pc_precision(B, K, coupling))
+                                                      coupling_group=coupling, precision=self._pc_precision(B, K, coupling), seed=seed)
             z1, z2 = noise if noise is not None else (None, None)
             self.last_sampler = smp  # statistics / timing of the sampler that served the last call
             xs, res = smp.run(cvec, centre, x0, z1, z2)

@@ -26,7 +26,7 @@ class PCSampler:
     """Predictor-corrector sampler state for a fixed (B, K, num_steps): buffers + optional hipGraph of the whole loop."""
 
     def __init__(self, net, B, K, num_steps, device, use_graph=True, record_traj=False, groups=1, coupling_group=None, tile=0, model="score",
-                 precision="f32", trunk=None):
+                 precision="f32", trunk=None, seed=None, row_base=None):
         """B clouds in `groups` independent batches of B/groups clouds laid out back to back: one launch chain serves all of
         them, the batch-mean gradient norm (samplers.py:130-132) stays per batch (gp_pc_step_grouped).
 
@@ -40,6 +40,21 @@ class PCSampler:
             raise ValueError(f"{B} clouds do not split into {groups} equal batches")
         if model not in ("score", "energy"):
             raise ValueError(model)
+        # seed (OPT-IN; an integer, taken modulo 2^64): the noise of both streams is drawn inside the step kernels by a counter-based
+        # generator (csrc/philox.h: Philox4x32-10 + Box-Muller keyed by seed, run index, step, stream and GLOBAL row = row_base + row of
+        # the launch) instead of torch's device generator: no z1 / z2 buffers, and a row draws the same values under every launch plan,
+        # in any batch of a launch (the caller gives the launch the base of its first row) and on any shard.  The seed state lives in a
+        # small device buffer the captured launches read: one pinned-memory copy in stream order before each replay updates it.
+        # seed=None: nothing changes.
+        if seed is not None:
+            if precision == "bf16x3":
+                raise NotImplementedError("seed= with precision='bf16x3': the split-bf16x3 PC step has no seeded kernel")
+            if model == "energy":
+                raise NotImplementedError("seed= with model='energy': the energy model's PC step has no seeded kernel")
+            if coupling_group is not None and groups > 1:
+                raise NotImplementedError("seed= with coupling_group and groups > 1: one row base cannot place the shards of several batches")
+        elif row_base is not None:
+            raise ValueError("row_base= needs seed=")
         # precision 'bf16x3' (OPT-IN, exploratory; csrc/trunk_bf16x3.hip): the trunk's dense layers as three-term bf16 split products with
         # fp32 accumulation, 128-row workgroups.  Score model, no cross-rank coupling; never the default.
         if precision not in ("f32", "bf16x3"):
@@ -99,7 +114,16 @@ class PCSampler:
         f = lambda *s: torch.empty(*s, device=self.dev)
         self.x, self.mean_x, self.score = f(R, 9), f(R, 9), f(R, 9)
         self.partials = torch.zeros(num_steps, self.nparts, device=self.dev)
-        self.z1, self.z2 = f(num_steps, R, 9), f(num_steps, R, 9)
+        self.seed = None if seed is None else int(seed) % (1 << 64)
+        if self.seed is None:
+            self.z1, self.z2 = f(num_steps, R, 9), f(num_steps, R, 9)
+        else:
+            self.z1 = self.z2 = None
+            self.seed_state = torch.zeros(4, dtype=torch.int64, device=self.dev)  # gp_philox::SEED_WORDS uint32: seed, run index, row base, 0
+            self._seed_host = torch.zeros(4, dtype=torch.int64).pin_memory()
+            self._seed_ev = None
+            self.next_run_index = 0
+            self.last_run_index = None
         self.cvec, self.centre = f(B, 768), f(B, 3)
         self.traj = f(num_steps, R, 9) if record_traj else None
         self.coupling_group = coupling_group
@@ -113,13 +137,52 @@ class PCSampler:
             use_graph = use_graph and dist.get_backend(coupling_group) == "nccl"  # an RCCL all-reduce is graph-capturable, a gloo one is not
         self.use_graph = use_graph
         self.graph = None
+        if self.seed is not None:
+            # a shard of a batch draws the rows it holds of the unsharded batch
+            rank = self._dist.get_rank(coupling_group) if coupling_group is not None else 0
+            self.row_base = int(row_base) if row_base is not None else rank * R
+
+    def reseed(self, seed):
+        """A new seed for the following runs (the run index starts again at 0); captured launches follow it."""
+        if self.seed is None:
+            raise ValueError("reseed() on a sampler built without seed=")
+        self.seed = int(seed) % (1 << 64)
+        self.next_run_index = 0
+
+    def _write_seed_state(self, run_index, row_base):
+        if run_index is None:
+            run_index = self.next_run_index
+            self.next_run_index = (run_index + 1) % (1 << 32)
+        if not 0 <= int(run_index) < (1 << 32):
+            raise ValueError(f"run_index {run_index}: 32 bits")
+        base = self.row_base if row_base is None else int(row_base)
+        if not 0 <= base < (1 << 63):
+            raise ValueError(f"row_base {base}")
+        self.last_run_index = int(run_index)
+        if self._seed_ev is not None:
+            self._seed_ev.synchronize()  # the previous copy out of the pinned words has completed
+        else:
+            self._seed_ev = torch.cuda.Event()
+        h = self._seed_host
+        h[0] = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
+        h[1], h[2], h[3] = int(run_index), base, 0
+        self.seed_state.copy_(h, non_blocking=True)
+        self._seed_ev.record(torch.cuda.current_stream(self.dev))
 
     def launch_step(self, i):
         """Launch i of the chain (0 <= i <= n) on the current stream: finishes step i-1 and, for i < n, evaluates the score at t_i."""
         shape = (self.groups, self.B // self.groups, self.K, i, self.n)
+        gn = (ptr(self.gn_ext), self.gn_rows)
+        if self.seed is not None:
+            bufs = (ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.seed_state), ptr(self.centre), ptr(self.x), ptr(self.mean_x),
+                    ptr(self.score), ptr(self.partials), ptr(self.traj))
+            if self.trunk == "bf16x9":
+                _lib.call("gp_pc_step_bf16x9_seeded", *shape, self.net.w.ref(), *bufs, *gn, *(ptr(w) for w in self._x9), stream_ptr())
+            else:
+                _lib.call("gp_pc_step_plan_seeded", self.plan, *shape, self.net.w.ref(), *bufs, *gn, stream_ptr())
+            return
         bufs = (ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.z1), ptr(self.z2), ptr(self.centre), ptr(self.x), ptr(self.mean_x),
                 ptr(self.score), ptr(self.partials), ptr(self.traj))
-        gn = (ptr(self.gn_ext), self.gn_rows)
         if self.precision == "bf16x3":
             t = self.net.w.tensors
             _lib.call("gp_pc_step_bf16x3", *shape, *bufs, *(ptr(w) for w in self._bf), ptr(t["b_pose0"]), ptr(t["b_pose2"]), ptr(t["w_out"]),
@@ -137,16 +200,24 @@ class PCSampler:
                 torch.sum(self.partials[i].view(self.groups, -1), dim=1, out=self.gn_ext[i])
                 self._dist.all_reduce(self.gn_ext[i], op=self._dist.ReduceOp.SUM, group=self.coupling_group)
 
-    def run(self, cvec, centre, init_x, z_langevin=None, z_predictor=None, slot_free_event=None, graph_events=None):
+    def run(self, cvec, centre, init_x, z_langevin=None, z_predictor=None, slot_free_event=None, graph_events=None, run_index=None, row_base=None):
         """cvec [B,768], centre [B,3], init_x [R,9]; noise [n,R,9] (drawn on the device generator if None).
         Returns (xs [R,n,9] or None, mean_x [R,9]) float32, like cond_pc_sampler.
-        slot_free_event: recorded once the inputs have been copied into the sampler's own buffers (pipelining)."""
+        slot_free_event: recorded once the inputs have been copied into the sampler's own buffers (pipelining).
+        A seeded sampler (seed=) draws its own noise: every run() takes the next run index (other draws), run_index= pins it (a
+        repeated index repeats the draws), row_base= places this launch's first row (default: the constructor's)."""
+        if self.seed is None and (run_index is not None or row_base is not None):
+            raise ValueError("run_index= / row_base= need a sampler built with seed=")
+        if self.seed is not None and (z_langevin is not None or z_predictor is not None):
+            raise ValueError("explicit z_langevin= / z_predictor= on a seeded sampler: it draws its own noise (build it without seed= to inject noise)")
         self.cvec.copy_(cvec)
         self.centre.copy_(centre)
         self.x.copy_(init_x)
         if slot_free_event is not None:
             slot_free_event.record(torch.cuda.current_stream())
-        if z_langevin is None:
+        if self.seed is not None:
+            self._write_seed_state(run_index, row_base)
+        elif z_langevin is None:
             self.z1.normal_()
             self.z2.normal_()
         else:
@@ -171,6 +242,26 @@ class PCSampler:
                 graph_events[1].record(torch.cuda.current_stream())
         xs = self.traj.permute(1, 0, 2) if self.traj is not None else None
         return xs, self.mean_x
+
+
+def pc_noise_fill(seed, run_index, num_steps, nrows, device, row_base=0, step0=0, row0=0):
+    """The draws of a seeded PC sampler as buffers (gp_pc_noise_fill: the step kernels' own device function): (z_langevin, z_predictor),
+    [num_steps, nrows, 9] each, for steps step0 .. and rows row0 .. of a launch whose first row is global row `row_base`.  Feeding them to
+    an unseeded sampler's run(z_langevin=, z_predictor=) reproduces the seeded run bit for bit."""
+    dev = torch.device(device)
+    seed = int(seed) % (1 << 64)
+    st = torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, int(run_index), int(row_base), 0], dtype=torch.int64).to(dev)
+    z1, z2 = torch.empty(num_steps, nrows, 9, device=dev), torch.empty(num_steps, nrows, 9, device=dev)
+    _lib.call("gp_pc_noise_fill", ptr(st), int(step0), int(num_steps), int(row0), int(nrows), ptr(z1), ptr(z2), stream_ptr())
+    return z1, z2
+
+
+def philox_raw(counters, keys):
+    """Raw Philox4x32-10 blocks on the device: counters [n,4], keys [n,2] (int32 tensors holding the uint32 words) -> [n,4]."""
+    counters, keys = counters.contiguous(), keys.contiguous()
+    out = torch.empty_like(counters)
+    _lib.call("gp_philox_raw", counters.shape[0], ptr(counters), ptr(keys), ptr(out), stream_ptr())
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- PF-ODE (RK45)

@@ -319,6 +319,30 @@ int gp_pc_step_plan(int model, int tile, int ngroups, int nclouds_per_group, int
                     const float *tvec_all, const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x,
                     float *mean_x, float *score, float *partials, float *traj, const float *gn_ext, int gn_rows_total, gp_stream_t s);
 
+/* SEEDED NOISE (opt-in; csrc/philox.h, csrc/noise.hip).  Replaces the two torch.randn_like draws of cond_pc_sampler (samplers.py:132,149)
+ * by Philox4x32-10 + Box-Muller keyed by (seed, run, step, stream, GLOBAL row): a row draws the same values under every plan, in any
+ * batch of a launch and on any shard, and no [nsteps][R][9] noise buffers exist.
+ * seed_state: 8 x uint32 in DEVICE memory, read by the kernels at run time (a captured launch chain follows what the host copies there
+ * in stream order before each replay): [0],[1] seed lo / hi, [2] run index, [4],[5] row base lo / hi (global row = row base + row of the
+ * launch), [3],[6],[7] zero.  Normals are truncated at |z| <= 5.77 (uniforms on a 2^-24 grid in (0, 1]).
+ *
+ * gp_pc_step_plan_seeded / gp_pc_step_bf16x9_seeded: gp_pc_step_plan (score model: model 0) / gp_pc_step_bf16x9 with seed_state in place of
+ * z_langevin / z_predictor; every other argument, plan and result as there, nsteps < 2^29.  Given buffers filled by gp_pc_noise_fill for
+ * the same seed state, the unseeded entry points compute the same bits. */
+int gp_pc_step_plan_seeded(int tile, int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
+                           const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
+                           float *partials, float *traj, const float *gn_ext, int gn_rows_total, gp_stream_t s);
+int gp_pc_step_bf16x9_seeded(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
+                             const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
+                             float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
+                             const void *w_headx_x9, gp_stream_t s);
+/* The draws themselves (the values torch.randn_like returns at samplers.py:132 -> z_lang_out, :149 -> z_pred_out): for steps step0 ..
+ * step0 + nsteps - 1 and rows row0 .. row0 + nrows - 1 of a launch, [nsteps][nrows][9] each (either may be NULL), exactly what the seeded
+ * step kernels draw for them (the same device function). */
+int gp_pc_noise_fill(const void *seed_state, int step0, int nsteps, int64_t row0, int64_t nrows, float *z_lang_out, float *z_pred_out, gp_stream_t s);
+/* Raw Philox4x32-10 blocks (tests: bit-exactness against the published generator): counters [n][4], keys [n][2] -> out [n][4], uint32. */
+int gp_philox_raw(int64_t n, const void *counters, const void *keys, void *out, gp_stream_t s);
+
 /* The same launch with the batch-mean gradient norm SUPPLIED: gn_ext [nsteps][ngroups] (device) holds, for step i, the mean of
  * |score_i| over ALL rows of the batch each group belongs to.  For a batch that is sharded over several GPUs (SURVEY §8e caveat): the
  * host sums this rank's `partials` of step i, all-reduces the sum across the ranks and writes gn_ext[i] before launching step i+1, so
