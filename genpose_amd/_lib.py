@@ -88,6 +88,8 @@ SIGNATURES = {
     "gp_rk45_partials_count": [c_int, c_int, c_int, c_int, c_int],
     "gp_rk45_phase_model": [c_int, c_int, P, c_int, c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5
                            + [c_int, c_int, P, P, c_int, P],
+    "gp_rk45_phase_bf16x9": [c_int, c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5
+                            + [c_int, c_int, P, P, c_int] + [P] * 3 + [P],
     "gp_rk45_set_dense_grouped": [c_int, P, P, c_int, P, P],
     "gp_rk45_phase_ragged": [c_int, c_int, P, c_int, P, c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5
                             + [c_int, c_int, P, P],

@@ -28,6 +28,7 @@ DEFAULTS = dict(
     # pre-processing / evaluation side (preprocess.py, evaluation.py): configs/config.py:8,72-78
     sampler_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products in the PC sampler's score network (csrc/trunk_bf16x3.hip)
     sampler_seed=None,  # (ours) an integer: opt-in seeded noise drawn inside the PC step kernels (csrc/philox.h), reproducible per row; None: torch's generator
+    ode_trunk=None,  # (ours) 'bf16x9': opt-in exact-product split-bf16 trunk in the ODE sampler's chain-plan stage kernels (ODESampler(trunk=)); None / 'f32mfma': the fp32 MFMA kernels
     encoder_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products on the 128-196-256 grouping level (csrc/sa_bf16x3.hip)
     dist_arith=DEFAULT_DIST_ARITH,  # (ours) contraction convention of the grouping operators' distances, see above
     synset_names=["bottle", "bowl", "camera", "can", "laptop", "mug"], img_size=256, max_eval_num=10000000, results_path="",

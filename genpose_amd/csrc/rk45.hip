@@ -9,6 +9,7 @@
 //   rk45_finish           : denoise step (samplers.py:209-218), normalize_rotation, + centre
 // The error norm is the reference's batch-global RMS over all R*9 components: per-tile partial sums, reduced in
 // a fixed order by the single-workgroup decide kernel (deterministic).
+#include "bf16x9.h"
 #include "score_bwd.h"
 #include "trunk_chain_vjp.h"
 
@@ -531,6 +532,243 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void rk45_stage_chain_kernel(OdeAr
     }
 }
 
+// The score model's chain stage (rk45_stage_chain_kernel<2, STAGE, 0>) with the trunk as EXACT-PRODUCT split bf16 on the BF16 matrix pipe
+// (bf16x9.h; ODESampler(trunk="bf16x9")).  Around the trunk: that kernel's solver work, line for line - the f64 stage input per owner
+// lane (lane group g owns components 4g .. 4g+3), the commit of the accepted step in stage 1, y_new in stage 6, the h0 probe in stage 7,
+// K_s, the sums of squares as one partial per workgroup, clamped duplicate rows, the early exit - on the same grid and OdeArgs, so the
+// controller, embed, record, group-sums and finish kernels serve both.  The trunk: pc_step_chain_bf16x9's (trunk_bf16x9.hip), its text
+// DUPLICATED here rather than shared - that kernel sits on the register cliff and keeps even its head epilogue written out for that
+// reason.  It wants all nine components of a row in every lane of the row: the owners convert to f32 and the nine are gathered with
+// __shfl; the f64 values are dead before the ring starts.  After each head, every lane keeps its own components of the three outputs.
+constexpr int X9_NW = 4, X9_NT = 64 * X9_NW, X9_RT = 2, X9_ROWS = 16 * X9_RT * X9_NW;
+using X9Lds = gp_split::SplitLds<3, 2>;  // 2 slots of 48 KB
+constexpr int X9_SLICE = X9Lds::SLICE, X9_PER_T = X9_SLICE / X9_NT;
+static_assert(X9_ROWS == gp_chain::Cfg<2>::ROWS && X9_NT == gp_chain::NT && gp_split::NCL == gp_chain::NCL && X9_PER_T <= 16,
+              "the grid, the partials and the admitted shapes of the fp32 chain stage");
+
+template <int STAGE>
+__global__ __launch_bounds__(X9_NT, 1) void rk45_stage_chain_kernel_bf16x9(OdeArgs a, gp_split::SplitNet w) {
+    using namespace gp_split;
+    using namespace gp_bf16x9;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ double sh[8];
+    bf16x8 *ring = reinterpret_cast<bf16x8 *>(lds);
+    const float *woutl = lds + X9Lds::OFF_WOUT, *b0l = lds + X9Lds::OFF_B0, *b2l = lds + X9Lds::OFF_B2, *cvtl = lds + X9Lds::OFF_CVT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), pt = lane & 15, g = lane >> 4;
+    const int grp = blockIdx.x / a.bpg, wg_row0 = blockIdx.x * X9_ROWS;
+    Rk45State *st = a.st + grp;
+    if (STAGE >= 1 && STAGE <= 6 && st->status != 0) return;
+    const size_t n = (size_t)a.nrows * POSE;
+    const int slot = (STAGE >= 1 && STAGE <= 6) ? STAGE : 0;
+    const float *tvec = a.tvec + ((size_t)grp * 8 + slot) * HEADS;
+    const int nown = g < 2 ? 4 : (g == 2 ? POSE - 8 : 0);  // components 4g .. of the row's 9-vector this lane owns
+    // ---- stage input: y (+ h * sum_q a_sq K_q) in f64 per owner lane (requests first, the ring prologue behind them), then f32
+    f32x4 xf[X9_RT];
+    {
+        const double h = st->h;
+        const bool commit = STAGE == 1 && st->last_accepted;
+#pragma unroll
+        for (int p = 0; p < X9_RT; ++p) {
+            const int row = wg_row0 + (wave * X9_RT + p) * 16 + pt;
+            const bool live = row < a.nrows;
+            const int r = live ? row : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
+            double yv[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                yv[c] = 0.0;
+                if (c < nown) {
+                    const size_t ge = (size_t)r * POSE + 4 * g + c;
+                    double v = commit ? a.ynew[ge] : a.y[ge];
+                    if (STAGE >= 1 && STAGE <= 6) {
+                        double dy = 0.0;
+#pragma unroll
+                        for (int q = 0; q < STAGE; ++q) {
+                            const double kq = (q == 0 && commit) ? a.K[6 * n + ge] : a.K[(size_t)q * n + ge];
+                            if (q == 0 && commit && live) {  // commit the previous accepted step for this element
+                                a.y[ge] = v;
+                                a.K[ge] = kq;
+                            }
+                            dy += kq * DP_A[STAGE][q];
+                        }
+                        v = v + dy * h;
+                        if (STAGE == 6 && live) a.ynew[ge] = v;
+                    } else if (STAGE == 7) {
+                        v = v + st->h0 * st->direction * a.K[ge];
+                    }
+                    yv[c] = v;
+                }
+            }
+            xf[p] = f32x4{(float)yv[0], (float)yv[1], (float)yv[2], (float)yv[3]};
+        }
+    }
+    // slice 0 (-> slot 0 below) and slice 1 (-> registers, written during step 0)
+    bf16x8 first[X9_PER_T], hold[X9_PER_T];
+#pragma unroll
+    for (int u = 0; u < X9_PER_T; ++u) first[u] = split_slice<3>(w, 0)[tid + u * X9_NT];
+#pragma unroll
+    for (int u = 0; u < X9_PER_T; ++u) hold[u] = split_slice<3>(w, 1)[tid + u * X9_NT];
+    // ---- staged epilogue operands and slot 0
+    split_stage<X9_NT, X9Lds>(lds, w, a.cvec, tvec, wg_row0, a.nrows, a.kcand);
+#pragma unroll
+    for (int u = 0; u < X9_PER_T; ++u) ring[tid + u * X9_NT] = first[u];
+    __syncthreads();
+    int gstep = 0;
+    f32x4 acc[X9_RT][16];
+    // one ring step over slot gstep % 2 (trunk_bf16x9.hip): per output chunk the three weight terms (read one chunk ahead) x the two row
+    // tiles' split k-block = 18 MFMAs; beside chunk n < PER_T, element n of slice gstep + 1 goes from the registers to the other slot and
+    // element n of slice gstep + 2 is requested; one barrier (LDS writes complete, the slice in flight stays in flight)
+    auto ring_step = [&](const Split8 (&xs)[X9_RT]) {
+        const bf16x8 *rslot = ring + (gstep & 1) * X9_SLICE;
+        bf16x8 *dst = ring + ((gstep + 1) & 1) * X9_SLICE;
+        const bf16x8 *src = split_slice<3>(w, gstep + 2);
+        bf16x8 wf[2][3];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) wf[0][t] = rslot[t * 64 + lane];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            if (c + 1 < 16) {
+#pragma unroll
+                for (int t = 0; t < 3; ++t) wf[(c + 1) & 1][t] = rslot[((c + 1) * 3 + t) * 64 + lane];
+            }
+            if (c < X9_PER_T) {
+                dst[tid + c * X9_NT] = hold[c];
+                hold[c] = src[tid + c * X9_NT];
+            }
+            f32x4 an[X9_RT];
+#pragma unroll
+            for (int p = 0; p < X9_RT; ++p) an[p] = acc[p][c];
+            mma9<X9_RT>(wf[c & 1], xs, an);
+#pragma unroll
+            for (int p = 0; p < X9_RT; ++p) acc[p][c] = an[p];
+            __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the step
+        }
+        ++gstep;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    auto zero_acc = [&]() {
+#pragma unroll
+        for (int p = 0; p < X9_RT; ++p)
+#pragma unroll
+            for (int c = 0; c < 16; ++c) acc[p][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    // bias + ReLU of a 256-wide hidden layer, kept in fp32 (split one k-block at a time as the next layer consumes it)
+    f32x4 act[X9_RT][16];
+    auto hidden = [&](const float *bias) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + 16 * c + 4 * g);
+#pragma unroll
+            for (int p = 0; p < X9_RT; ++p) act[p][c] = relu4(acc[p][c] + bv);
+        }
+    };
+    auto layer = [&]() {  // acc = W . act over the 8 k-blocks of a 256-wide input
+        zero_acc();
+#pragma unroll
+        for (int kb = 0; kb < 8; ++kb) {
+            Split8 xs[X9_RT];
+#pragma unroll
+            for (int p = 0; p < X9_RT; ++p) xs[p] = split8(act[p][2 * kb], act[p][2 * kb + 1]);
+            ring_step(xs);
+        }
+    };
+    // ---- pose_encoder.0: the row's nine f32 components gathered from the lane groups that own them
+    {
+        Split8 xs[X9_RT];
+#pragma unroll
+        for (int p = 0; p < X9_RT; ++p) {
+            float xv[POSE];
+#pragma unroll
+            for (int j = 0; j < POSE; ++j) xv[j] = __shfl(xf[p][j & 3], pt + 16 * (j >> 2), 64);
+            f32x4 pa, pb;
+            split_pose_fragment(xv, g, pa, pb);
+            xs[p] = split8(pa, pb);
+        }
+        zero_acc();
+        ring_step(xs);
+    }
+    hidden(b0l);
+    // ---- pose_encoder.2
+    layer();
+    hidden(b2l);
+    // ---- the three heads; their Linear(256, 3) output layers as fp32 dot products on the accumulator fragments
+    int cl[X9_RT];
+#pragma unroll
+    for (int p = 0; p < X9_RT; ++p) {
+        const int row = wg_row0 + (wave * X9_RT + p) * 16 + pt;
+        const int r = row < a.nrows ? row : a.nrows - 1;
+        cl[p] = r / a.kcand - wg_row0 / a.kcand;  // < NCL (Cfg<2>::fits(k))
+    }
+    // K_s and the sums of squares (the fp32 chain stage's lines) follow each head at once, by the lane group that owns the component:
+    // head hd's outputs are components 3 hd .. 3 hd + 2, final once its epilogue is done - carrying them to the end of the kernel
+    // costs eight more live registers through the other heads' rings, on a kernel that sits on the register cliff
+    const double h = st->h;
+    const float sigma = st->stage_sigma[slot];
+    const double g2 = st->stage_g2[slot];
+    double *Kout = a.K + (size_t)(STAGE == 7 ? 1 : (STAGE == 0 ? 0 : (STAGE == 6 ? 6 : STAGE))) * n;
+    double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll 1
+    for (int hd = 0; hd < 3; ++hd) {
+        layer();
+#pragma unroll
+        for (int p = 0; p < X9_RT; ++p) {
+            float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                const int ch = 16 * c + 4 * g;
+                const f32x4 v = relu4(acc[p][c] + *reinterpret_cast<const f32x4 *>(cvtl + cl[p] * HEADS + 256 * hd + ch));
+                const f32x4 w0 = *reinterpret_cast<const f32x4 *>(woutl + (3 * hd + 0) * HID + ch);
+                const f32x4 w1 = *reinterpret_cast<const f32x4 *>(woutl + (3 * hd + 1) * HID + ch);
+                const f32x4 w2 = *reinterpret_cast<const f32x4 *>(woutl + (3 * hd + 2) * HID + ch);
+                o0 += v.x * w0.x + v.y * w0.y + v.z * w0.z + v.w * w0.w;
+                o1 += v.x * w1.x + v.y * w1.y + v.z * w1.z + v.w * w1.w;
+                o2 += v.x * w2.x + v.y * w2.y + v.z * w2.z + v.w * w2.w;
+            }
+            // the four lane groups hold the four channel quarters: fixed order, every lane gets the sum
+            const float fh[3] = {lane_groups_sum(o0) + w.b_out[3 * hd + 0], lane_groups_sum(o1) + w.b_out[3 * hd + 1],
+                                 lane_groups_sum(o2) + w.b_out[3 * hd + 2]};
+            const int row = wg_row0 + (wave * X9_RT + p) * 16 + pt;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int j = 3 * hd + c;
+                if ((j >> 2) != g || row >= a.nrows) continue;  // component j = 4g + (j & 3): this lane computed its stage input
+                const size_t ge = (size_t)row * POSE + j;
+                const float rhs = fh[c] / (sigma + 1e-7f);
+                const double kv = 0.0 - (0.5 * g2) * (double)rhs;
+                Kout[ge] = kv;
+                if (STAGE == 0) {
+                    const double y0 = a.y[ge];
+                    const double sc = st->atol + fabs(y0) * st->rtol;
+                    acc0 += (y0 / sc) * (y0 / sc);
+                    acc1 += (kv / sc) * (kv / sc);
+                } else if (STAGE == 7) {
+                    const double sc = st->atol + fabs(a.y[ge]) * st->rtol;
+                    const double d = (kv - a.K[ge]) / sc;
+                    acc0 += d * d;
+                } else if (STAGE == 6) {
+                    double er = 0.0;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) er += a.K[(size_t)q * n + ge] * DP_E[q];
+                    er += kv * DP_E[6];
+                    er *= h;
+                    const double yo = a.y[ge], yn = a.ynew[ge];
+                    const double sc = st->atol + fmax(fabs(yo), fabs(yn)) * st->rtol;
+                    acc0 += (er / sc) * (er / sc);
+                }
+            }
+        }
+    }
+    if (STAGE == 0 || STAGE == 6 || STAGE == 7) {
+        const double s0 = block_sum(acc0, sh);
+        if (threadIdx.x == 0) a.partials[blockIdx.x] = s0;
+        if (STAGE == 0) {
+            const double s1 = block_sum(acc1, sh);
+            if (threadIdx.x == 0) a.partials[a.nblocks + blockIdx.x] = s1;
+        }
+    }
+}
+
 __device__ __forceinline__ double sum_partials(const double *p, int nb, double *sh) {
     double s = 0.0;
     for (int q = threadIdx.x; q < nb; q += 256) s += p[q];
@@ -876,7 +1114,8 @@ int set_lds_attr(K kern, size_t lds) {
 // SPLIT: the head-split plan (three workgroups per 16-row tile, one head each; OdeArgs::hsplit == 3): every stage is a launch of its own
 template <int P, int MODEL, bool CHAIN = false, bool SPLIT = false>
 static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double *traj, int traj_cap, double t0, double t_bound, double rtol,
-                           double atol, double denoise_scale, int do_denoise, int nstates, const float *centre, double *x_out, hipStream_t st) {
+                           double atol, double denoise_scale, int do_denoise, int nstates, const float *centre, double *x_out, hipStream_t st,
+                           const gp_split::SplitNet *x9 = nullptr) {
     const size_t chain_lds = MODEL == 0 ? gp_chain::Cfg<2>::LDS_BYTES : gp_chain::CfgV<2>::LDS_BYTES;
     const double *y = a.y;
     const size_t lds = MODEL == 0 ? trunk_lds_bytes<P>() : gp_bwd::LDS_BYTES;
@@ -902,6 +1141,19 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
         }
         attr_done = true;
     }
+    // x9 (gp_rk45_phase_bf16x9; score model, chain form): the stage kernels with the split-bf16 trunk, everything else as it is
+    if (x9 && !(CHAIN && MODEL == 0)) return GP_EINVAL;
+    if constexpr (CHAIN && MODEL == 0) {
+        static bool x9_attr_done = false;
+        if (x9 && !x9_attr_done) {
+            if (set_lds_attr(rk45_stage_chain_kernel_bf16x9<0>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<1>, X9Lds::BYTES) ||
+                set_lds_attr(rk45_stage_chain_kernel_bf16x9<2>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<3>, X9Lds::BYTES) ||
+                set_lds_attr(rk45_stage_chain_kernel_bf16x9<4>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<5>, X9Lds::BYTES) ||
+                set_lds_attr(rk45_stage_chain_kernel_bf16x9<6>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<7>, X9Lds::BYTES))
+                return GP_ELAUNCH;
+            x9_attr_done = true;
+        }
+    }
     if ((a.hsplit == 3) != SPLIT) return GP_EINVAL;
     const dim3 grid(a.nblocks * (SPLIT ? 3 : 1)), blk(TrunkCfg<P>::NT), blk1(256);
     const size_t n = (size_t)a.nrows * a.ncomp;
@@ -914,7 +1166,12 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
     };
     auto stage = [&](auto tag) {
         constexpr int S = decltype(tag)::value;
-        if constexpr (CHAIN)
+        if constexpr (CHAIN && MODEL == 0) {
+            if (x9)
+                hipLaunchKernelGGL((rk45_stage_chain_kernel_bf16x9<S>), grid, dim3(X9_NT), X9Lds::BYTES, st, a, *x9);
+            else
+                hipLaunchKernelGGL((rk45_stage_chain_kernel<2, S, MODEL>), grid, dim3(gp_chain::NT), chain_lds, st, a, *net);
+        } else if constexpr (CHAIN)
             hipLaunchKernelGGL((rk45_stage_chain_kernel<2, S, MODEL>), grid, dim3(gp_chain::NT), chain_lds, st, a, *net);
         else
             hipLaunchKernelGGL((rk45_stage_kernel<P, S, MODEL, SPLIT>), grid, blk, lds, st, a, *net);
@@ -1160,6 +1417,28 @@ int gp_rk45_phase_model(int model, int plan, const float *probe, int phase, int 
                                                    (hipStream_t)s);
     return P == 16 ? GP_RK45_CALL(16, 0) : (P == 64 ? GP_RK45_CALL(64, 0) : GP_RK45_CALL(32, 0));
 #undef GP_RK45_CALL
+}
+
+/* gp_rk45_phase_model(model 0, plan 128) with the stage kernels' score trunk as exact-product split bf16 on the BF16 matrix pipe
+ * (rk45_stage_chain_kernel_bf16x9; the packs of weights.pack_bf16x9, as gp_pc_step_bf16x9 takes them).  A second ARITHMETIC of the
+ * chain plan, not a plan: phases 1-3 launch the split-bf16 stage kernels, every other phase - and the controller, embedding, record,
+ * group-sums (ext_sums: phases 11-13) and finish kernels of phases 1-3 - is plan 128's code.  Only shapes that plan serves
+ * (gp_chain::Cfg<2>::fits(k); several groups: rows per group a multiple of 128), else GP_EINVAL.  partials: gp_rk45_partials_count(0, 128, ...). */
+int gp_rk45_phase_bf16x9(int phase, int ngroups, int nclouds_per_group, int k, const gp_scorenet *net, const float *cvec, float *tvec, const float *centre,
+                         void *state, double *y, double *ynew, double *K, double *partials, double *traj, int traj_cap, double t0, double t_bound,
+                         double rtol, double atol, double denoise_scale, int do_denoise, int nstates, double *x_out, double *ext_sums,
+                         int ext_rows_per_group, const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
+    if (!net || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9) return GP_EINVAL;
+    OdeArgs a;
+    int P = 0;
+    if (ode_args(&a, &P, 128, 0, nullptr, ngroups, nclouds_per_group, k, cvec, tvec, centre, state, y, ynew, K, partials, traj, nullptr) != GP_OK || P != 128)
+        return GP_EINVAL;
+    if (ext_sums && ext_rows_per_group < a.rows_per_group) return GP_EINVAL;
+    a.ext_sums = ext_sums, a.ext_rows = ext_rows_per_group;
+    const gp_split::SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
+                                  reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
+    return rk45_phase_impl<32, 0, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out, (hipStream_t)s,
+                                        &w);
 }
 
 int gp_rk45_plan_rows(int model, int ngroups, int nclouds_per_group, int k) {

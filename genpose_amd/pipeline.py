@@ -205,13 +205,15 @@ class GroupedODEPredictor:
         self.T0 = self.net.T if T0 is None else T0
         self.dev = self.net.device
         self._ODESampler = ODESampler
+        self.trunk = getattr(self.net.cfg, "ode_trunk", None)  # opt-in: split-bf16 trunk where the launch runs the chain plan
         self.smp = {}
         self.last_nfev = []
 
     def _sampler(self, g):
-        if g not in self.smp:
-            self.smp[g] = self._ODESampler(self.net.pose_score_net, self.B1 * g, self.K, self.dev, groups=g)
-        return self.smp[g]
+        key = (g, self.trunk)
+        if key not in self.smp:
+            self.smp[key] = self._ODESampler(self.net.pose_score_net, self.B1 * g, self.K, self.dev, groups=g, trunk=self.trunk)
+        return self.smp[key]
 
     def run(self, batches, prior_noise=None):
         """batches: sequence of device tensors [B,1024,3] -> list of pred_pose [B,K,9] float64 (one per batch).

@@ -157,10 +157,11 @@ class GFObjectPose:
             pr = self._prior_to_device((R, 9), T=T0)
             x0 = pr if init_x is None else init_x.float() + pr
             coupling = getattr(self, "coupling_group", None)  # batch sharded over the ranks of that group: error norm over ALL its rows
-            key = ("ode", B, K, id(coupling) if coupling is not None else None)
+            trunk = getattr(self.cfg, "ode_trunk", None)  # opt-in: the chain plan's stage kernels on the BF16 matrix pipe (ODESampler(trunk=))
+            key = ("ode", B, K, id(coupling) if coupling is not None else None, trunk)
             smp = self._samplers.get(key)
             if smp is None:
-                smp = self._samplers[key] = ODESampler(self.pose_score_net, B, K, self.device, coupling_group=coupling)
+                smp = self._samplers[key] = ODESampler(self.pose_score_net, B, K, self.device, coupling_group=coupling, trunk=trunk)
             self.last_sampler = smp
             return smp.run(cvec, centre, x0, T0, num_steps=self.cfg.sampling_steps, eps=self.sampling_eps, return_process=return_process)
         raise NotImplementedError(sampler)

@@ -285,10 +285,11 @@ class TrackingRunner:
             n = pts.shape[0]
             prior = net._prior_to_device((n * K, 9), T=self.T0)
             x0 = (prior.view(n, K, 9) + init_x.float().unsqueeze(1)).view(n * K, 9)  # samplers.py:180: init_x repeated K times + prior
-            key = ("ode", n, K, None)
+            trunk = getattr(net.cfg, "ode_trunk", None)
+            key = ("ode", n, K, None, trunk)
             smp = net._samplers.get(key)
             if smp is None:
-                smp = net._samplers[key] = ODESampler(net.pose_score_net, n, K, net.device)
+                smp = net._samplers[key] = ODESampler(net.pose_score_net, n, K, net.device, trunk=trunk)
             net.last_sampler = smp
             _, x = smp.run(cvec_s, centre, x0, self.T0, num_steps=net.cfg.sampling_steps, eps=net.sampling_eps)
             pred = x.reshape(n, K, 9)

@@ -289,7 +289,8 @@ class ODESampler:
     MAX_GRAPHS = 12  # captured attempt graphs kept per kind (each holds chunk x 8 kernel nodes)
     MODELS = {"score": 0, "energy": 1, "likelihood": 2}
 
-    def __init__(self, net, B, K, device, use_graph=True, poll=8, groups=1, group_clouds=None, model="score", coupling_group=None, tile=0):
+    def __init__(self, net, B, K, device, use_graph=True, poll=8, groups=1, group_clouds=None, model="score", coupling_group=None, tile=0,
+                 trunk=None):
         """B clouds in `groups` independent batches of B/groups clouds laid out back to back: every batch keeps its own adaptive
         step control (error norm over ITS rows, accept / reject, step size - what separate cond_ode_sampler calls would do) while
         all of them share each launch (gp_rk45_phase_grouped).
@@ -305,7 +306,14 @@ class ODESampler:
         batch.  On RCCL the all-reduce is captured with the attempts; on gloo the attempts run launch by launch.
 
         tile: launch plan of the stage kernels (0 = pick: 16- / 32-row tiles, or the 128-row chain form of the trunk for score-model
-        launches of ~32 000 rows and more, gp_rk45_plan_rows); tests and measurements force one."""
+        launches of ~32 000 rows and more, gp_rk45_plan_rows); tests and measurements force one.
+
+        trunk: the arithmetic of the score model's chain plan (128 rows per workgroup, equal groups) - None / 'f32mfma' (the default: the
+        fp32 MFMA stage kernels) or 'bf16x9' (OPT-IN; csrc/rk45.hip: rk45_stage_chain_kernel_bf16x9 - the dense layers as exact-product
+        split bf16 on the BF16 matrix pipe, fp32 accuracy; gp_rk45_phase_bf16x9).  It does not touch the choice of plan and is ignored
+        under every other plan or model; `self.trunk` holds the effective value."""
+        if trunk not in (None, "f32mfma", "bf16x9"):
+            raise ValueError(f"trunk {trunk!r}: 'f32mfma' or 'bf16x9'")
         self.model = self.MODELS[model]
         self.ncomp = 10 if self.model == 2 else 9
         self.ragged = group_clouds is not None
@@ -352,6 +360,22 @@ class ODESampler:
             if npart <= 0:
                 raise ValueError(f"plan {self.plan:#x} does not serve {groups} x {B // groups} clouds x {K} candidates")
             self.nblocks = npart // (3 * self.hsplit)
+        self.trunk = "f32mfma"
+        if trunk == "bf16x9" and not self.ragged and self.model == 0 and self.plan == 128:
+            self.trunk = "bf16x9"
+            self._x9 = net.w.bf16x9_packs()
+        if self.trunk == "bf16x9":
+            self.kernel_name = "rk45_stage_chain_kernel<bf16x9>"
+        elif self.shared:
+            self.kernel_name = f"rk45_attempt_shared_kernel<{self.tile}>"
+        elif self.tile == 128:
+            self.kernel_name = "rk45_stage_chain_kernel<2>" if self.model == 0 else f"rk45_stage_chain_kernel<2,{model}>"
+        elif self.hsplit == 3:
+            self.kernel_name = "rk45_stage_kernel<16,split>"
+        elif self.tile == 16:
+            self.kernel_name = "rk45_attempt_kernel<16>" if self.model == 0 else f"rk45_attempt_kernel<16,{model}>"
+        else:
+            self.kernel_name = f"rk45_stage_kernel<{self.tile}>"
         if self.ragged:
             self.set_groups(group_clouds)
         self.layout, nbytes = _state_layout()
@@ -424,6 +448,14 @@ class ODESampler:
         if self.ragged:
             _lib.call("gp_rk45_phase_ragged", phase, self.groups, ptr(self.grp_info), self.nblocks, ptr(self.blk_info), self.plan, self.B, self.K,
                       self.net.w.ref(), *tail)
+        elif self.trunk == "bf16x9":
+            x9 = tuple(ptr(w) for w in self._x9)
+            _lib.call("gp_rk45_phase_bf16x9", phase, self.groups, self.B // self.groups, self.K, self.net.w.ref(), *tail[:-1], ptr(self.ext_sums), self.ext_rows,
+                      *x9, tail[-1])
+            if self.ext_sums is not None and phase in (1, 2, 3):
+                self._dist.all_reduce(self.ext_sums, op=self._dist.ReduceOp.SUM, group=self.coupling_group)
+                _lib.call("gp_rk45_phase_bf16x9", phase + 10, self.groups, self.B // self.groups, self.K, self.net.w.ref(), *tail[:-1], ptr(self.ext_sums),
+                          self.ext_rows, *x9, tail[-1])
         else:
             _lib.call("gp_rk45_phase_model", self.model, self.plan, ptr(self.probe), phase, self.groups, self.B // self.groups, self.K, self.net.w.ref(), *tail[:-1],
                       ptr(self.ext_sums), self.ext_rows, tail[-1])

@@ -430,6 +430,18 @@ int gp_rk45_phase_model(int model, int plan, const float *probe, int phase, int 
                         float *tvec, const float *centre, void *state, double *y, double *ynew, double *K, double *partials, double *traj,
                         int traj_cap, double t0, double t_bound, double rtol, double atol, double denoise_scale, int do_denoise, int nstates,
                         double *x_out, double *ext_sums, int ext_rows_per_group, gp_stream_t s);
+/* The score model's chain plan (gp_rk45_phase_model(model = 0, plan = 128)) with a second ARITHMETIC of the stage kernels' trunk: the three
+ * dense layers as exact-product split bf16 on the BF16 matrix pipe (csrc/rk45.hip: rk45_stage_chain_kernel_bf16x9; every fp32 operand is
+ * hi + mid + lo, all nine cross products are exact, only the fp32 accumulation rounds - the error class of the fp32 MFMA stage kernels, as
+ * gp_pc_step_bf16x9 is to gp_pc_step_plan).  w_*_x9: the packs of weights.pack_bf16x9 (device).  No new plan: phases 1, 2 and 3 launch the
+ * split-bf16 stage kernels; the step controller, the time embeddings, the trajectory / dense-output record, the sharded batch's group sums
+ * (ext_sums, phases 11-13) and phases 0, 4 and 5 are plan 128's own code, on the same grid, state and buffers (partials:
+ * gp_rk45_partials_count(0, 128, ...) doubles).  Serves the shapes plan 128 serves - k >= 43, rows_per_group % 128 == 0 when ngroups > 1 -
+ * and returns GP_EINVAL for every other.  Opt-in (ODESampler(trunk="bf16x9")): results differ from the fp32 chain's in the last bits. */
+int gp_rk45_phase_bf16x9(int phase, int ngroups, int nclouds_per_group, int k, const gp_scorenet *net, const float *cvec, float *tvec, const float *centre,
+                         void *state, double *y, double *ynew, double *K, double *partials, double *traj, int traj_cap, double t0, double t_bound,
+                         double rtol, double atol, double denoise_scale, int do_denoise, int nstates, double *x_out, double *ext_sums,
+                         int ext_rows_per_group, const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s);
 /* Ragged variant: groups with different numbers of clouds (tracking: the objects of one frame form a group, frames of different
  * sequences share the launches).  grp_info [ngroups][4] = {first workgroup, workgroups, rows, first row}; blk_info [nblocks][3] =
  * {group, first row, end row (exclusive) of the group} per workgroup of `tile` (16 or 32) rows; both device int32.  Rows stay

@@ -39,7 +39,7 @@ for f in range(200):
     init_x = torch.cat([init_sRT[:, :3, 0], init_sRT[:, :3, 1], init_sRT[:, :3, 3] - centre], dim=1); t = mark("init_x (slices, sub, cat)", t)
     prior = net._prior_to_device((n_obj * K, 9), T=tr.T0); t = mark("prior draw on the CPU + pinned staging + H2D", t)
     x0 = (prior.view(n_obj, K, 9) + init_x.float().unsqueeze(1)).view(n_obj * K, 9); t = mark("x0", t)
-    smp = net._samplers.get(("ode", n_obj, K, None))
+    smp = net._samplers.get(("ode", n_obj, K, None, getattr(net.cfg, "ode_trunk", None)))
     eS = torch.cuda.Event(enable_timing=True); eS.record()
     _, x = smp.run(cvec_s, centre, x0, tr.T0, num_steps=net.cfg.sampling_steps, eps=net.sampling_eps); t = mark("ODESampler.run (incl. the status read = the frame's one sync)", t)
     pred = x.reshape(n_obj, K, 9)
