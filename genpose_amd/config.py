@@ -30,9 +30,23 @@ DEFAULTS = dict(
     sampler_seed=None,  # (ours) an integer: opt-in seeded noise drawn inside the PC step kernels (csrc/philox.h), reproducible per row; None: torch's generator
     ode_trunk=None,  # (ours) 'bf16x9': opt-in exact-product split-bf16 trunk in the ODE sampler's chain-plan stage kernels (ODESampler(trunk=)); None / 'f32mfma': the fp32 MFMA kernels
     encoder_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products on the 128-196-256 grouping level (csrc/sa_bf16x3.hip)
+    encoder_level2="auto",  # (ours) under encoder_precision 'f32', the arithmetic of grouping level 2 (128-196-256): 'bf16x9' = exact-product split bf16 on the BF16 matrix pipe (csrc/sa_bf16x9.hip, the fp32 kernels' error class), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the adaptive ODE sampler (its goldens pin RK45 attempt counts that move with the last bits of the features); encoder_precision='bf16x9' forces it
     dist_arith=DEFAULT_DIST_ARITH,  # (ours) contraction convention of the grouping operators' distances, see above
     synset_names=["bottle", "bowl", "camera", "can", "laptop", "mug"], img_size=256, max_eval_num=10000000, results_path="",
 )
+
+
+def encoder_precision_of(cfg):
+    """The `precision` of Pointnet2EncoderHIP a namespace asks for (the reference's own namespace has neither field: the defaults).
+    encoder_precision 'f32' names the accuracy class; within it encoder_level2 picks the matrix pipe of grouping level 2."""
+    prec = getattr(cfg, "encoder_precision", "f32")
+    lvl2 = getattr(cfg, "encoder_level2", "auto")
+    if lvl2 not in ("auto", "bf16x9", "f32mfma"):
+        raise ValueError(f"encoder_level2 {lvl2!r}: 'auto', 'bf16x9' or 'f32mfma'")
+    if lvl2 == "auto":
+        mode = getattr(cfg, "sampler_mode", None) or ["ode"]
+        lvl2 = "bf16x9" if mode[0] == "pc" else "f32mfma"
+    return "bf16x9" if prec == "f32" and lvl2 == "bf16x9" else prec
 
 
 def get_config(**overrides):

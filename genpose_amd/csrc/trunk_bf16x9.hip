@@ -14,11 +14,13 @@
 // slot s is multiplied, slice s + 2 is requested, one barrier per slice.
 // Budget per workgroup and launch (MI355X: LDS 256 B/clk/CU for conflict-free ds_read_b128, v_mfma_f32_16x16x32_bf16 16 cycles):
 //   LDS fragment reads  33 slices x 48 KB x 4 waves = 6.3 MB  -> 24.8 k cycles (49.5 k at 128 B/clk)
-//   MFMA                33 x 16 chunks x 9 products x 2 tiles = 9 504 per wave x 16 cycles = 152 k cycles per SIMD (63 us at 2.4 GHz)
+//   MFMA                33 x 16 chunks x 9 products x 2 tiles = 9 504 per wave x 16 cycles = 152 k cycles per SIMD (63 us at the 2.4 GHz
+//                       peak clock; dense BF16 MFMA loops on random data sustain 1.5-1.95 GHz on this part: 80 us at 1.9 GHz)
 // so the matrix pipe bounds it, not LDS (bf16x3's 8 waves x 16 rows read the same 1.5 MB weight stream twice as often per row) and not
 // the fp32 peak: 9 bf16 products per fp32 product at 16x the fp32 rate = 1.8x the fp32 MFMA FLOP rate.
-// Measured (MI355X, 32 000 rows, rocprofv3): 118.0 us per launch against 142.7 us for pc_step_chain_kernel<2, 0>; the rest of the gap to
-// the 63 us floor is barrier drains (one wave per SIMD), the head epilogues (not overlapped with MFMAs) and a few spilled registers.
+// Measured (MI355X, 32 000 rows, rocprofv3): 118.0 us per launch against 142.7 us for pc_step_chain_kernel<2, 0> (102.7 us by HIP events
+// since); the rest of the gap to the floor - 80 us at a sustained 1.9 GHz, not the 63 us of the peak clock, so the kernel runs near 0.8 of
+// what the clock allows - is barrier drains (one wave per SIMD), the head epilogues (not overlapped with MFMAs) and a few spilled registers.
 #include "bf16x9.h"
 #include "pc_rows.h"
 #include "trunk_chain.h"

@@ -5,7 +5,8 @@ forward(pts [B,N,3] f32 on the GPU) -> [B,1024].  Launch sequence per call (all 
   L x gp_ball_query_msg both radii of a level in one pass
   L x gp_point_linear   hoisted feature half of the first layer, once per source point (both scales)
   2L x gp_sa_pre_mlp_max_layout  gather -> xyz half of layer 1 -> layers 2-3 on fp32 MFMA -> max-pool, per scale (register-chain kernels;
-                        the hidden-layer layout the weights were packed for, weights.SAScale)
+                        the hidden-layer layout the weights were packed for, weights.SAScale); grouping level 2 (128-196-256) by default
+                        through gp_sa_pre_mlp_max_bf16x9: the same job with layers 2-3 as exact-product split bf16
   1 + 2 x the same pair  GroupAll level: whole rounds of 256 clouds on the ring kernel (one cloud per workgroup), the rest on 32-row tiles
                         (the tiles of a cloud combine by integer atomic max into a zeroed buffer)
 Intermediate features stay point-major [B, n, C]; the reference's grouped [B,C+3,np,ns] tensors never exist.
@@ -40,11 +41,15 @@ class Pointnet2EncoderHIP:
     def __init__(self, state_dict, device="cuda", params="light", prefix="pts_encoder.", arith=None, precision="f32"):
         """arith: contraction convention of the squared distances in furthest point sampling and the ball queries ('A' | 'B' | 'C',
         config.DEFAULT_DIST_ARITH when None; include/genpose_hip.h GP_ARITH_*).
-        precision: 'f32' (default: every dense layer on the fp32 matrix pipe - what all parity claims and the headline bench line run) or
-        'bf16x3' (OPT-IN, exploratory, round 5): grouping levels 1 and 2 (64-64/96-128, 128-196-256) on the bf16 matrix pipe as three-term split products with
-        fp32 accumulation (csrc/sa_bf16x3.hip; ~2^-17 relative per product); centres and neighbourhoods are unaffected."""
-        if precision not in ("f32", "bf16x3"):
-            raise ValueError(f"encoder precision {precision!r}: 'f32' or 'bf16x3'")
+        precision: 'f32' (default of this class): every dense layer on the fp32 matrix pipe.
+        'bf16x9' (what an agent of the PC sampler asks for by default, config.encoder_precision_of): grouping level 2 (128-196-256) on the
+        BF16 matrix pipe as exact-product split bf16 (csrc/sa_bf16x9.hip: every operand hi + mid + lo, all nine products exact, fp32
+        accumulation - the fp32 kernels' error class), every other dense layer on the fp32 matrix pipe; a scale whose folded weights do
+        not split exactly keeps the fp32 kernel (`sa_kernels` says which kernel serves each scale).
+        'bf16x3' (OPT-IN, exploratory, round 5): grouping levels 1 and 2 (64-64/96-128, 128-196-256) as three-term split products with
+        fp32 accumulation (csrc/sa_bf16x3.hip; ~2^-17 relative per product).  Centres and neighbourhoods are unaffected by any of them."""
+        if precision not in ("f32", "bf16x3", "bf16x9"):
+            raise ValueError(f"encoder precision {precision!r}: 'f32', 'bf16x9' or 'bf16x3'")
         self.precision = precision
         self.device = torch.device(device)
         self.arith = dist_arith_code(arith)
@@ -56,8 +61,24 @@ class Pointnet2EncoderHIP:
         self._ws = ShapeCache(self.MAX_WORKSPACES, can_evict=_unpinned)
         self._pass_graphs = ShapeCache(self.MAX_PASS_GRAPHS, on_evict=_unpin_entry)  # (no closure over self: no reference cycle)
         self._seen_once = ShapeCache(4 * self.MAX_PASS_GRAPHS)
+        # which kernel serves each (level, scale) of the grouping levels: 'f32mfma' | 'bf16x9' | 'bf16x3' (bf16x3 also needs whole 32-row
+        # units of the batch at hand, see forward)
+        self.sa_kernels = {}
+        for k, npnt in enumerate(self.cfg["npoints"]):
+            if npnt is None:
+                break
+            for i, sc in enumerate(self.w.levels[k]):
+                shape = (tuple(sc.couts), self.cfg["nsamples"][k][i])
+                name = "f32mfma"
+                if precision == "bf16x3" and k > 0 and shape in self.BF16X3_SHAPES:
+                    name = "bf16x3"
+                elif precision == "bf16x9" and k > 0 and shape in self.BF16X9_SHAPES and (npnt * shape[1]) % 32 == 0 and sc.bf16x9_packs() is not None:
+                    name = "bf16x9"
+                self.sa_kernels[(k, i)] = name
 
     MAX_WORKSPACES = 12
+    # (layer widths, neighbourhood size) the exact-product split-bf16 kernel is instantiated for: grouping level 2 (csrc/sa_bf16x9.hip)
+    BF16X9_SHAPES = {((128, 196, 256), 16), ((128, 196, 256), 32)}
     # (layer widths, neighbourhood size) the opt-in split-bf16 kernel is instantiated for: grouping levels 1 and 2 (csrc/sa_bf16x3.hip)
     BF16X3_SHAPES = {((128, 196, 256), 16), ((128, 196, 256), 32), ((64, 64, 128), 16), ((64, 96, 128), 32), ((64, 64, 128), 32)}
 
@@ -353,6 +374,13 @@ class Pointnet2EncoderHIP:
                     w2s, b2s, w3s, b3s = sc.bf16x3_packs()
                     _lib.call("gp_sa_pre_mlp_max_bf16x3", B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(src["bq"][k][i]), ptr(z),
                               zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(w2s), ptr(b2s), ptr(w3s), ptr(b3s), ptr(out), cout_total, off, st)
+                    off += sc.couts[2]
+                    zoff += sc.couts[0]
+                    continue
+                if self.sa_kernels[(k, i)] == "bf16x9":
+                    wx9, b2x9, b3x9 = sc.bf16x9_packs()
+                    _lib.call("gp_sa_pre_mlp_max_bf16x9", B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(src["bq"][k][i]), ptr(z),
+                              zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(wx9), ptr(b2x9), ptr(b3x9), ptr(out), cout_total, off, st)
                     off += sc.couts[2]
                     zoff += sc.couts[0]
                     continue

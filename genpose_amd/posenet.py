@@ -12,6 +12,7 @@ and every cloud owns K consecutive pose rows - this is how PoseNet.pred_func avo
 """
 import torch
 
+from .config import encoder_precision_of
 from .encoder import Pointnet2EncoderHIP
 from .lru import ShapeCache
 from .samplers import ODESampler, PCSampler
@@ -50,8 +51,7 @@ class GFObjectPose:
     def load_state_dict(self, state_dict, strict=True):
         sd = {k[7:] if k.startswith("module.") else k: v for k, v in state_dict.items()}
         params = getattr(self.cfg, "pointnet2_params", "light")
-        self.pts_encoder = Pointnet2EncoderHIP(sd, self.device, params, arith=getattr(self.cfg, "dist_arith", None),
-                                               precision=getattr(self.cfg, "encoder_precision", "f32"))
+        self.pts_encoder = Pointnet2EncoderHIP(sd, self.device, params, arith=getattr(self.cfg, "dist_arith", None), precision=encoder_precision_of(self.cfg))
         self.pose_score_net = ScoreNetHIP(sd, self.device)
         self._samplers.clear()
         return self

@@ -87,6 +87,7 @@ class SAScale:
         self._folded_plain = [(W.clone(), b.clone()) for W, b in folded]  # channel order as trained (the fp32 packs below may permute it)
         self._device = device
         self._bf16x3 = None
+        self._bf16x9 = None
         c2 = self.couts[1]
         if c2 % 16:
             # hidden width not a multiple of 16 (light level 2: 196): the channels of the last, partly filled 16-channel block go to
@@ -121,6 +122,24 @@ class SAScale:
             dev = self._device
             self._bf16x3 = (w2.to(dev), b2p.to(dev), w3.to(dev), b3.float().contiguous().to(dev))
         return self._bf16x3
+
+
+    def bf16x9_packs(self):
+        """Operands of the exact-product split-bf16 level-2 kernel (csrc/sa_bf16x9.hip) for layers 2 and 3 (128 -> 196 -> 256):
+        -> (w [22][8][3][64][8] int16 (pack_sa_bf16x9), b2 [224] zero padded, b3 [256]) as device tensors, channel order as trained; or None
+        where a BN-folded weight does not split exactly into three normal bf16 terms (split_bf16x9) - the caller keeps the fp32 kernel."""
+        if self._bf16x9 is None:
+            (_, _), (W2, b2), (W3, b3) = self._folded_plain
+            try:
+                w = pack_sa_bf16x9(W2, W3)
+            except ValueError:
+                self._bf16x9 = False
+                return None
+            b2p = torch.zeros(224)
+            b2p[:b2.numel()] = b2
+            dev = self._device
+            self._bf16x9 = (w.to(dev), b2p.to(dev), b3.float().contiguous().to(dev))
+        return self._bf16x9 or None
 
 
 def pack_bf16x3(W, n_chunks, k_blocks, chain=True):
@@ -181,6 +200,19 @@ def pack_bf16x9(W, n_chunks, k_blocks, chain=True):
     """W [n_out, k_in] f32 -> int16 [k_blocks][n_chunks][3 = hi, mid, lo][64 lanes][8]: pack_bf16x3's fragment order and k order with the
     three exact terms of split_bf16x9 (checked there: hi + mid + lo == W for every weight).  Out-of-range outputs / inputs are zero."""
     return _gather_fragments(split_bf16x9(_pad_for_fragments(W, n_chunks, k_blocks)), n_chunks, k_blocks, chain)
+
+
+def pack_sa_bf16x9(W2, W3):
+    """Level 2's layer-2 [196, 128] and layer-3 [256, 196 (or zero padded up to 224)] weights -> int16 [22 slices][8 chunks][3][64][8]: the
+    stream of csrc/sa_bf16x9.hip's ring in the order it is consumed.  Slices 0-7: layer 2 as (k-block kb, chunk half h) = 2 kb + h, output
+    chunks 8 h .. 8 h + 7 (13 chunks padded to 16); slices 8-21: layer 3 as (half h, k-block kb) = 8 + 7 h + kb, output chunks 8 h .. 8 h + 7.
+    Fragments, k order and the exactness check are pack_bf16x9's; out-of-range outputs / inputs are zero."""
+    if tuple(W2.shape) != (196, 128) or W3.shape[0] != 256 or not 196 <= W3.shape[1] <= 224:
+        raise ValueError(f"level-2 shapes [196, 128] and [256, 196..224] expected, got {tuple(W2.shape)} and {tuple(W3.shape)}")
+    w2 = pack_bf16x9(W2, 16, 4).reshape(8, 8, 3, 64, 8)                      # [kb][16] -> [(kb, h)][8]
+    w3 = pack_bf16x9(W3, 16, 7)                                              # [kb][16][3][64][8]
+    w3 = torch.stack([w3[:, 8 * h:8 * h + 8] for h in range(2)], dim=0).reshape(14, 8, 3, 64, 8)  # [(h, kb)][8]
+    return torch.cat([w2, w3], dim=0).contiguous()
 
 
 class EncoderWeights:

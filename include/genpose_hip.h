@@ -176,6 +176,17 @@ int gp_sa_pre_mlp_max_bf16x3(int b, int n, int np, int ns, int c1, int c2, int c
                              const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w2_split, const float *bias2,
                              const void *w3_split, const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s);
 
+/* gp_sa_pre_mlp_max for grouping level 2 (c1, c2, c3 = 128, 196, 256; ns = 16 | 32; hoisted first layer: z required) with layers 2 and 3 as
+ * EXACT-PRODUCT split bf16 on the BF16 matrix pipe (csrc/sa_bf16x9.hip: every fp32 operand = hi + mid + lo, all nine bf16 cross products on
+ * v_mfma_f32_16x16x32_bf16, fp32 accumulation - the error class of the fp32 MFMA kernel, as gp_pc_step_bf16x9 is to gp_pc_step_plan).  Layer 1,
+ * the pooling, the inputs and the [b, np, c3] output columns are gp_sa_pre_mlp_max's.  w23_x9: both layers' weights as hi / mid / lo bf16
+ * triples in the kernel's streaming order (genpose_amd/weights.py: pack_sa_bf16x9 - [22 slices][8 chunks][3][64][8] bf16: layer 2 as
+ * (k-block, chunk half), layer 3 as (half, k-block)); bias2 [224] zero padded, bias3 [256], channel order as trained.  b * np * ns must be
+ * a multiple of 32.  What an agent of the PC sampler runs for this level by default (genpose_amd/config.py: encoder_level2); the fp32 entry points above stay selectable. */
+int gp_sa_pre_mlp_max_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c3, const float *xyz, const float *new_xyz, const int32_t *idx,
+                             const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w23_x9, const float *bias2,
+                             const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s);
+
 
 /* Weight packing for the MFMA layers (host-callable helpers operating on HOST memory):
  * W is [n_out, k_in] row-major (torch Linear / 1x1 conv layout).  Packed size in floats = gp_pack_weight_size(). */
