@@ -38,14 +38,56 @@ __device__ __forceinline__ Split8 split8(const f32x4 a, const f32x4 b) {
 // acc[p] += W . X[p] for NT B tiles sharing one A operand W = (hi, mid, lo): the nine exact products of each tile, SMALLEST TERMS FIRST
 // (lo.lo; lo.mid, mid.lo; lo.hi, mid.mid, hi.lo; mid.hi, hi.mid; hi.hi), so the small terms meet the accumulator before the large
 // ones; the tiles are interleaved product by product (independent accumulation chains for the pipe).
-template <int NT>
+// TRANSPOSED: acc[p] += X[p] . W, the activations as the A operand - the same nine products in the same order.
+template <int NT, bool TRANSPOSED = false>
 __device__ __forceinline__ void mma9(const bf16x8 (&w)[3], const Split8 (&x)[NT], f32x4 (&acc)[NT]) {
     constexpr int WA[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0};  // term of W
     constexpr int XB[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0};  // term of X
 #pragma unroll
     for (int q = 0; q < 9; ++q)
 #pragma unroll
-        for (int p = 0; p < NT; ++p) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[WA[q]], x[p].t[XB[q]], acc[p], 0, 0, 0);
+        for (int p = 0; p < NT; ++p) {
+            if constexpr (TRANSPOSED) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[p].t[XB[q]], w[WA[q]], acc[p], 0, 0, 0);
+            else acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[WA[q]], x[p].t[XB[q]], acc[p], 0, 0, 0);
+        }
+}
+
+// End of a ring step: this wave's LDS writes of the step have completed (lgkmcnt), then the bare barrier.  No vmcnt wait: the slice in
+// flight to the registers may stay in flight across it.  The empty asm statements keep LDS accesses on their side.
+__device__ __forceinline__ void ring_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// One step of the two-slot LDS ring every bf16x9 kernel streams its weights through (slice = chunks x (hi, mid, lo) x 64 lanes of
+// bf16x8; NTH threads, PER_T slice elements per thread), over the slice in `slot`: for chunk n < NCH of the slice (output chunk N0 + n
+// of acc), the three weight terms (read one chunk ahead) x the two row tiles' split k-block = 18 MFMAs; beside chunk n < PER_T, element
+// n of the next slice goes from the registers (`hold`, requested a step ago) to the other slot `dst` (last read one step ago) and
+// element n of the slice after it, `src`, is requested; one barrier.  The caller keeps the ring's position and names the three slices.
+template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NA>
+__device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], const Split8 (&xs)[2],
+                                          f32x4 (&acc)[2][NA], int tid, int lane) {
+    static_assert(NCH >= PER_T && N0 + NCH <= NA, "every slice element moves beside a chunk");
+    bf16x8 wf[2][3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) wf[0][t] = slot[t * 64 + lane];
+#pragma unroll
+    for (int n = 0; n < NCH; ++n) {
+        if (n + 1 < NCH) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) wf[(n + 1) & 1][t] = slot[((n + 1) * 3 + t) * 64 + lane];
+        }
+        if (n < PER_T) {
+            dst[tid + n * NTH] = hold[n];
+            hold[n] = src[tid + n * NTH];
+        }
+        f32x4 an[2] = {acc[0][N0 + n], acc[1][N0 + n]};
+        mma9<2, TRANSPOSED>(wf[n & 1], xs, an);
+        acc[0][N0 + n] = an[0], acc[1][N0 + n] = an[1];
+        __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the step
+    }
+    ring_barrier();
 }
 
 }  // namespace gp_bf16x9

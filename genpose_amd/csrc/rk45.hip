@@ -9,7 +9,7 @@
 //   rk45_finish           : denoise step (samplers.py:209-218), normalize_rotation, + centre
 // The error norm is the reference's batch-global RMS over all R*9 components: per-tile partial sums, reduced in
 // a fixed order by the single-workgroup decide kernel (deterministic).
-#include "bf16x9.h"
+#include "trunk_bf16x9.h"
 #include "score_bwd.h"
 #include "trunk_chain_vjp.h"
 
@@ -150,6 +150,80 @@ __device__ __forceinline__ void stx(double *p, double v) {
         *p = v;
 }
 
+// ---- The Dormand-Prince stage arithmetic of ONE state element ge (f64), shared by every stage kernel: the tile kernels (one element per
+// thread and pass), the fp32 chain stage and the bf16x9 chain stage (the components a lane owns).  STAGE 1..6: Runge-Kutta stage;
+// STAGE 0: f0 = fun(t0, y0); STAGE 7: f1 = fun(t0 + h0*dir, y0 + h0*dir*f0).  n = elements of one K_q; XWG as ldx / stx.
+
+// K_q a stage writes: K_STAGE; the two evaluations of the initial step into K_0 and K_1
+template <int STAGE>
+constexpr int STAGE_K = STAGE == 7 ? 1 : STAGE;
+
+// The stage input y (+ h * sum_q a_sq K_q).  commit (stage 1 after an accepted step): y_new and K_6 of that step become y and K_0 first,
+// element-local.  `store`: the element is a live row's and this thread's to write (commit, y_new of stage 6); clamped duplicates of the
+// last row and components another workgroup owns are computed only.
+template <int STAGE, bool XWG = false>
+__device__ __forceinline__ double stage_input(const OdeArgs &a, const Rk45State *st, double h, bool commit, size_t n, size_t ge, bool store) {
+    double yv = commit ? ldx<XWG>(a.ynew + ge) : ldx<XWG>(a.y + ge);
+    if (commit && store) {  // commit the previous accepted step for this element (element-local: no other thread touches it)
+        stx<XWG>(a.y + ge, yv);
+        stx<XWG>(a.K + ge, ldx<XWG>(a.K + 6 * n + ge));
+    }
+    if (STAGE >= 1 && STAGE <= 6) {
+        double dy = 0.0;
+#pragma unroll
+        for (int q = 0; q < STAGE; ++q) {
+            const double kq = (q == 0 && commit) ? ldx<XWG>(a.K + 6 * n + ge) : ldx<XWG>(a.K + (size_t)q * n + ge);
+            dy += kq * DP_A[STAGE][q];
+        }
+        yv = yv + dy * h;  // rk.py: dy = dot(K[:s].T, a[:s]) * h ; y + dy   (stage 6: y + h * dot(K[:-1].T, B))
+        if (STAGE == 6 && store) stx<XWG>(a.ynew + ge, yv);
+    } else if (STAGE == 7) {
+        yv = yv + st->h0 * st->direction * a.K[ge];  // common.py: y1 = y0 + h0 * direction * f0
+    }
+    return yv;
+}
+
+// K_s = -g^2/2 . rhs of the element (drift - 0.5 * g^2 * score, samplers.py:198; :83-86 for the log-density) into Kout, and its term
+// of the stage's sums of squares: the initial step's d0, d1 (stage 0) and d2 (stage 7), the error norm (stage 6)
+template <int STAGE, bool XWG = false>
+__device__ __forceinline__ void stage_emit(const OdeArgs &a, const Rk45State *st, size_t n, size_t ge, double h, double g2, float rhs, double *Kout,
+                                           double &acc0, double &acc1) {
+    const double kv = 0.0 - (0.5 * g2) * (double)rhs;
+    stx<XWG>(Kout + ge, kv);
+    if (STAGE == 0) {
+        const double yv = a.y[ge];
+        const double sc = st->atol + fabs(yv) * st->rtol;
+        acc0 += (yv / sc) * (yv / sc);
+        acc1 += (kv / sc) * (kv / sc);
+    } else if (STAGE == 7) {
+        const double sc = st->atol + fabs(a.y[ge]) * st->rtol;
+        const double d = (kv - a.K[ge]) / sc;
+        acc0 += d * d;
+    } else if (STAGE == 6) {
+        double er = 0.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) er += ldx<XWG>(a.K + (size_t)q * n + ge) * DP_E[q];
+        er += kv * DP_E[6];
+        er *= h;  // rk.py: dot(K.T, E) * h
+        const double yo = ldx<XWG>(a.y + ge), yn = ldx<XWG>(a.ynew + ge);
+        const double sc = st->atol + fmax(fabs(yo), fabs(yn)) * st->rtol;
+        acc0 += (er / sc) * (er / sc);
+    }
+}
+
+// The workgroup's sums -> partials[part] (and, stage 0, partials[second + part])
+template <int STAGE>
+__device__ __forceinline__ void stage_partials(const OdeArgs &a, double acc0, double acc1, int part, int second, double *sh) {
+    if (STAGE == 0 || STAGE == 6 || STAGE == 7) {
+        const double s0 = block_sum(acc0, sh);
+        if (threadIdx.x == 0) a.partials[part] = s0;
+        if (STAGE == 0) {
+            const double s1 = block_sum(acc1, sh);
+            if (threadIdx.x == 0) a.partials[second + part] = s1;
+        }
+    }
+}
+
 // Fused stage kernel.  STAGE 1..6: Runge-Kutta stage;  STAGE 0: f0 = fun(t0, y0) (+ d0,d1 partials);
 // STAGE 7: f1 = fun(t0 + h0*dir, y0 + h0*dir*f0) (+ d2 partial).
 // One stage for the workgroup's tile.  Returns false when the workgroup has nothing to do (padding workgroup, finished solve).
@@ -192,26 +266,7 @@ __device__ __forceinline__ bool rk45_stage_body(const OdeArgs &a, const gp_score
         }
         const bool live = row0 + rr < rend;
         const int r = live ? row0 + rr : rend - 1;  // rows past the end: clamped duplicates (computed, never stored)
-        const size_t ge = (size_t)r * NC + j;
-        const bool commit = STAGE == 1 && st->last_accepted;
-        double yv = commit ? ldx<XWG>(a.ynew + ge) : ldx<XWG>(a.y + ge);
-        if (commit && live && owned(j)) {
-            // commit the previous accepted step for this element (element-local: no other thread touches it)
-            stx<XWG>(a.y + ge, yv);
-            stx<XWG>(a.K + ge, ldx<XWG>(a.K + 6 * n + ge));
-        }
-        if (STAGE >= 1 && STAGE <= 6) {
-            double dy = 0.0;
-#pragma unroll
-            for (int q = 0; q < STAGE; ++q) {
-                const double kq = (q == 0 && commit) ? ldx<XWG>(a.K + 6 * n + ge) : ldx<XWG>(a.K + (size_t)q * n + ge);
-                dy += kq * DP_A[STAGE][q];
-            }
-            yv = yv + dy * h;  // rk.py: dy = dot(K[:s].T, a[:s]) * h ; y + dy   (stage 6: y + h * dot(K[:-1].T, B))
-            if (STAGE == 6 && live && owned(j)) stx<XWG>(a.ynew + ge, yv);
-        } else if (STAGE == 7) {
-            yv = yv + st->h0 * st->direction * a.K[ge];  // common.py: y1 = y0 + h0 * direction * f0
-        }
+        const double yv = stage_input<STAGE, XWG>(a, st, h, STAGE == 1 && st->last_accepted, n, (size_t)r * NC + j, live && owned(j));
         xr[j] = j < POSE ? (float)yv : 0.f;  // torch.tensor(x, dtype=float32) (samplers.py:191); the log-density component is no network input
     }
     if (MODEL == 2) gp_bwd::load_probe_tile(lds, a.probe, row0, rend);
@@ -227,43 +282,15 @@ __device__ __forceinline__ bool rk45_stage_body(const OdeArgs &a, const gp_score
         F = gp_bwd::score_vjp_tile<MODEL == 1 ? gp_bwd::ENERGY : gp_bwd::SCORE_DIV>(lds, net, a.cvec, tvec, row0, rend, a.kcand, pre, sigma);
         ldf = gp_bwd::LDS_OUT;
     }
-    double *Kout = a.K + (size_t)(STAGE == 7 ? 1 : (STAGE == 0 ? 0 : (STAGE == 6 ? 6 : STAGE))) * n;
+    double *Kout = a.K + (size_t)STAGE_K<STAGE> * n;
     double acc0 = 0.0, acc1 = 0.0;
     for (int e = tid; e < P * NC; e += TrunkCfg<P>::NT) {
         const int r = e / NC, j = e - r * NC;
         if (row0 + r >= rend || !owned(j)) continue;
-        const size_t ge = (size_t)(row0 + r) * NC + j;
         const float rhs = MODEL == 0 ? F[r * ldf + j] / (sigma + 1e-7f) : F[r * ldf + j];  // score component (j = 9: divergence estimate)
-        const double kv = 0.0 - (0.5 * g2) * (double)rhs;  // drift - 0.5 * g^2 * score (samplers.py:198; :83-86 for the log-density)
-        stx<XWG>(Kout + ge, kv);
-        if (STAGE == 0) {
-            const double yv = a.y[ge];
-            const double sc = st->atol + fabs(yv) * st->rtol;
-            acc0 += (yv / sc) * (yv / sc);
-            acc1 += (kv / sc) * (kv / sc);
-        } else if (STAGE == 7) {
-            const double sc = st->atol + fabs(a.y[ge]) * st->rtol;
-            const double d = (kv - a.K[ge]) / sc;
-            acc0 += d * d;
-        } else if (STAGE == 6) {
-            double er = 0.0;
-#pragma unroll
-            for (int q = 0; q < 6; ++q) er += ldx<XWG>(a.K + (size_t)q * n + ge) * DP_E[q];
-            er += kv * DP_E[6];
-            er *= h;  // rk.py: dot(K.T, E) * h
-            const double yo = ldx<XWG>(a.y + ge), yn = ldx<XWG>(a.ynew + ge);
-            const double sc = st->atol + fmax(fabs(yo), fabs(yn)) * st->rtol;
-            acc0 += (er / sc) * (er / sc);
-        }
+        stage_emit<STAGE, XWG>(a, st, n, (size_t)(row0 + r) * NC + j, h, g2, rhs, Kout, acc0, acc1);
     }
-    if (STAGE == 0 || STAGE == 6 || STAGE == 7) {
-        const double s0 = block_sum(acc0, sh);
-        if (tid == 0) a.partials[part] = s0;
-        if (STAGE == 0) {
-            const double s1 = block_sum(acc1, sh);
-            if (tid == 0) a.partials[a.nblocks * a.hsplit + part] = s1;
-        }
-    }
+    stage_partials<STAGE>(a, acc0, acc1, part, a.nblocks * a.hsplit, sh);
     return true;
 }
 
@@ -418,28 +445,8 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void rk45_stage_chain_kernel(OdeAr
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            yv[p][c] = 0.0;
-            if (c < nown) {
-                const size_t ge = ge0[p] + c;
-                double v = commit ? a.ynew[ge] : a.y[ge];
-                if (STAGE >= 1 && STAGE <= 6) {
-                    double dy = 0.0;
-#pragma unroll
-                    for (int q = 0; q < STAGE; ++q) {
-                        const double kq = (q == 0 && commit) ? a.K[6 * n + ge] : a.K[(size_t)q * n + ge];
-                        if (q == 0 && commit && live[p]) {  // commit the previous accepted step for this element
-                            a.y[ge] = v;
-                            a.K[ge] = kq;
-                        }
-                        dy += kq * DP_A[STAGE][q];
-                    }
-                    v = v + dy * h;
-                    if (STAGE == 6 && live[p]) a.ynew[ge] = v;
-                } else if (STAGE == 7) {
-                    v = v + st->h0 * st->direction * a.K[ge];
-                }
-                yv[p][c] = v;
-            }
+            yv[p][c] = 0.0;  // (an if, not a conditional expression: see the note at the bf16x9 stage's call)
+            if (c < nown) yv[p][c] = stage_input<STAGE>(a, st, h, commit, n, ge0[p] + c, live[p]);
         }
     }
     gp_chain::State<PT> cs;
@@ -480,7 +487,7 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void rk45_stage_chain_kernel(OdeAr
             }
         }
     }
-    double *Kout = a.K + (size_t)(STAGE == 7 ? 1 : (STAGE == 0 ? 0 : (STAGE == 6 ? 6 : STAGE))) * n;
+    double *Kout = a.K + (size_t)STAGE_K<STAGE> * n;
     double acc0 = 0.0, acc1 = 0.0;
     f32x4 ff[PT];  // f_theta components 4g .. 4g+3 of the lane's rows
 #pragma unroll
@@ -491,7 +498,6 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void rk45_stage_chain_kernel(OdeAr
         for (int c = 0; c < 4; ++c) {
             if (c >= nown || !live[p]) continue;
             const float fc = ff[p][c];
-            const size_t ge = ge0[p] + c;
             float rhs;
             if constexpr (MODEL == 0)
                 rhs = fc / (sigma + 1e-7f);
@@ -499,61 +505,27 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void rk45_stage_chain_kernel(OdeAr
                 rhs = fc / sigma + gx[p][c];  // d/dx <x, f(x)/sigma> (energynet.py:200-222)
             else
                 rhs = (g == 2 && c == 1) ? extra[p] : fc / (sigma + 1e-7f);  // component 9: the divergence estimate (samplers.py:83-86)
-            const double kv = 0.0 - (0.5 * g2) * (double)rhs;
-            Kout[ge] = kv;
-            if (STAGE == 0) {
-                const double y0 = a.y[ge];
-                const double sc = st->atol + fabs(y0) * st->rtol;
-                acc0 += (y0 / sc) * (y0 / sc);
-                acc1 += (kv / sc) * (kv / sc);
-            } else if (STAGE == 7) {
-                const double sc = st->atol + fabs(a.y[ge]) * st->rtol;
-                const double d = (kv - a.K[ge]) / sc;
-                acc0 += d * d;
-            } else if (STAGE == 6) {
-                double er = 0.0;
-#pragma unroll
-                for (int q = 0; q < 6; ++q) er += a.K[(size_t)q * n + ge] * DP_E[q];
-                er += kv * DP_E[6];
-                er *= h;
-                const double yo = a.y[ge], yn = a.ynew[ge];
-                const double sc = st->atol + fmax(fabs(yo), fabs(yn)) * st->rtol;
-                acc0 += (er / sc) * (er / sc);
-            }
+            stage_emit<STAGE>(a, st, n, ge0[p] + c, h, g2, rhs, Kout, acc0, acc1);
         }
     }
-    if (STAGE == 0 || STAGE == 6 || STAGE == 7) {
-        const double s0 = block_sum(acc0, sh);
-        if (threadIdx.x == 0) a.partials[blockIdx.x] = s0;
-        if (STAGE == 0) {
-            const double s1 = block_sum(acc1, sh);
-            if (threadIdx.x == 0) a.partials[a.nblocks + blockIdx.x] = s1;
-        }
-    }
+    stage_partials<STAGE>(a, acc0, acc1, blockIdx.x, a.nblocks, sh);
 }
 
 // The score model's chain stage (rk45_stage_chain_kernel<2, STAGE, 0>) with the trunk as EXACT-PRODUCT split bf16 on the BF16 matrix pipe
-// (bf16x9.h; ODESampler(trunk="bf16x9")).  Around the trunk: that kernel's solver work, line for line - the f64 stage input per owner
-// lane (lane group g owns components 4g .. 4g+3), the commit of the accepted step in stage 1, y_new in stage 6, the h0 probe in stage 7,
-// K_s, the sums of squares as one partial per workgroup, clamped duplicate rows, the early exit - on the same grid and OdeArgs, so the
-// controller, embed, record, group-sums and finish kernels serve both.  The trunk: pc_step_chain_bf16x9's (trunk_bf16x9.hip), its text
-// DUPLICATED here rather than shared - that kernel sits on the register cliff and keeps even its head epilogue written out for that
-// reason.  It wants all nine components of a row in every lane of the row: the owners convert to f32 and the nine are gathered with
-// __shfl; the f64 values are dead before the ring starts.  After each head, every lane keeps its own components of the three outputs.
-constexpr int X9_NW = 4, X9_NT = 64 * X9_NW, X9_RT = 2, X9_ROWS = 16 * X9_RT * X9_NW;
-using X9Lds = gp_split::SplitLds<3, 2>;  // 2 slots of 48 KB
-constexpr int X9_SLICE = X9Lds::SLICE, X9_PER_T = X9_SLICE / X9_NT;
-static_assert(X9_ROWS == gp_chain::Cfg<2>::ROWS && X9_NT == gp_chain::NT && gp_split::NCL == gp_chain::NCL && X9_PER_T <= 16,
+// (bf16x9.h; ODESampler(trunk="bf16x9")).  Around the trunk: that kernel's solver work through the same stage_input / stage_emit /
+// stage_partials - the f64 stage input per owner lane (lane group g owns components 4g .. 4g+3), clamped duplicate rows, the early exit -
+// on the same grid and OdeArgs, so the controller, embed, record, group-sums and finish kernels serve both.  The trunk is
+// trunk_bf16x9.h's, shared with the PC step (trunk_bf16x9.hip).  It wants all nine components of a row in every lane of the row: the owners
+// convert to f32 and the nine are gathered with __shfl; the f64 values are dead before the ring starts.  After each head, the trunk hands
+// over its three outputs and the lane that owns a component writes K_s and its term of the sums of squares.
+using namespace gp_x9trunk;
+static_assert(X9_ROWS == gp_chain::Cfg<2>::ROWS && X9_NT == gp_chain::NT && gp_split::NCL == gp_chain::NCL,
               "the grid, the partials and the admitted shapes of the fp32 chain stage");
 
 template <int STAGE>
 __global__ __launch_bounds__(X9_NT, 1) void rk45_stage_chain_kernel_bf16x9(OdeArgs a, gp_split::SplitNet w) {
-    using namespace gp_split;
-    using namespace gp_bf16x9;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double sh[8];
-    bf16x8 *ring = reinterpret_cast<bf16x8 *>(lds);
-    const float *woutl = lds + X9Lds::OFF_WOUT, *b0l = lds + X9Lds::OFF_B0, *b2l = lds + X9Lds::OFF_B2, *cvtl = lds + X9Lds::OFF_CVT;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), pt = lane & 15, g = lane >> 4;
     const int grp = blockIdx.x / a.bpg, wg_row0 = blockIdx.x * X9_ROWS;
     Rk45State *st = a.st + grp;
@@ -574,199 +546,39 @@ __global__ __launch_bounds__(X9_NT, 1) void rk45_stage_chain_kernel_bf16x9(OdeAr
             const int r = live ? row : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
             double yv[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                yv[c] = 0.0;
-                if (c < nown) {
-                    const size_t ge = (size_t)r * POSE + 4 * g + c;
-                    double v = commit ? a.ynew[ge] : a.y[ge];
-                    if (STAGE >= 1 && STAGE <= 6) {
-                        double dy = 0.0;
-#pragma unroll
-                        for (int q = 0; q < STAGE; ++q) {
-                            const double kq = (q == 0 && commit) ? a.K[6 * n + ge] : a.K[(size_t)q * n + ge];
-                            if (q == 0 && commit && live) {  // commit the previous accepted step for this element
-                                a.y[ge] = v;
-                                a.K[ge] = kq;
-                            }
-                            dy += kq * DP_A[STAGE][q];
-                        }
-                        v = v + dy * h;
-                        if (STAGE == 6 && live) a.ynew[ge] = v;
-                    } else if (STAGE == 7) {
-                        v = v + st->h0 * st->direction * a.K[ge];
-                    }
-                    yv[c] = v;
-                }
-            }
+            // (a conditional expression here, an if in the fp32 chain stage: each form is the one that keeps its kernel's SGPR / AGPR count at
+            // the written-out code's, profiles/r11_shared_ring_stage_resources.txt - do not unify them without that table)
+            for (int c = 0; c < 4; ++c) yv[c] = c < nown ? stage_input<STAGE>(a, st, h, commit, n, (size_t)r * POSE + 4 * g + c, live) : 0.0;
             xf[p] = f32x4{(float)yv[0], (float)yv[1], (float)yv[2], (float)yv[3]};
         }
     }
-    // slice 0 (-> slot 0 below) and slice 1 (-> registers, written during step 0)
     bf16x8 first[X9_PER_T], hold[X9_PER_T];
-#pragma unroll
-    for (int u = 0; u < X9_PER_T; ++u) first[u] = split_slice<3>(w, 0)[tid + u * X9_NT];
-#pragma unroll
-    for (int u = 0; u < X9_PER_T; ++u) hold[u] = split_slice<3>(w, 1)[tid + u * X9_NT];
-    // ---- staged epilogue operands and slot 0
-    split_stage<X9_NT, X9Lds>(lds, w, a.cvec, tvec, wg_row0, a.nrows, a.kcand);
-#pragma unroll
-    for (int u = 0; u < X9_PER_T; ++u) ring[tid + u * X9_NT] = first[u];
-    __syncthreads();
-    int gstep = 0;
-    f32x4 acc[X9_RT][16];
-    // one ring step over slot gstep % 2 (trunk_bf16x9.hip): per output chunk the three weight terms (read one chunk ahead) x the two row
-    // tiles' split k-block = 18 MFMAs; beside chunk n < PER_T, element n of slice gstep + 1 goes from the registers to the other slot and
-    // element n of slice gstep + 2 is requested; one barrier (LDS writes complete, the slice in flight stays in flight)
-    auto ring_step = [&](const Split8 (&xs)[X9_RT]) {
-        const bf16x8 *rslot = ring + (gstep & 1) * X9_SLICE;
-        bf16x8 *dst = ring + ((gstep + 1) & 1) * X9_SLICE;
-        const bf16x8 *src = split_slice<3>(w, gstep + 2);
-        bf16x8 wf[2][3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) wf[0][t] = rslot[t * 64 + lane];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            if (c + 1 < 16) {
-#pragma unroll
-                for (int t = 0; t < 3; ++t) wf[(c + 1) & 1][t] = rslot[((c + 1) * 3 + t) * 64 + lane];
-            }
-            if (c < X9_PER_T) {
-                dst[tid + c * X9_NT] = hold[c];
-                hold[c] = src[tid + c * X9_NT];
-            }
-            f32x4 an[X9_RT];
-#pragma unroll
-            for (int p = 0; p < X9_RT; ++p) an[p] = acc[p][c];
-            mma9<X9_RT>(wf[c & 1], xs, an);
-#pragma unroll
-            for (int p = 0; p < X9_RT; ++p) acc[p][c] = an[p];
-            __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the step
-        }
-        ++gstep;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int p = 0; p < X9_RT; ++p)
-#pragma unroll
-            for (int c = 0; c < 16; ++c) acc[p][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    };
-    // bias + ReLU of a 256-wide hidden layer, kept in fp32 (split one k-block at a time as the next layer consumes it)
-    f32x4 act[X9_RT][16];
-    auto hidden = [&](const float *bias) {
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + 16 * c + 4 * g);
-#pragma unroll
-            for (int p = 0; p < X9_RT; ++p) act[p][c] = relu4(acc[p][c] + bv);
-        }
-    };
-    auto layer = [&]() {  // acc = W . act over the 8 k-blocks of a 256-wide input
-        zero_acc();
-#pragma unroll
-        for (int kb = 0; kb < 8; ++kb) {
-            Split8 xs[X9_RT];
-#pragma unroll
-            for (int p = 0; p < X9_RT; ++p) xs[p] = split8(act[p][2 * kb], act[p][2 * kb + 1]);
-            ring_step(xs);
-        }
-    };
-    // ---- pose_encoder.0: the row's nine f32 components gathered from the lane groups that own them
-    {
-        Split8 xs[X9_RT];
-#pragma unroll
-        for (int p = 0; p < X9_RT; ++p) {
-            float xv[POSE];
-#pragma unroll
-            for (int j = 0; j < POSE; ++j) xv[j] = __shfl(xf[p][j & 3], pt + 16 * (j >> 2), 64);
-            f32x4 pa, pb;
-            split_pose_fragment(xv, g, pa, pb);
-            xs[p] = split8(pa, pb);
-        }
-        zero_acc();
-        ring_step(xs);
-    }
-    hidden(b0l);
-    // ---- pose_encoder.2
-    layer();
-    hidden(b2l);
-    // ---- the three heads; their Linear(256, 3) output layers as fp32 dot products on the accumulator fragments
-    int cl[X9_RT];
+    request(w, tid, first, hold);
+    // the trunk wants the row's nine f32 components in every lane of the row: gathered from the lane groups that own them
+    float xv[X9_RT][POSE];
+    int row[X9_RT];
 #pragma unroll
     for (int p = 0; p < X9_RT; ++p) {
-        const int row = wg_row0 + (wave * X9_RT + p) * 16 + pt;
-        const int r = row < a.nrows ? row : a.nrows - 1;
-        cl[p] = r / a.kcand - wg_row0 / a.kcand;  // < NCL (Cfg<2>::fits(k))
+        row[p] = wg_row0 + (wave * X9_RT + p) * 16 + pt;
+#pragma unroll
+        for (int j = 0; j < POSE; ++j) xv[p][j] = __shfl(xf[p][j & 3], pt + 16 * (j >> 2), 64);
     }
-    // K_s and the sums of squares (the fp32 chain stage's lines) follow each head at once, by the lane group that owns the component:
-    // head hd's outputs are components 3 hd .. 3 hd + 2, final once its epilogue is done - carrying them to the end of the kernel
-    // costs eight more live registers through the other heads' rings, on a kernel that sits on the register cliff
+    // K_s and the sums of squares follow each head at once, by the lane group that owns the component: head hd's outputs are components
+    // 3 hd .. 3 hd + 2, final once its epilogue is done
     const double h = st->h;
     const float sigma = st->stage_sigma[slot];
     const double g2 = st->stage_g2[slot];
-    double *Kout = a.K + (size_t)(STAGE == 7 ? 1 : (STAGE == 0 ? 0 : (STAGE == 6 ? 6 : STAGE))) * n;
+    double *Kout = a.K + (size_t)STAGE_K<STAGE> * n;
     double acc0 = 0.0, acc1 = 0.0;
-#pragma unroll 1
-    for (int hd = 0; hd < 3; ++hd) {
-        layer();
+    run(lds, w, a.cvec, tvec, wg_row0, a.nrows, a.kcand, first, hold, xv, row, [&](int hd, int p, const float (&fh)[3]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int p = 0; p < X9_RT; ++p) {
-            float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const int ch = 16 * c + 4 * g;
-                const f32x4 v = relu4(acc[p][c] + *reinterpret_cast<const f32x4 *>(cvtl + cl[p] * HEADS + 256 * hd + ch));
-                const f32x4 w0 = *reinterpret_cast<const f32x4 *>(woutl + (3 * hd + 0) * HID + ch);
-                const f32x4 w1 = *reinterpret_cast<const f32x4 *>(woutl + (3 * hd + 1) * HID + ch);
-                const f32x4 w2 = *reinterpret_cast<const f32x4 *>(woutl + (3 * hd + 2) * HID + ch);
-                o0 += v.x * w0.x + v.y * w0.y + v.z * w0.z + v.w * w0.w;
-                o1 += v.x * w1.x + v.y * w1.y + v.z * w1.z + v.w * w1.w;
-                o2 += v.x * w2.x + v.y * w2.y + v.z * w2.z + v.w * w2.w;
-            }
-            // the four lane groups hold the four channel quarters: fixed order, every lane gets the sum
-            const float fh[3] = {lane_groups_sum(o0) + w.b_out[3 * hd + 0], lane_groups_sum(o1) + w.b_out[3 * hd + 1],
-                                 lane_groups_sum(o2) + w.b_out[3 * hd + 2]};
-            const int row = wg_row0 + (wave * X9_RT + p) * 16 + pt;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int j = 3 * hd + c;
-                if ((j >> 2) != g || row >= a.nrows) continue;  // component j = 4g + (j & 3): this lane computed its stage input
-                const size_t ge = (size_t)row * POSE + j;
-                const float rhs = fh[c] / (sigma + 1e-7f);
-                const double kv = 0.0 - (0.5 * g2) * (double)rhs;
-                Kout[ge] = kv;
-                if (STAGE == 0) {
-                    const double y0 = a.y[ge];
-                    const double sc = st->atol + fabs(y0) * st->rtol;
-                    acc0 += (y0 / sc) * (y0 / sc);
-                    acc1 += (kv / sc) * (kv / sc);
-                } else if (STAGE == 7) {
-                    const double sc = st->atol + fabs(a.y[ge]) * st->rtol;
-                    const double d = (kv - a.K[ge]) / sc;
-                    acc0 += d * d;
-                } else if (STAGE == 6) {
-                    double er = 0.0;
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) er += a.K[(size_t)q * n + ge] * DP_E[q];
-                    er += kv * DP_E[6];
-                    er *= h;
-                    const double yo = a.y[ge], yn = a.ynew[ge];
-                    const double sc = st->atol + fmax(fabs(yo), fabs(yn)) * st->rtol;
-                    acc0 += (er / sc) * (er / sc);
-                }
-            }
+        for (int c = 0; c < 3; ++c) {
+            const int j = 3 * hd + c;
+            if ((j >> 2) != g || row[p] >= a.nrows) continue;  // component j = 4g + (j & 3): this lane computed its stage input
+            stage_emit<STAGE>(a, st, n, (size_t)row[p] * POSE + j, h, g2, fh[c] / (sigma + 1e-7f), Kout, acc0, acc1);
         }
-    }
-    if (STAGE == 0 || STAGE == 6 || STAGE == 7) {
-        const double s0 = block_sum(acc0, sh);
-        if (threadIdx.x == 0) a.partials[blockIdx.x] = s0;
-        if (STAGE == 0) {
-            const double s1 = block_sum(acc1, sh);
-            if (threadIdx.x == 0) a.partials[a.nblocks + blockIdx.x] = s1;
-        }
-    }
+    });
+    stage_partials<STAGE>(a, acc0, acc1, blockIdx.x, a.nblocks, sh);
 }
 
 __device__ __forceinline__ double sum_partials(const double *p, int nb, double *sh) {
@@ -1101,12 +913,6 @@ __global__ void rk45_set_slot0_kernel(Rk45State *st, double t) {
     if (threadIdx.x == 0) set_stage(st + blockIdx.x, 0, t);
 }
 
-template <typename K>
-int set_lds_attr(K kern, size_t lds) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? GP_OK
-                                                                                                                                            : GP_ELAUNCH;
-}
-
 }  // namespace
 
 // CHAIN: the stage kernels run in the chain form (a.bpg / a.nblocks count 128-row workgroups); the denoising evaluation of phase 5
@@ -1122,22 +928,22 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
     static bool attr_done = false;
     if (!attr_done) {
         if constexpr (CHAIN) {
-            if (set_lds_attr(rk45_stage_chain_kernel<2, 0, MODEL>, chain_lds) || set_lds_attr(rk45_stage_chain_kernel<2, 1, MODEL>, chain_lds) ||
-                set_lds_attr(rk45_stage_chain_kernel<2, 2, MODEL>, chain_lds) || set_lds_attr(rk45_stage_chain_kernel<2, 3, MODEL>, chain_lds) ||
-                set_lds_attr(rk45_stage_chain_kernel<2, 4, MODEL>, chain_lds) || set_lds_attr(rk45_stage_chain_kernel<2, 5, MODEL>, chain_lds) ||
-                set_lds_attr(rk45_stage_chain_kernel<2, 6, MODEL>, chain_lds) || set_lds_attr(rk45_stage_chain_kernel<2, 7, MODEL>, chain_lds))
+            if (set_lds(rk45_stage_chain_kernel<2, 0, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 1, MODEL>, chain_lds) ||
+                set_lds(rk45_stage_chain_kernel<2, 2, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 3, MODEL>, chain_lds) ||
+                set_lds(rk45_stage_chain_kernel<2, 4, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 5, MODEL>, chain_lds) ||
+                set_lds(rk45_stage_chain_kernel<2, 6, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 7, MODEL>, chain_lds))
                 return GP_ELAUNCH;
         }
-        if (set_lds_attr(rk45_stage_kernel<P, 0, MODEL, SPLIT>, lds) || set_lds_attr(rk45_stage_kernel<P, 1, MODEL, SPLIT>, lds) ||
-            set_lds_attr(rk45_stage_kernel<P, 2, MODEL, SPLIT>, lds) || set_lds_attr(rk45_stage_kernel<P, 3, MODEL, SPLIT>, lds) ||
-            set_lds_attr(rk45_stage_kernel<P, 4, MODEL, SPLIT>, lds) || set_lds_attr(rk45_stage_kernel<P, 5, MODEL, SPLIT>, lds) ||
-            set_lds_attr(rk45_stage_kernel<P, 6, MODEL, SPLIT>, lds) || set_lds_attr(rk45_stage_kernel<P, 7, MODEL, SPLIT>, lds))
+        if (set_lds(rk45_stage_kernel<P, 0, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 1, MODEL, SPLIT>, lds) ||
+            set_lds(rk45_stage_kernel<P, 2, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 3, MODEL, SPLIT>, lds) ||
+            set_lds(rk45_stage_kernel<P, 4, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 5, MODEL, SPLIT>, lds) ||
+            set_lds(rk45_stage_kernel<P, 6, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 7, MODEL, SPLIT>, lds))
             return GP_ELAUNCH;
         if constexpr (MODEL != 2) {
-            if (set_lds_attr(rk45_finish_kernel<P, MODEL>, lds)) return GP_ELAUNCH;
+            if (set_lds(rk45_finish_kernel<P, MODEL>, lds)) return GP_ELAUNCH;
         }
         if constexpr (!CHAIN && !SPLIT && P == 16) {
-            if (set_lds_attr(rk45_attempt_kernel<P, MODEL>, lds)) return GP_ELAUNCH;
+            if (set_lds(rk45_attempt_kernel<P, MODEL>, lds)) return GP_ELAUNCH;
         }
         attr_done = true;
     }
@@ -1146,10 +952,10 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
     if constexpr (CHAIN && MODEL == 0) {
         static bool x9_attr_done = false;
         if (x9 && !x9_attr_done) {
-            if (set_lds_attr(rk45_stage_chain_kernel_bf16x9<0>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<1>, X9Lds::BYTES) ||
-                set_lds_attr(rk45_stage_chain_kernel_bf16x9<2>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<3>, X9Lds::BYTES) ||
-                set_lds_attr(rk45_stage_chain_kernel_bf16x9<4>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<5>, X9Lds::BYTES) ||
-                set_lds_attr(rk45_stage_chain_kernel_bf16x9<6>, X9Lds::BYTES) || set_lds_attr(rk45_stage_chain_kernel_bf16x9<7>, X9Lds::BYTES))
+            if (set_lds(rk45_stage_chain_kernel_bf16x9<0>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<1>, X9Lds::BYTES) ||
+                set_lds(rk45_stage_chain_kernel_bf16x9<2>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<3>, X9Lds::BYTES) ||
+                set_lds(rk45_stage_chain_kernel_bf16x9<4>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<5>, X9Lds::BYTES) ||
+                set_lds(rk45_stage_chain_kernel_bf16x9<6>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<7>, X9Lds::BYTES))
                 return GP_ELAUNCH;
             x9_attr_done = true;
         }
@@ -1276,7 +1082,7 @@ static int rk45_attempt_shared(const OdeArgs &a0, const SharedPlan &sp, const gp
     const size_t lds = trunk_lds_bytes<PW>() > trunk_lds_bytes<16>() ? trunk_lds_bytes<PW>() : trunk_lds_bytes<16>();
     static bool attr_done = false;
     if (!attr_done) {
-        if (set_lds_attr(rk45_attempt_shared_kernel<PW>, lds)) return GP_ELAUNCH;
+        if (set_lds(rk45_attempt_shared_kernel<PW>, lds)) return GP_ELAUNCH;
         attr_done = true;
     }
     OdeArgs a = a0;

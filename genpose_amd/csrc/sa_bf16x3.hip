@@ -8,7 +8,8 @@
 // Furthest point sampling and the ball queries see coordinates only: centres and neighbourhoods are bit-identical either way.
 //
 // Form: sa_chain_ring_kernel's (sa_mlp.hip) - 8 waves per workgroup, activations register-resident from the gather to the pooled output,
-// layer-2 weights LDS-resident, layer-3 weights through a 3-slot LDS ring shared by the waves, one barrier per ring step - with
+// layer-2 weights LDS-resident, layer-3 weights through a 3-slot LDS ring shared by the waves, one barrier per ring step; the row front and
+// back end (unit schedule, prefetch, layer 1, pooled store) is sa_rows.h's, shared with sa_bf16x9.hip - with
 //   * 32 rows per wave and iteration (two 16-row sub-chunks: one neighbourhood of 32, or two of 16), so that every weight fragment read
 //     from LDS feeds two rows' worth of matrix instructions (at 16 rows the kernel would be bound by the LDS reads: the matrix work shrinks
 //     5x, the fragment bytes do not);
@@ -18,6 +19,7 @@
 //   * layer 3 in halves of eight output chunks (64 accumulator registers for the two sub-chunks), ring slice = (half, k-block) = 16 KB;
 //   * level 1 (64-64/96-128: all weights fit LDS) runs the same kernel without the ring and without a barrier in the loop.
 #include "bf16x3.h"
+#include "sa_rows.h"
 
 namespace {
 
@@ -53,13 +55,7 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
     float *b3l = b2l + 32 * KB2;                                    // [C3]
     const int tid = threadIdx.x, lane = tid & 63, pt = lane & 15, g = lane >> 4;
     for (int e = tid; e < KB1 * NC2 * 2 * 64; e += NTH) w2l[e] = a.w2[e];
-    for (int e = tid; e < C1; e += NTH) {
-        f32x4 w = *reinterpret_cast<const f32x4 *>(a.wxyz + e * 4);
-        w.w = a.b1[e];
-        w1l[e] = w;
-    }
-    for (int e = tid; e < 32 * KB2; e += NTH) b2l[e] = a.b2[e];
-    for (int e = tid; e < C3; e += NTH) b3l[e] = a.b3[e];
+    gp_sa_rows::stage_operands<C1, KB2, C3, NTH>(a, w1l, b2l, b3l, tid);
     // ring prologue: slices 0 and 1 into slots 0 and 1; slice 2 held in registers
     bf16x8 hold[PER_T];
     if constexpr (RING) {
@@ -73,34 +69,14 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
         for (int e = tid; e < NSL * SLICE; e += NTH) ring[e] = a.w3[e];
     }
     __syncthreads();
-    const int wave_global = blockIdx.x * NWV + __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = gridDim.x * NWV;  // (scalar, as in the fp32 chain kernels)
-    const int my_units = wave_global < nunits_total ? (nunits_total - wave_global + nwaves - 1) / nwaves : 0;
     // RING: every wave runs the same number of iterations (idle ones compute on clamped rows and store nothing): barrier counts match
-    const int nits_wg = RING ? (nunits_total + nwaves - 1) / nwaves : my_units;
-    // unit `it` of this wave: 32 consecutive (centre, sample) rows = sub-chunks s = 0, 1 of 16 rows
-    auto unit_of = [&](int it) { return it < my_units ? wave_global + it * nwaves : 0; };
-    auto load_idx = [&](int it, int (&j)[2]) {
-        const size_t r0 = (size_t)unit_of(it) * 32;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) j[s] = a.idx[r0 + 16 * s + pt];
-    };
-    auto centre_of = [&](int it, int s) { return (unit_of(it) * 32 + 16 * s) / NS; };
-    auto load_d = [&](int it, const int (&j)[2], float (&d)[2][3]) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int cc = centre_of(it, s), bcl = cc / a.np;
-            const float *xyz = a.xyz + (size_t)bcl * a.n * 3;
-            const float *cp = a.new_xyz + (size_t)cc * 3;
-            d[s][0] = xyz[j[s] * 3 + 0] - cp[0];  // grouped_xyz -= new_xyz (pointnet2_utils.py:253)
-            d[s][1] = xyz[j[s] * 3 + 1] - cp[1];
-            d[s][2] = xyz[j[s] * 3 + 2] - cp[2];
-        }
-    };
+    const gp_sa_rows::Units<NS> un(nunits_total, NWV, tid);
+    const int nits_wg = RING ? un.nits_all(nunits_total) : un.my_units;
     int jcur[2], jn[2];
     float dcur[2][3];
-    load_idx(0, jcur);
-    load_d(0, jcur, dcur);
-    load_idx(1, jn);
+    un.load_idx(a, 0, pt, jcur);
+    un.load_d(a, 0, jcur, dcur);
+    un.load_idx(a, 1, pt, jn);
     int gstep = 0;  // global ring step: slice gstep % NSL sits in slot gstep % 3
 #pragma unroll 1
     for (int it = 0; it < nits_wg; ++it) {
@@ -109,11 +85,7 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
         const int g4 = (lo_ >> 4) * 4;
         // ---- layers 1 + 2: k-block by k-block; the hoisted feature rows of k-block kb + 1 are requested while kb is multiplied
         const float *zrow[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int bcl = centre_of(it, s) / a.np;
-            zrow[s] = a.z + ((size_t)bcl * a.n + jcur[s]) * a.zstride + a.zoff + g4;
-        }
+        un.z_rows(a, it, jcur, g4, zrow);
         f32x4 zz[2][2][2];  // [buffer][sub][chunk of the k-block]
 #pragma unroll
         for (int s = 0; s < 2; ++s)
@@ -133,19 +105,8 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
             bf16x8 h1hi[2], h1lo[2];
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const float dx = dcur[s][0], dy = dcur[s][1], dz = dcur[s][2];
                 f32x4 h[2];
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int q = 2 * kb + c;
-                    const f32x4 r0 = w1l[16 * q + g4 + 0], r1 = w1l[16 * q + g4 + 1], r2 = w1l[16 * q + g4 + 2], r3 = w1l[16 * q + g4 + 3];
-                    f32x4 v = zz[kb & 1][s][c];
-                    v.x += (r0.x * dx + r0.y * dy + r0.z * dz) + r0.w;  // the fp32 kernels' layer-1 arithmetic
-                    v.y += (r1.x * dx + r1.y * dy + r1.z * dz) + r1.w;
-                    v.z += (r2.x * dx + r2.y * dy + r2.z * dz) + r2.w;
-                    v.w += (r3.x * dx + r3.y * dy + r3.z * dz) + r3.w;
-                    h[c] = relu4(v);
-                }
+                gp_sa_rows::layer1(w1l, zz[kb & 1][s], dcur[s], kb, g4, h);
                 split8(h[0], h[1], h1hi[s], h1lo[s]);
             }
             // two output chunks at a time: four independent accumulators, the three terms in separate passes over them
@@ -178,12 +139,9 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
                     }
             }
         }
-        // the next unit's indices were requested an iteration ago: its coordinates now, the indices of the one after
-        const int cur_valid = it < my_units;
-        const int unit = unit_of(it);
-        load_d(it + 1, jn, dcur);
-        jcur[0] = jn[0], jcur[1] = jn[1];
-        load_idx(it + 2, jn);
+        const bool cur_valid = it < un.my_units;
+        const int unit = un.unit_of(it);
+        un.advance(a, it, pt, jcur, jn, dcur);
         // ---- bias + ReLU + split of the hidden layer: k-block m of layer 3 = chunks 2m, 2m+1 (a missing odd chunk is zero)
         bf16x8 h2hi[KB2][2], h2lo[KB2][2];
 #pragma unroll
@@ -239,21 +197,10 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
                     __syncthreads();
                 }
             }
-            // pooling over the points (max_i relu(x_i + b) = relu(max_i x_i + b): bias and ReLU once per channel, after the pooling)
+            // pooling over the points, bias + ReLU, store
 #pragma unroll
-            for (int n = 0; n < NC3H; ++n) {
-                const float m0 = points16_max_t(acc3[n][0]), m1 = points16_max_t(acc3[n][1]);
-                const int ch = 16 * (half * NC3H + n) + (lo_ & 15);
-                const float b = b3l[ch];
-                if (cur_valid && g == 0) {
-                    if (NS == 32) {
-                        a.out[(size_t)unit * a.cout_total + a.cout_off + ch] = fmaxf(fmaxf(m0, m1) + b, 0.f);
-                    } else {
-                        a.out[(size_t)(2 * unit) * a.cout_total + a.cout_off + ch] = fmaxf(m0 + b, 0.f);
-                        a.out[(size_t)(2 * unit + 1) * a.cout_total + a.cout_off + ch] = fmaxf(m1 + b, 0.f);
-                    }
-                }
-            }
+            for (int n = 0; n < NC3H; ++n)
+                gp_sa_rows::pooled_store<NS>(a, b3l, acc3[n][0], acc3[n][1], 16 * (half * NC3H + n) + (lo_ & 15), unit, cur_valid && g == 0);
         }
     }
 }
@@ -266,7 +213,7 @@ int launch_bf16x3(const SABfArgs &a, int b, hipStream_t st) {
     auto kern = sa_chain_bf16x3_kernel<C1, C2, C3, NS, RING>;
     static bool done = false;
     if (!done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GP_ELAUNCH;
+        if (set_lds(kern, lds)) return GP_ELAUNCH;
         done = true;
     }
     const int nunits = (int)(((size_t)b * a.np * NS) / 32);
@@ -286,8 +233,9 @@ int gp_sa_pre_mlp_max_bf16x3(int b, int n, int np, int ns, int c1, int c2, int c
                              const void *w3_split, const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s) {
     if (b < 0 || n <= 0 || np <= 0 || !xyz || !new_xyz || !idx || !z || !wxyz || !bias1 || !w2_split || !bias2 || !w3_split || !bias3 || !out)
         return GP_EINVAL;
-    if ((cout_total & 3) || (cout_off & 3) || cout_off + c3 > cout_total || (zstride & 3) || (zoff & 3) || zoff + c1 > zstride) return GP_EINVAL;
-    if (((size_t)b * np * ns) % 32) return GP_EINVAL;  // whole 32-row units
+    if ((cout_total & 3) || (cout_off & 3) || cout_off < 0 || cout_off + c3 > cout_total || (zstride & 3) || (zoff & 3) || zoff < 0 || zoff + c1 > zstride)
+        return GP_EINVAL;
+    if (((size_t)b * np * ns) % 32 || ((size_t)b * np * ns) / 32 > 0x3ffffffu) return GP_EINVAL;  // whole 32-row units, row indices in an int
     if (b == 0) return GP_OK;
     SABfArgs a{n, np, zstride, zoff, xyz, new_xyz, z, idx, wxyz, bias1, reinterpret_cast<const bf16x8 *>(w2_split), bias2,
                reinterpret_cast<const bf16x8 *>(w3_split), bias3, out, cout_total, cout_off};
