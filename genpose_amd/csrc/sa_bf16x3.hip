@@ -55,7 +55,7 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
     float *b3l = b2l + 32 * KB2;                                    // [C3]
     const int tid = threadIdx.x, lane = tid & 63, pt = lane & 15, g = lane >> 4;
     for (int e = tid; e < KB1 * NC2 * 2 * 64; e += NTH) w2l[e] = a.w2[e];
-    gp_sa_rows::stage_operands<C1, KB2, C3, NTH>(a, w1l, b2l, b3l, tid);
+    gp_sa_rows::stage_operands<C1, 32 * KB2, C3, NTH>(a, w1l, b2l, b3l, tid);
     // ring prologue: slices 0 and 1 into slots 0 and 1; slice 2 held in registers
     bf16x8 hold[PER_T];
     if constexpr (RING) {
@@ -106,7 +106,8 @@ __global__ __launch_bounds__(512) void sa_chain_bf16x3_kernel(SABfArgs a, int nu
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 f32x4 h[2];
-                gp_sa_rows::layer1(w1l, zz[kb & 1][s], dcur[s], kb, g4, h);
+#pragma unroll
+                for (int c = 0; c < 2; ++c) h[c] = gp_sa_rows::layer1(w1l, 2 * kb + c, g4, zz[kb & 1][s][c], dcur[s][0], dcur[s][1], dcur[s][2]);  // chunks 2 kb, 2 kb + 1
                 split8(h[0], h[1], h1hi[s], h1lo[s]);
             }
             // two output chunks at a time: four independent accumulators, the three terms in separate passes over them

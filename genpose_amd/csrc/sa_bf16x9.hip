@@ -80,7 +80,7 @@ __global__ __launch_bounds__(SX_NTH) void sa_chain_bf16x9_kernel(SAX9Args a, int
     float *b2l = reinterpret_cast<float *>(w1l + C1);               // [32 KB2]
     float *b3l = b2l + 32 * KB2;                                    // [C3]
     const int tid = threadIdx.x, lane = tid & 63, pt = lane & 15, g = lane >> 4;
-    gp_sa_rows::stage_operands<C1, KB2, C3, NTH>(a, w1l, b2l, b3l, tid);
+    gp_sa_rows::stage_operands<C1, 32 * KB2, C3, NTH>(a, w1l, b2l, b3l, tid);
     // ring prologue: slice 0 into slot 0; slice 1 held in registers (written during step 0)
     bf16x8 hold[SX_PER_T];
 #pragma unroll
@@ -122,7 +122,8 @@ __global__ __launch_bounds__(SX_NTH) void sa_chain_bf16x9_kernel(SAX9Args a, int
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 f32x4 h[2];
-                gp_sa_rows::layer1(w1l, zz[s], dcur[s], kb, g4, h);
+#pragma unroll
+                for (int c = 0; c < 2; ++c) h[c] = gp_sa_rows::layer1(w1l, 2 * kb + c, g4, zz[s][c], dcur[s][0], dcur[s][1], dcur[s][2]);  // chunks 2 kb, 2 kb + 1
                 xs[s] = split8(h[0], h[1]);
             }
             // (into the registers layer 1 has just consumed: the two ring steps cover the latency)

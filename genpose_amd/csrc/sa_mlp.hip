@@ -8,8 +8,11 @@
 //   layer 1: LDS A -> LDS B,  layer 2: LDS B -> LDS A,  layer 3: LDS A -> registers -> max -> global.
 // Weights stream from L2 straight into MFMA A-operand registers (host-packed fragment order, gp_common.h).
 #include "gp_common.h"
+#include "sa_rows.h"
 
 namespace {
+
+namespace rows = gp_sa_rows;
 
 struct SAArgs {
     int n, np, ns, cin, c1, c2, c3;
@@ -20,10 +23,22 @@ struct SAArgs {
     int cout_total, cout_off, groupall;
 };
 
+// what the tile kernels' last layer reads of SAArgs / SAPreArgs
+struct L3Args {
+    int np, ns, c3, groupall;
+    const float *w3, *b3;
+    float *out;
+    int cout_total, cout_off;
+};
+template <class A>
+__device__ __forceinline__ L3Args l3_args(const A &a) {
+    return L3Args{a.np, a.ns, a.c3, a.groupall, a.w3, a.b3, a.out, a.cout_total, a.cout_off};
+}
+
 // layer 3 + max over the neighbourhood, straight from the accumulators (WN waves along channels, PT p-chunks per wave)
-// [nc_lo, nc_hi): the 16-channel output chunks this workgroup computes (all of them unless the launch splits the channels, launch_pre)
+// [nc_lo, nc_hi): the 16-channel output chunks this workgroup computes (all of them unless the launch splits the channels, launch_tiles)
 template <int PT, int WN>
-__device__ __forceinline__ void layer3_max(const SAArgs &a, const float *A, int lda, int c2p, int row0, int b, int nc_lo = 0, int nc_hi = 1 << 30) {
+__device__ __forceinline__ void layer3_max(const L3Args &a, const float *A, int lda, int c2p, int row0, int b, int nc_lo, int nc_hi) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wn = wave % WN, wp = wave / WN;
     const int KG = c2p / 16, NC = gp_round16(a.c3) / 16;
@@ -92,6 +107,25 @@ __device__ __forceinline__ void layer3_max(const SAArgs &a, const float *A, int 
     }
 }
 
+// The tile kernels' last layer with the channel split (gridDim.z workgroups per row tile, launch_tiles on small GroupAll batches): every
+// workgroup has computed layers 1-2 for its rows and takes its share of the last layer's output chunks - same MFMA order per output as the
+// unsplit launch, bit for bit
+template <int P>
+__device__ __forceinline__ void layer3_max_split(const L3Args &a, const float *A, int lda, int c2p, int row0, int b) {
+    const int NC3 = gp_round16(a.c3) / 16, per = (NC3 + (int)gridDim.z - 1) / (int)gridDim.z;
+    const int nc_lo = (int)blockIdx.z * per, nc_hi = nc_lo + per < NC3 ? nc_lo + per : NC3;
+    if (nc_lo >= nc_hi) return;
+    // a wave must own whole neighbourhoods for the in-register max: >= ns points per wave (GroupAll: any split, atomics combine)
+    const int wn = pick_wn(nc_hi - nc_lo, P, a.groupall ? 16 : a.ns);
+    if constexpr (P >= 64) {
+        if (wn == 1) return layer3_max<P / 64, 1>(a, A, lda, c2p, row0, b, nc_lo, nc_hi);
+    }
+    if constexpr (P >= 32) {
+        if (wn == 2) return layer3_max<P / 32, 2>(a, A, lda, c2p, row0, b, nc_lo, nc_hi);
+    }
+    layer3_max<P / 16, 4>(a, A, lda, c2p, row0, b, nc_lo, nc_hi);
+}
+
 template <int P>
 __global__ __launch_bounds__(256) void sa_mlp_kernel(SAArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -142,20 +176,7 @@ __global__ __launch_bounds__(256) void sa_mlp_kernel(SAArgs a) {
     __syncthreads();
     dense_to_lds<P, true>(Bf, ldb, a.w2, a.b2, a.c1, a.c2, A, lda);
     __syncthreads();
-    // channel split (gridDim.z workgroups per row tile, launch<P> on small GroupAll batches): every workgroup has computed layers 1-2 for
-    // its rows and takes its share of the last layer's output chunks - same MFMA order per output as the unsplit launch, bit for bit
-    const int NC3 = gp_round16(a.c3) / 16, per = (NC3 + (int)gridDim.z - 1) / (int)gridDim.z;
-    const int nc_lo = (int)blockIdx.z * per, nc_hi = nc_lo + per < NC3 ? nc_lo + per : NC3;
-    if (nc_lo >= nc_hi) return;
-    // a wave must own whole neighbourhoods for the in-register max: >= ns points per wave (GroupAll: any split, atomics combine)
-    const int wn = pick_wn(nc_hi - nc_lo, P, a.groupall ? 16 : a.ns);
-    if constexpr (P >= 64) {
-        if (wn == 1) return layer3_max<P / 64, 1>(a, A, lda, c2p, row0, b, nc_lo, nc_hi);
-    }
-    if constexpr (P >= 32) {
-        if (wn == 2) return layer3_max<P / 32, 2>(a, A, lda, c2p, row0, b, nc_lo, nc_hi);
-    }
-    layer3_max<P / 16, 4>(a, A, lda, c2p, row0, b, nc_lo, nc_hi);
+    layer3_max_split<P>(l3_args(a), A, lda, c2p, row0, b);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -305,9 +326,7 @@ int launch_point_linear_ws(int rows, int n_out, const float *x, const float *wpa
     constexpr size_t lds = (size_t)R * (K + GP_LD_PAD) * sizeof(float);
     static bool done = false;
     if (!done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(point_linear_ws_kernel<KB, NCW, PT, PF, WGS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(point_linear_ws_kernel<KB, NCW, PT, PF, WGS>, lds)) return GP_ELAUNCH;
         done = true;
     }
     const int ntiles = (rows + R - 1) / R, nsplit = n_out / (64 * NCW);
@@ -374,55 +393,29 @@ __global__ __launch_bounds__(256) void sa_pre_mlp_kernel(SAPreArgs a) {
             const f32x4 w1 = *reinterpret_cast<const f32x4 *>(a.wxyz + (4 * q + 1) * 4);
             const f32x4 w2 = *reinterpret_cast<const f32x4 *>(a.wxyz + (4 * q + 2) * 4);
             const f32x4 w3 = *reinterpret_cast<const f32x4 *>(a.wxyz + (4 * q + 3) * 4);
-            v.x += w0.x * d.x + w0.y * d.y + w0.z * d.z;
-            v.y += w1.x * d.x + w1.y * d.y + w1.z * d.z;
-            v.z += w2.x * d.x + w2.y * d.y + w2.z * d.z;
-            v.w += w3.x * d.x + w3.y * d.y + w3.z * d.z;
-            v.x = fmaxf(v.x, 0.f);
-            v.y = fmaxf(v.y, 0.f);
-            v.z = fmaxf(v.z, 0.f);
-            v.w = fmaxf(v.w, 0.f);
-            *reinterpret_cast<f32x4 *>(Bf + r * ldb + 4 * q) = v;
+            v.x += rows::xyz_dot(w0, d.x, d.y, d.z);  // (b1 + z) + dot
+            v.y += rows::xyz_dot(w1, d.x, d.y, d.z);
+            v.z += rows::xyz_dot(w2, d.x, d.y, d.z);
+            v.w += rows::xyz_dot(w3, d.x, d.y, d.z);
+            *reinterpret_cast<f32x4 *>(Bf + r * ldb + 4 * q) = relu4(v);
         }
     }
     __syncthreads();
     dense_to_lds<P, true>(Bf, ldb, a.w2, a.b2, a.c1, a.c2, A, lda);
     __syncthreads();
-    SAArgs l3;  // layer 3 + max reuses the generic epilogue
-    l3.n = a.n, l3.np = a.np, l3.ns = a.ns, l3.cin = 0, l3.c1 = a.c1, l3.c2 = a.c2, l3.c3 = a.c3;
-    l3.xyz = nullptr, l3.feats_in = nullptr, l3.new_xyz = nullptr, l3.idx = nullptr;
-    l3.w1 = l3.b1 = l3.w2 = l3.b2 = nullptr, l3.w3 = a.w3, l3.b3 = a.b3;
-    l3.out = a.out, l3.cout_total = a.cout_total, l3.cout_off = a.cout_off, l3.groupall = a.groupall;
-    // channel split (gridDim.z workgroups per row tile, launch_pre): every workgroup has computed layers 1-2 for its rows and takes its
-    // share of the last layer's output chunks - same MFMA order per output, so the results are those of the unsplit launch, bit for bit
-    const int NC3 = gp_round16(a.c3) / 16, per = (NC3 + (int)gridDim.z - 1) / (int)gridDim.z;
-    const int nc_lo = (int)blockIdx.z * per, nc_hi = nc_lo + per < NC3 ? nc_lo + per : NC3;
-    if (nc_lo >= nc_hi) return;
-    const int wn = pick_wn(nc_hi - nc_lo, P, a.groupall ? 16 : a.ns);
-    if constexpr (P >= 64) {
-        if (wn == 1) return layer3_max<P / 64, 1>(l3, A, lda, c2p, row0, b, nc_lo, nc_hi);
-    }
-    if constexpr (P >= 32) {
-        if (wn == 2) return layer3_max<P / 32, 2>(l3, A, lda, c2p, row0, b, nc_lo, nc_hi);
-    }
-    layer3_max<P / 16, 4>(l3, A, lda, c2p, row0, b, nc_lo, nc_hi);
+    layer3_max_split<P>(l3_args(a), A, lda, c2p, row0, b);
 }
 
-template <int P>
-int launch_pre(const SAPreArgs &a, int b, hipStream_t st) {
-    const int c1p = gp_round16(a.c1), c2p = gp_round16(a.c2);
-    const size_t lds = ((size_t)P * (c2p + c1p + 2 * GP_LD_PAD) + (size_t)P * 4 + P) * sizeof(float);
+// A tile kernel's launch: one workgroup per P rows and cloud.
+// The GroupAll level of a SMALL batch (a tracking frame: 5 clouds = 20 tiles; one cloud: 4): every tile streams all of both weight
+// matrices (0.77 / 1.15 MB) through one CU while the others idle - 48 us per launch whatever the batch.  While the chip has CUs to spare,
+// 2 or 4 workgroups share a row tile: each recomputes layers 1-2 (a third of the work) and takes a half / quarter of layer 3's channels.
+template <int P, class K, class A>
+int launch_tiles(K kern, const A &a, size_t lds, int b, hipStream_t st) {
     if (lds > 160 * 1024) return GP_EINVAL;
-    auto kern = sa_pre_mlp_kernel<P>;
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
-    }
+    if (lds > 64 * 1024 && set_lds(kern, lds)) return GP_ELAUNCH;
     const int nrows = a.groupall ? a.n : a.np * a.ns;
     const int tiles = (nrows + P - 1) / P;
-    // The GroupAll level of a SMALL batch (a tracking frame: 5 clouds = 20 tiles; one cloud: 4): every tile streams all of both weight
-    // matrices (0.77 / 1.15 MB) through one CU while the others idle - 48 us per launch whatever the batch.  While the chip has CUs to spare,
-    // 2 or 4 workgroups share a row tile: each recomputes layers 1-2 (a third of the work) and takes a half / quarter of layer 3's channels.
     int split = 1;
     if (a.groupall) {
         const int ncu = gp_num_cus();
@@ -430,6 +423,12 @@ int launch_pre(const SAPreArgs &a, int b, hipStream_t st) {
     }
     hipLaunchKernelGGL(kern, dim3(tiles, b, split), dim3(256), lds, st, a);
     return gp_launch_status();
+}
+
+template <int P>
+int launch_pre(const SAPreArgs &a, int b, hipStream_t st) {
+    const int c1p = gp_round16(a.c1), c2p = gp_round16(a.c2);
+    return launch_tiles<P>(sa_pre_mlp_kernel<P>, a, ((size_t)P * (c2p + c1p + 2 * GP_LD_PAD) + (size_t)P * 4 + P) * sizeof(float), b, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -503,12 +502,12 @@ __global__ __launch_bounds__(256, 3) void sa0_chain_kernel(SAPreArgs a, int ncen
             f32x4 h1[Q1], h2[Q2];
 #pragma unroll
             for (int q = 0; q < Q1; ++q) {
-                f32x4 v = bb1[q];
-                v.x += w1[q][0].x * dx + w1[q][0].y * dy + w1[q][0].z * dz;
-                v.y += w1[q][1].x * dx + w1[q][1].y * dy + w1[q][1].z * dz;
-                v.z += w1[q][2].x * dx + w1[q][2].y * dy + w1[q][2].z * dz;
-                v.w += w1[q][3].x * dx + w1[q][3].y * dy + w1[q][3].z * dz;
-                h1[q] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+                f32x4 v = bb1[q];  // b1 + dot
+                v.x += rows::xyz_dot(w1[q][0], dx, dy, dz);
+                v.y += rows::xyz_dot(w1[q][1], dx, dy, dz);
+                v.z += rows::xyz_dot(w1[q][2], dx, dy, dz);
+                v.w += rows::xyz_dot(w1[q][3], dx, dy, dz);
+                h1[q] = relu4(v);
             }
             // every output chunk of a layer has its own accumulator and the chunks are interleaved k-step by k-step: consecutive
             // MFMAs never wait on each other's result (40-cycle dependent latency against a 32-cycle issue interval)
@@ -523,10 +522,7 @@ __global__ __launch_bounds__(256, 3) void sa0_chain_kernel(SAPreArgs a, int ncen
 #pragma unroll
                         for (int n = 0; n < Q2; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2[n][q][jj], h1[q][jj], acc[n], 0, 0, 0);
 #pragma unroll
-                for (int n = 0; n < Q2; ++n) {
-                    const f32x4 v = acc[n] + bb2[n];
-                    h2[n] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-                }
+                for (int n = 0; n < Q2; ++n) h2[n] = relu4(acc[n] + bb2[n]);
             }
             {
                 // last layer TRANSPOSED (activations as the A operand): lane = channel, registers x lane groups = the 16 rows
@@ -546,11 +542,7 @@ __global__ __launch_bounds__(256, 3) void sa0_chain_kernel(SAPreArgs a, int ncen
                 }
             }
         }
-        // max_i relu(x_i + b) = relu(max_i x_i + b): bias and ReLU once per channel, after the pooling (exact: rounding is monotone)
-        float *o = a.out + (size_t)c * a.cout_total + a.cout_off;
-#pragma unroll
-        for (int n = 0; n < Q3; ++n)
-            if (g == 0) o[16 * n + pt] = fmaxf(res[n] + bb3[n], 0.f);
+        rows::pooled_store_chunks(a.out + (size_t)c * a.cout_total + a.cout_off, res, [&](int n) { return bb3[n]; }, pt, g == 0);
 #pragma unroll
         for (int p = 0; p < PT; ++p) {
             dcur[p][0] = dn[p][0], dcur[p][1] = dn[p][1], dcur[p][2] = dn[p][2];
@@ -574,11 +566,7 @@ __global__ __launch_bounds__(256, 3) void sa_chain_lds_kernel(SAPreArgs a, int n
     const int tid = threadIdx.x, lane = tid & 63, pt = lane & 15, g = lane >> 4;
     for (int e = tid; e < Q1 * Q2 * 64; e += 256) w2l[e] = reinterpret_cast<const f32x4 *>(a.w2)[e];
     for (int e = tid; e < Q2 * Q3 * 64; e += 256) w3l[e] = reinterpret_cast<const f32x4 *>(a.w3)[e];
-    for (int e = tid; e < C1; e += 256) {
-        f32x4 w = *reinterpret_cast<const f32x4 *>(a.wxyz + e * 4);
-        w.w = a.b1[e];
-        w1l[e] = w;
-    }
+    rows::stage_operands<C1, 0, 0, 256>(a, w1l, nullptr, nullptr, tid);  // (the biases of layers 2 and 3: registers, below)
     f32x4 bb2[Q2];
     float bb3[Q3];  // the last layer runs transposed (lane = channel 16 n + pt, see points16_max_t): one bias per lane and chunk
 #pragma unroll
@@ -586,41 +574,14 @@ __global__ __launch_bounds__(256, 3) void sa_chain_lds_kernel(SAPreArgs a, int n
 #pragma unroll
     for (int n = 0; n < Q3; ++n) bb3[n] = a.b3[16 * n + pt];
     __syncthreads();
-    const int wave_global = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = gridDim.x * 4;  // (scalar, as in sa0_chain_kernel)
-    // The wave walks 16-row chunks: iteration `it` is chunk p = it % PT of the wave's (it / PT)-th neighbourhood, so the
-    // per-iteration register footprint is one chunk whatever the neighbourhood size (the running max lives in `res`).
-    const int my_centres = wave_global < ncentres_total ? (ncentres_total - wave_global + nwaves - 1) / nwaves : 0;
-    const int nits = my_centres * PT;
-    auto chunk_row0 = [&](int it, int &c) {
-        c = wave_global + (it / PT) * nwaves;
-        return (size_t)c * NS + (size_t)(it % PT) * 16;
-    };
-    auto load_idx = [&](int it) {
-        int c;
-        const size_t r0 = chunk_row0(it, c);
-        return it < nits ? a.idx[r0 + pt] : 0;
-    };
-    // operands of one chunk: xyz deltas and the gathered rows of Z (this lane's channels 16q + 4g + 0..3)
-    auto load_ops = [&](int it, int j, float (&d)[3], f32x4 (&zz)[Q1]) {
-        int c;
-        chunk_row0(it, c);
-        const int cc = it < nits ? c : 0;
-        const int bcl = cc / a.np;
-        const float *xyz = a.xyz + (size_t)bcl * a.n * 3;
-        const float *zb = a.z + (size_t)bcl * a.n * a.zstride + a.zoff;
-        const float *cp = a.new_xyz + (size_t)cc * 3;
-        d[0] = xyz[j * 3 + 0] - cp[0];  // grouped_xyz -= new_xyz (pointnet2_utils.py:253)
-        d[1] = xyz[j * 3 + 1] - cp[1];
-        d[2] = xyz[j * 3 + 2] - cp[2];
-#pragma unroll
-        for (int q = 0; q < Q1; ++q) zz[q] = *reinterpret_cast<const f32x4 *>(zb + (size_t)j * a.zstride + 16 * q + 4 * g);
-    };
+    const rows::Chunks<NS> ch(ncentres_total, 4, __builtin_amdgcn_readfirstlane(tid >> 6));  // (scalar wave index, as in sa0_chain_kernel)
+    const int nits = ch.nits;
     int jn, jnn;
     float dcur[3], dn[3];
     f32x4 zcur[Q1], zn[Q1];
-    jn = load_idx(0);
-    load_ops(0, jn, dcur, zcur);
-    jn = load_idx(1);
+    jn = ch.load_idx(a, 0, pt);
+    ch.load_ops(a, 0, jn, g, dcur, zcur);
+    jn = ch.load_idx(a, 1, pt);
     float res[Q3];  // running max over the neighbourhood's rows of the pre-bias layer-3 output, per channel 16 n + pt
     // The weight fragments are read from LDS as ONE software-pipelined stream per 16-row chunk: layer-2 groups (two output chunks of
     // one k-group: 8 MFMAs) in order (n0, q), then layer-3 groups (four output chunks of one k-group: 16 MFMAs); the fragments of
@@ -642,8 +603,8 @@ __global__ __launch_bounds__(256, 3) void sa_chain_lds_kernel(SAPreArgs a, int n
     ld2(0, w2b[0], lane);
 #pragma unroll 1
     for (int it = 0; it < nits; ++it) {
-        load_ops(it + 1, jn, dn, zn);
-        jnn = load_idx(it + 2);
+        ch.load_ops(a, it + 1, jn, g, dn, zn);
+        jnn = ch.load_idx(a, it + 2, pt);
         // the weight fragments are loop-invariant LDS reads: launder the lane offset so hipcc keeps them as streamed
         // ds_read_b128 inside the loop instead of hoisting all (Q1*Q2 + Q2*Q3) fragments into registers (spills)
         int lo = lane;
@@ -653,16 +614,7 @@ __global__ __launch_bounds__(256, 3) void sa_chain_lds_kernel(SAPreArgs a, int n
             const float dx = dcur[0], dy = dcur[1], dz = dcur[2];
             f32x4 h1[Q1], h2[Q2];
 #pragma unroll
-            for (int q = 0; q < Q1; ++q) {
-                const int g4 = (lo >> 4) * 4;
-                const f32x4 r0 = w1l[16 * q + g4 + 0], r1 = w1l[16 * q + g4 + 1], r2 = w1l[16 * q + g4 + 2], r3 = w1l[16 * q + g4 + 3];
-                f32x4 v = zcur[q];
-                v.x += (r0.x * dx + r0.y * dy + r0.z * dz) + r0.w;
-                v.y += (r1.x * dx + r1.y * dy + r1.z * dz) + r1.w;
-                v.z += (r2.x * dx + r2.y * dy + r2.z * dz) + r2.w;
-                v.w += (r3.x * dx + r3.y * dy + r3.z * dz) + r3.w;
-                h1[q] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-            }
+            for (int q = 0; q < Q1; ++q) h1[q] = rows::layer1(w1l, q, (lo >> 4) * 4, zcur[q], dx, dy, dz);
             // layer 2: two output chunks in flight (independent accumulators hide the 40-cycle dependent MFMA latency)
             f32x4 acc2[2];
 #pragma unroll
@@ -683,10 +635,7 @@ __global__ __launch_bounds__(256, 3) void sa_chain_lds_kernel(SAPreArgs a, int n
                 if (q == Q1 - 1) {
 #pragma unroll
                     for (int u = 0; u < 2; ++u)
-                        if (n0 + u < Q2) {
-                            f32x4 v = acc2[u] + bb2[n0 + u];
-                            h2[n0 + u] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-                        }
+                        if (n0 + u < Q2) h2[n0 + u] = relu4(acc2[u] + bb2[n0 + u]);
                 }
             }
             // layer 3 + running max over the neighbourhood's chunks: four output chunks in flight
@@ -714,14 +663,7 @@ __global__ __launch_bounds__(256, 3) void sa_chain_lds_kernel(SAPreArgs a, int n
                 }
             }
         }
-        if (p == PT - 1) {
-            // max_i relu(x_i + b) = relu(max_i x_i + b): bias and ReLU once per channel, after the pooling (exact: rounding is monotone)
-            const int c = wave_global + (it / PT) * nwaves;
-            float *o = a.out + (size_t)c * a.cout_total + a.cout_off;
-#pragma unroll
-            for (int n = 0; n < Q3; ++n)
-                if (g == 0) o[16 * n + pt] = fmaxf(res[n] + bb3[n], 0.f);
-        }
+        if (p == PT - 1) rows::pooled_store_chunks(a.out + (size_t)ch.centre_of(it) * a.cout_total + a.cout_off, res, [&](int n) { return bb3[n]; }, pt, g == 0);
         dcur[0] = dn[0], dcur[1] = dn[1], dcur[2] = dn[2];
         jn = jnn;
 #pragma unroll
@@ -737,8 +679,7 @@ int launch_chain_lds(const SAPreArgs &a, int b, hipStream_t st) {
     auto kern = sa_chain_lds_kernel<C1, C2, C3, NS>;
     static bool done = false;
     if (!done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(kern, lds)) return GP_ELAUNCH;
         done = true;
     }
     const int ncentres = b * a.np;
@@ -751,6 +692,13 @@ int launch_chain_lds(const SAPreArgs &a, int b, hipStream_t st) {
     return gp_launch_status();
 }
 
+// out[r][0 .. 4 w4) = 0 for the rows of a [rows][ld] tensor: the zeroed output the SPLITP form below combines into
+__global__ __launch_bounds__(256) void zero_columns_kernel(float *out, int ld, int w4, int total) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < total) *reinterpret_cast<f32x4 *>(out + (size_t)(e / w4) * ld + 4 * (e % w4)) = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+
 // Chain kernel for a level whose layer-3 weights do not fit LDS (light config level 2: 128 -> 196 -> 256):
 //   * 8 waves per workgroup, each wave walks its own neighbourhoods 16 rows at a time, activations in registers;
 //   * layer-2 weights (Q1*Q2 KB) are LDS-resident; layer-3 weights stream through a 3-slot LDS ring, one k-group slice
@@ -761,12 +709,6 @@ int launch_chain_lds(const SAPreArgs &a, int b, hipStream_t st) {
 // SPREAD (hidden-layer layout GP_SA_TAIL_SPREAD, genpose_hip.h): the r = C2 % 16 channels of the last, partly filled 16-channel block
 // sit at positions 4 (c % 4) + c / 4, i.e. in k-steps jj < ceil(r / 4) of all four lane groups, so layer 3 skips the k-steps of
 // that block that only multiply padding (196 channels: one MFMA instead of four, -5.8 % of layer 3).
-// out[r][0 .. 4 w4) = 0 for the rows of a [rows][ld] tensor: the zeroed output the SPLITP form below combines into
-__global__ __launch_bounds__(256) void zero_columns_kernel(float *out, int ld, int w4, int total) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < total) *reinterpret_cast<f32x4 *>(out + (size_t)(e / w4) * ld + 4 * (e % w4)) = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
 // SPLITP (small batches: fewer neighbourhoods than the chip has wave slots for): the unit of work is one 16-row CHUNK of a neighbourhood
 // instead of the neighbourhood - twice the waves, half the iterations; a unit applies bias and ReLU to its own maximum and combines with
 // the neighbourhood's other chunk through an integer atomic max (values >= 0: the order of the bit patterns) into the ZEROED output.
@@ -785,13 +727,7 @@ __global__ __launch_bounds__(512) void sa_chain_ring_kernel(SAPreArgs a, int nce
     float *b3l = b2l + 16 * Q2;                         // a global read there waits (in-order vmcnt) for every operand request in flight
     const int tid = threadIdx.x, lane = tid & 63, pt = lane & 15, g = lane >> 4;
     for (int e = tid; e < Q1 * Q2 * 64; e += NTH) w2l[e] = reinterpret_cast<const f32x4 *>(a.w2)[e];
-    for (int e = tid; e < C1; e += NTH) {
-        f32x4 w = *reinterpret_cast<const f32x4 *>(a.wxyz + e * 4);
-        w.w = a.b1[e];
-        w1l[e] = w;
-    }
-    for (int e = tid; e < 16 * Q2; e += NTH) b2l[e] = a.b2[e];
-    for (int e = tid; e < C3; e += NTH) b3l[e] = a.b3[e];
+    rows::stage_operands<C1, 16 * Q2, C3, NTH>(a, w1l, b2l, b3l, tid);
     const f32x4 *w3g = reinterpret_cast<const f32x4 *>(a.w3);  // [Q2][Q3][64]: slice q = w3g + q*SLICE
     // ring prologue: slices 0 and 1 into slots 0 and 1; slice 2 held in registers
     f32x4 hold[PER_T];
@@ -804,49 +740,17 @@ __global__ __launch_bounds__(512) void sa_chain_ring_kernel(SAPreArgs a, int nce
     __syncthreads();
     // the wave's index as a SCALAR (the centre index and everything addressed through it stay on the scalar unit: -7 % VALU instructions,
     // -2.8 % time at NS = 32); at NS = 16 the same change measured +1.3 % (another schedule of the same loop), so that form keeps the vector index
-    const int wave_in_wg = NS == 16 ? (tid >> 6) : __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wave_global = blockIdx.x * NWV + wave_in_wg, nwaves = gridDim.x * NWV;
-    const int nunits = SPLITP ? ncentres_total * PT : ncentres_total;   // what the waves share out: chunks or whole neighbourhoods
-    const int my_units = wave_global < nunits ? (nunits - wave_global + nwaves - 1) / nwaves : 0;
-    const int nits = SPLITP ? my_units : my_units * PT;
-    const int nits_wg = ((nunits + nwaves - 1) / nwaves) * (SPLITP ? 1 : PT);  // uniform over the grid: barrier counts match
-    auto chunk_row0 = [&](int it, int &c) {
-        if constexpr (SPLITP) {
-            const int u = wave_global + it * nwaves;
-            c = u / PT;
-            return (size_t)c * NS + (size_t)(u % PT) * 16;
-        }
-        c = wave_global + (it / PT) * nwaves;
-        return (size_t)c * NS + (size_t)(it % PT) * 16;
-    };
-    auto load_idx = [&](int it) {
-        int c;
-        const size_t r0 = chunk_row0(it, c);
-        return it < nits ? a.idx[r0 + pt] : 0;
-    };
-    auto load_ops = [&](int it, int j, float (&d)[3], f32x4 (&zz)[Q1]) {
-        int c;
-        chunk_row0(it, c);
-        const int cc = it < nits ? c : 0;
-        const int bcl = cc / a.np;
-        const float *xyz = a.xyz + (size_t)bcl * a.n * 3;
-        const float *zb = a.z + (size_t)bcl * a.n * a.zstride + a.zoff;
-        const float *cp = a.new_xyz + (size_t)cc * 3;
-        d[0] = xyz[j * 3 + 0] - cp[0];  // grouped_xyz -= new_xyz (pointnet2_utils.py:253)
-        d[1] = xyz[j * 3 + 1] - cp[1];
-        d[2] = xyz[j * 3 + 2] - cp[2];
-#pragma unroll
-        for (int q = 0; q < Q1; ++q) zz[q] = *reinterpret_cast<const f32x4 *>(zb + (size_t)j * a.zstride + 16 * q + 4 * g);
-    };
+    const rows::Chunks<NS, SPLITP> ch(ncentres_total, NWV, NS == 16 ? (tid >> 6) : __builtin_amdgcn_readfirstlane(tid >> 6));
+    const int nits = ch.nits, nits_wg = ch.nits_all(ncentres_total);  // nits_wg: uniform over the grid, the barrier counts match
     // register budget (256 at two waves per SIMD): the operands of the NEXT chunk are requested into the same registers
     // right after layer 1 has consumed the current ones (the ~40 k cycles of layers 2-3 cover the latency); biases are
     // re-read from LDS where they are used; the running max of a two-chunk neighbourhood is one register per output chunk (`res`).
     int jn;
     float dcur[3];
     f32x4 zcur[Q1];
-    jn = load_idx(0);
-    load_ops(0, jn, dcur, zcur);
-    jn = load_idx(1);
+    jn = ch.load_idx(a, 0, pt);
+    ch.load_ops(a, 0, jn, g, dcur, zcur);
+    jn = ch.load_idx(a, 1, pt);
     int gstep = 0;  // global ring step: slice gstep % Q2 sits in slot gstep % 3
     f32x4 wpre[4];  // first fragment group of the upcoming ring step
     float res[Q3];  // running max of the pre-bias layer-3 output over the chunks of a neighbourhood, per channel 16 n + pt
@@ -860,18 +764,9 @@ __global__ __launch_bounds__(512) void sa_chain_ring_kernel(SAPreArgs a, int nce
         const float dx = dcur[0], dy = dcur[1], dz = dcur[2];
         f32x4 h1[Q1], h2[Q2];
 #pragma unroll
-        for (int q = 0; q < Q1; ++q) {
-            const int g4 = (lo >> 4) * 4;
-            const f32x4 r0 = w1l[16 * q + g4 + 0], r1 = w1l[16 * q + g4 + 1], r2 = w1l[16 * q + g4 + 2], r3 = w1l[16 * q + g4 + 3];
-            f32x4 v = zcur[q];
-            v.x += (r0.x * dx + r0.y * dy + r0.z * dz) + r0.w;
-            v.y += (r1.x * dx + r1.y * dy + r1.z * dz) + r1.w;
-            v.z += (r2.x * dx + r2.y * dy + r2.z * dz) + r2.w;
-            v.w += (r3.x * dx + r3.y * dy + r3.z * dz) + r3.w;
-            h1[q] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        }
-        load_ops(it + 1, jn, dcur, zcur);
-        jn = load_idx(it + 2);
+        for (int q = 0; q < Q1; ++q) h1[q] = rows::layer1(w1l, q, (lo >> 4) * 4, zcur[q], dx, dy, dz);
+        ch.load_ops(a, it + 1, jn, g, dcur, zcur);
+        jn = ch.load_idx(a, it + 2, pt);
         // ---- layer 2 from the resident weights, two output chunks in flight
 #pragma unroll
         for (int n0 = 0; n0 < Q2; n0 += 2) {
@@ -889,10 +784,7 @@ __global__ __launch_bounds__(512) void sa_chain_ring_kernel(SAPreArgs a, int nce
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u)
-                if (n0 + u < Q2) {
-                    f32x4 v = acc[u] + *reinterpret_cast<const f32x4 *>(b2l + 16 * (n0 + u) + 4 * (lo >> 4));
-                    h2[n0 + u] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-                }
+                if (n0 + u < Q2) h2[n0 + u] = relu4(acc[u] + *reinterpret_cast<const f32x4 *>(b2l + 16 * (n0 + u) + 4 * (lo >> 4)));
         }
         // ---- layer 3 through the ring: Q2 steps, all Q3 output chunks accumulate across the steps.
         // Fragment groups are requested one group ahead; the first group of the NEXT step is requested before this step's barrier
@@ -913,6 +805,8 @@ __global__ __launch_bounds__(512) void sa_chain_ring_kernel(SAPreArgs a, int nce
             }
             const f32x4 *slot = ring + (gstep % 3) * SLICE, *nslot = ring + ((gstep + 1) % 3) * SLICE;
 #pragma unroll
+            // (rows::ring_group<true> written out: through the helper the NS = 16 form gets another schedule, 25 instructions longer, and
+            // measured +0.7 % at 640 clouds, outside the parent's spread - profiles/r12_sa_fp32_rows_ab.txt)
             for (int n0 = 0; n0 < Q3; n0 += 4) {
                 f32x4 wf[4], wn[4];
 #pragma unroll
@@ -932,11 +826,8 @@ __global__ __launch_bounds__(512) void sa_chain_ring_kernel(SAPreArgs a, int nce
             __syncthreads();
         }
         {
-            int c;
-            chunk_row0(it, c);
-            float *o = a.out + (size_t)(it < nits ? c : 0) * a.cout_total + a.cout_off;
-            // layer 3 ran transposed: lane = channel 16 n + pt, the 16 rows are the registers x lane groups (points16_max_t);
-            // max_i relu(x_i + b) = relu(max_i x_i + b), so bias and ReLU come once per channel after the pooling
+            float *o = a.out + (size_t)ch.centre_of(it) * a.cout_total + a.cout_off;
+            // layer 3 ran transposed: lane = channel 16 n + pt, the 16 rows are the registers x lane groups (points16_max_t)
 #pragma unroll
             for (int n = 0; n < Q3; ++n) {
                 const float m = points16_max_t(acc3[n]);
@@ -946,6 +837,8 @@ __global__ __launch_bounds__(512) void sa_chain_ring_kernel(SAPreArgs a, int nce
                     const float v = fmaxf(m + b3l[16 * n + (lo & 15)], 0.f);
                     if (g == 0 && it < nits) atomicMax(reinterpret_cast<int *>(o + 16 * n + pt), __float_as_int(v));
                 } else {
+                    // rows::pooled_store_chunks written out: as a second loop behind this one it costs the NS = 32 forms (256 VGPRs) 12 B of
+                    // scratch and two spilled registers (profiles/r12_sa_fp32_rows_resources.txt)
                     res[n] = p == 0 ? m : fmaxf(res[n], m);  // running max over the neighbourhood's chunks: one register per chunk
                     if (p == PT - 1 && g == 0 && it < nits) o[16 * n + pt] = fmaxf(res[n] + b3l[16 * n + (lo & 15)], 0.f);
                 }
@@ -1011,12 +904,7 @@ __global__ __launch_bounds__(512) void sa_groupall_ring_kernel(SAPreArgs a, int 
             if (e < SLOT) ring[slot * SLOT + e] = hold[set][u];
         }
     };
-    for (int e = tid; e < C1; e += NTH) {
-        f32x4 w = *reinterpret_cast<const f32x4 *>(a.wxyz + e * 4);
-        w.w = a.b1[e];
-        w1l[e] = w;
-    }
-    for (int e = tid; e < C2; e += NTH) b2l[e] = a.b2[e];
+    rows::stage_operands<C1, C2, 0, NTH>(a, w1l, b2l, nullptr, tid);  // (the layer-3 bias: one register per thread)
     const float bias3 = a.b3[tid];
     request(0, 0);
     deposit(0, 0);
@@ -1054,15 +942,7 @@ __global__ __launch_bounds__(512) void sa_groupall_ring_kernel(SAPreArgs a, int 
         zq[0] = *reinterpret_cast<const f32x4 *>(zb);
         zq[1] = *reinterpret_cast<const f32x4 *>(zb + 16);
         zq[2] = *reinterpret_cast<const f32x4 *>(zb + 32);
-        auto layer1 = [&](int q) {
-            const f32x4 r0 = w1l[16 * q + 4 * g + 0], r1 = w1l[16 * q + 4 * g + 1], r2 = w1l[16 * q + 4 * g + 2], r3 = w1l[16 * q + 4 * g + 3];
-            f32x4 v = zq[q % 4];
-            v.x += (r0.x * dx + r0.y * dy + r0.z * dz) + r0.w;
-            v.y += (r1.x * dx + r1.y * dy + r1.z * dz) + r1.w;
-            v.z += (r2.x * dx + r2.y * dy + r2.z * dz) + r2.w;
-            v.w += (r3.x * dx + r3.y * dy + r3.z * dz) + r3.w;
-            return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        };
+        auto layer1 = [&](int q) { return rows::layer1(w1l, q, 4 * g, zq[q % 4], dx, dy, dz); };
         f32x4 h1q = layer1(0);  // k-block q + 1 is prepared while k-block q is multiplied
         // ---- layer 2: Q1 ring steps, all Q2 output chunks accumulate across them
         f32x4 h2[Q2];
@@ -1076,17 +956,7 @@ __global__ __launch_bounds__(512) void sa_groupall_ring_kernel(SAPreArgs a, int 
             const f32x4 *slot = ring + (gstep % NRS) * SLOT, *nslot = ring + ((gstep + 1) % NRS) * SLOT;
 #pragma unroll
             for (int n0 = 0; n0 < Q2; n0 += 4) {
-                f32x4 wf[4], wn[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) wf[u] = wpre[u];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) wn[u] = (n0 + 4 < Q2) ? slot[(n0 + 4 + u) * 64 + lane] : nslot[u * 64 + lane];
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) h2[n0 + u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[u][jj], h1q[jj], h2[n0 + u], 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) wpre[u] = wn[u];
+                rows::ring_group<false>(wpre, n0 + 4 < Q2 ? slot + (n0 + 4) * 64 : nslot, lane, h1q, 4, h2 + n0);
                 __builtin_amdgcn_sched_barrier(0);  // one fragment group ahead, not the whole slice (its reads would take 64-96 registers)
             }
             h1q = h1n;
@@ -1094,10 +964,7 @@ __global__ __launch_bounds__(512) void sa_groupall_ring_kernel(SAPreArgs a, int 
             __syncthreads();
         }
 #pragma unroll
-        for (int n = 0; n < Q2; ++n) {
-            const f32x4 v = h2[n] + *reinterpret_cast<const f32x4 *>(b2l + 16 * n + 4 * g);
-            h2[n] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        }
+        for (int n = 0; n < Q2; ++n) h2[n] = relu4(h2[n] + *reinterpret_cast<const f32x4 *>(b2l + 16 * n + 4 * g));
         // ---- layer 3, transposed (lane = channel 16 n + pt, registers x lane groups = the wave's 16 rows), 16 output chunks at a time
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {
@@ -1110,17 +977,7 @@ __global__ __launch_bounds__(512) void sa_groupall_ring_kernel(SAPreArgs a, int 
                 const f32x4 *slot = ring + (gstep % NRS) * SLOT, *nslot = ring + ((gstep + 1) % NRS) * SLOT;
 #pragma unroll
                 for (int n0 = 0; n0 < 16; n0 += 4) {
-                    f32x4 wf[4], wn[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) wf[u] = wpre[u];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) wn[u] = (n0 + 4 < 16) ? slot[(n0 + 4 + u) * 64 + lane] : nslot[u * 64 + lane];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) acc3[n0 + u] = __builtin_amdgcn_mfma_f32_16x16x4f32(h2[q][jj], wf[u][jj], acc3[n0 + u], 0, 0, 0);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) wpre[u] = wn[u];
+                    rows::ring_group<true>(wpre, n0 + 4 < 16 ? slot + (n0 + 4) * 64 : nslot, lane, h2[q], 4, acc3 + n0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 ++gstep;
@@ -1152,8 +1009,7 @@ int launch_groupall_ring(const SAPreArgs &a, int b, hipStream_t st) {
     auto kern = sa_groupall_ring_kernel<C1, C2, C3>;
     static bool done = false;
     if (!done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(kern, lds)) return GP_ELAUNCH;
         done = true;
     }
     hipLaunchKernelGGL(kern, dim3(b < gp_num_cus() ? b : gp_num_cus()), dim3(512), lds, st, a, b);
@@ -1168,8 +1024,7 @@ int launch_chain_ring(const SAPreArgs &a, int b, hipStream_t st) {
     auto kern = sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD>;
     static bool done = false;
     if (!done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(kern, lds)) return GP_ELAUNCH;
         done = true;
     }
     const int ncentres = b * a.np;
@@ -1181,8 +1036,7 @@ int launch_chain_ring(const SAPreArgs &a, int b, hipStream_t st) {
             auto kern_s = sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD, true>;
             static bool done_s = false;
             if (!done_s) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_s), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                    return GP_ELAUNCH;
+                if (set_lds(kern_s, lds)) return GP_ELAUNCH;
                 done_s = true;
             }
             // (a KERNEL, not hipMemset2DAsync: as a memset node of a graph captured on a side stream - the tracking runner's energy-model
@@ -1208,34 +1062,14 @@ int launch_chain(const SAPreArgs &a, int b, hipStream_t st) {
     return gp_launch_status();
 }
 
-template <int P>
-int launch(const SAArgs &a, int b, hipStream_t st) {
-    const int K0p = gp_round16(a.cin + 3), c1p = gp_round16(a.c1), c2p = gp_round16(a.c2);
-    const int lda = (K0p > c2p ? K0p : c2p) + GP_LD_PAD, ldb = c1p + GP_LD_PAD;
-    const size_t lds = (size_t)P * (lda + ldb) * sizeof(float);
-    if (lds > 160 * 1024) return GP_EINVAL;
-    auto kern = sa_mlp_kernel<P>;
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
-    }
-    const int nrows = a.groupall ? a.n : a.np * a.ns;
-    const int tiles = (nrows + P - 1) / P;
-    // The GroupAll level of a SMALL batch (a tracking frame: 5 clouds = 20 tiles; one cloud: 4): every tile streams all of both weight
-    // matrices (0.77 / 1.15 MB) through one CU while the others idle - 48 us per launch whatever the batch.  While the chip has CUs to spare,
-    // 2 or 4 workgroups share a row tile: each recomputes layers 1-2 (a third of the work) and takes a half / quarter of layer 3's channels.
-    int split = 1;
-    if (a.groupall) {
-        const int ncu = gp_num_cus();
-        split = tiles * b * 4 <= ncu ? 4 : (tiles * b * 2 <= ncu ? 2 : 1);
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles, b, split), dim3(256), lds, st, a);
-    return gp_launch_status();
-}
-
 size_t lds_bytes(int P, const SAArgs &a) {
     const int K0p = gp_round16(a.cin + 3), c1p = gp_round16(a.c1), c2p = gp_round16(a.c2);
     return (size_t)P * ((K0p > c2p ? K0p : c2p) + c1p + 2 * GP_LD_PAD) * sizeof(float);
+}
+
+template <int P>
+int launch(const SAArgs &a, int b, hipStream_t st) {
+    return launch_tiles<P>(sa_mlp_kernel<P>, a, lds_bytes(P, a), b, st);
 }
 
 }  // namespace
@@ -1282,9 +1116,7 @@ int gp_point_linear(int rows, int k_in, int n_out, const float *x, const float *
     if (lds > 64 * 1024) {
         static bool done = false;
         if (!done) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(point_linear_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess)
-                return GP_ELAUNCH;
+            if (set_lds(point_linear_kernel, 160 * 1024)) return GP_ELAUNCH;
             done = true;
         }
     }

@@ -42,9 +42,7 @@ extern "C" int gp_score_div(int nclouds, int k, const gp_scorenet *net, const fl
     const size_t lds = LDS_BYTES;
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(score_div_kernel<SCORE_DIV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(score_div_kernel<ENERGY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(score_div_kernel<SCORE_DIV>, lds) || set_lds(score_div_kernel<ENERGY>, lds)) return GP_ELAUNCH;
         attr_done = true;
     }
     hipLaunchKernelGGL(score_div_kernel<SCORE_DIV>, dim3((R + DP - 1) / DP), dim3(DNT), lds, (hipStream_t)s, R, k, *net, cvec, tvec, x, eps, sigma_dev, score, div);
@@ -60,8 +58,7 @@ extern "C" int gp_energy_score(int nclouds, int k, const gp_scorenet *net, const
     const size_t lds = LDS_BYTES;
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(score_div_kernel<ENERGY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(score_div_kernel<ENERGY>, lds)) return GP_ELAUNCH;
         attr_done = true;
     }
     hipLaunchKernelGGL(score_div_kernel<ENERGY>, dim3((R + DP - 1) / DP), dim3(DNT), lds, (hipStream_t)s, R, k, *net, cvec, tvec, x, x, sigma_dev, score, energy);

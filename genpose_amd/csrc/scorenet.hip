@@ -471,8 +471,7 @@ int gp_cloud_embed(int b, const gp_scorenet *net, const float *pts_feat, float *
     auto kern = cloud_embed_kernel;
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return GP_ELAUNCH;
+        if (set_lds(kern, lds)) return GP_ELAUNCH;
         attr_done = true;
     }
     hipLaunchKernelGGL(kern, dim3((b + 15) / 16, 3), dim3(256), lds, (hipStream_t)s, b, *net, pts_feat, cvec);
