@@ -36,6 +36,7 @@ SIGNATURES = {
     "gp_three_nn_arith": [c_int, c_int, c_int, c_int, P, P, P, P, P],
     "gp_three_interpolate_arith": [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P],
     "gp_fps_chain_arith": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), P, P, P, P, P, P, P, P],
+    "gp_ball_query_msg_fits": [c_int, c_int, c_int],
     "gp_ball_query_msg_arith": [c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_int, P, P, P, P, P],
     "gp_gather_points": [c_int, c_int, c_int, c_int, P, P, P, P],
     "gp_gather_points_grad": [c_int, c_int, c_int, c_int, P, P, P, P],

@@ -697,10 +697,16 @@ int gp_ball_query(int b, int n, int m, float radius, int nsample, const float *n
     return gp_ball_query_arith(GP_ARITH_DEFAULT, b, n, m, radius, nsample, new_xyz, xyz, idx, s);
 }
 
+// the fused two-scale kernel keeps the whole cloud and both staging rows in LDS: the one place that says which (n, nsample0, nsample1) it
+// takes (12 n + 16 (nsample0 + nsample1 + 2) bytes <= 60 KiB: n <= 5053 at 16 + 32 samples).  No device needed.
+int gp_ball_query_msg_fits(int n, int nsample0, int nsample1) {
+    return n > 0 && nsample0 > 0 && nsample1 > 0 && bq_lds_bytes(n, nsample0, nsample1) <= 60 * 1024;
+}
+
 int gp_ball_query_msg_arith(int arith, int b, int n, int m, float radius0, int nsample0, float radius1, int nsample1, const float *new_xyz,
                             const float *xyz, int32_t *idx0, int32_t *idx1, gp_stream_t s) {
     if (!arith_ok(arith) || b < 0 || n <= 0 || m < 0 || nsample0 <= 0 || nsample1 <= 0 || !new_xyz || !xyz || !idx0 || !idx1) return GP_EINVAL;
-    if (bq_lds_bytes(n, nsample0, nsample1) > 60 * 1024) return GP_EINVAL;
+    if (!gp_ball_query_msg_fits(n, nsample0, nsample1)) return GP_EINVAL;
     if (b == 0 || m == 0) return GP_OK;
     dim3 grid((m + (BQ_T / 64) * BQ_CPW - 1) / ((BQ_T / 64) * BQ_CPW), b);
     GP_ARITH_SWITCH(arith, {

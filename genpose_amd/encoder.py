@@ -10,6 +10,18 @@ forward(pts [B,N,3] f32 on the GPU) -> [B,1024].  Launch sequence per call (all 
   1 + 2 x the same pair  GroupAll level: whole rounds of 256 clouds on the ring kernel (one cloud per workgroup), the rest on 32-row tiles
                         (the tiles of a cloud combine by integer atomic max into a zeroed buffer)
 Intermediate features stay point-major [B, n, C]; the reference's grouped [B,C+3,np,ns] tensors never exist.
+
+Points per cloud.  Any N >= the first level's npoint (512 in every shipped configuration) is served; fewer points than level 0 selects
+raise GenposeHipError (the reference would read past the cloud).  Only the grouping front end depends on N:
+  centres   N <= 1024 and at most three grouping levels: gp_fps_chain (one wave per cloud; a level of exactly 64 * 2^k points takes the
+            form without bounds checks).  N > 1024, or four grouping levels ('lighter'): one gp_furthest_point_sampling + torch.gather
+            per level - n <= 1024 on one wave, <= 2048 / <= 4096 on four waves with 8 / 16 register-resident points per thread, beyond
+            that the running minima in global memory.  prepare_grouping(defer_join=True) splits the levels over two streams only in
+            the gp_fps_chain range; elsewhere it is the plain sequence on the calling stream.
+  balls     a two-scale level: gp_ball_query_msg while the source cloud fits its LDS (gp_ball_query_msg_fits: n <= 5053 at 16 + 32
+            samples, n <= 4989 at 32 + 64), else gp_ball_query once per scale into zeroed rows - the cloud in LDS while 12 n + 16 (nsample
+            + 1) bytes fit 60 KiB, candidates from global memory beyond.  A single-scale level always takes the per-scale form.
+Levels 1.. see at most 512 source points, so they never leave the small-cloud kernels.  encode() captures whichever sequence applies.
 """
 import ctypes
 import itertools
@@ -172,7 +184,9 @@ class Pointnet2EncoderHIP:
                 xyz, n = new_xyz, npnt
                 continue
             radii, nss = cfg["radii"][k], cfg["nsamples"][k]
-            if len(self.w.levels[k]) == 2:
+            # two scales in one pass while the cloud fits the fused kernel's LDS (n <= 5053 at 16 + 32 samples: the C side owns the limit);
+            # a larger cloud, like a level of one or three scales: one query per scale into zeroed rows, which takes any n
+            if len(self.w.levels[k]) == 2 and _lib.lib().gp_ball_query_msg_fits(n, nss[0], nss[1]):
                 _lib.call("gp_ball_query_msg_arith", self.arith, B, n, npnt, float(radii[0]), nss[0], float(radii[1]), nss[1], ptr(new_xyz), ptr(xyz),
                           ptr(ws["bq"][k][0]), ptr(ws["bq"][k][1]), st)
             else:

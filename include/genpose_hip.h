@@ -117,13 +117,21 @@ int gp_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out,
 
 /* FPS + gather for up to 3 consecutive set-abstraction levels in one launch (one workgroup per cloud).
  * xyz [b,n0,3]; level l selects m[l] points out of the previous level's selection.
- * idx_l [b,m_l] i32 (indices into the previous level's point list), new_xyz_l [b,m_l,3].  Unused levels: m = 0. */
+ * idx_l [b,m_l] i32 (indices into the previous level's point list), new_xyz_l [b,m_l,3].  Unused levels: m = 0.
+ * Limits: 1 <= n0 <= 1024 (one wave holds a level in registers), 1 <= nlevels <= 3, 1 <= m[0] <= n0 and 1 <= m[l] <= m[l-1], and a
+ * non-null idx_l / new_xyz_l for every level l < nlevels (those of the unused levels are not read: NULL).  Anything else returns
+ * GP_EINVAL before any launch: no output is written.  Larger clouds: one gp_furthest_point_sampling per level. */
 int gp_fps_chain(int b, int n0, int nlevels, const int *m, const float *xyz, int32_t *idx0, float *new_xyz0,
                  int32_t *idx1, float *new_xyz1, int32_t *idx2, float *new_xyz2, gp_stream_t s);
 int gp_fps_chain_arith(int arith, int b, int n0, int nlevels, const int *m, const float *xyz, int32_t *idx0, float *new_xyz0,
                        int32_t *idx1, float *new_xyz1, int32_t *idx2, float *new_xyz2, gp_stream_t s);
 
-/* Ball query for the two scales of one MSG level in a single pass; rows with no hit are zero-filled. */
+/* Ball query for the two scales of one MSG level in a single pass; rows with no hit are zero-filled (the caller need not zero idx0 /
+ * idx1 beforehand).  The workgroup keeps the cloud and its staging rows in LDS, 12 n + 16 (nsample0 + nsample1 + 2) bytes, and the
+ * entry takes what fits 60 KiB: n <= 5053 at 16 + 32 samples.  gp_ball_query_msg_fits says so (1 / 0; host only, no device needed); for
+ * a shape that does not fit, gp_ball_query_msg[_arith] returns GP_EINVAL before any launch and writes nothing - the caller runs
+ * gp_ball_query once per scale on zeroed buffers instead (any n). */
+int gp_ball_query_msg_fits(int n, int nsample0, int nsample1);
 int gp_ball_query_msg(int b, int n, int m, float radius0, int nsample0, float radius1, int nsample1, const float *new_xyz,
                       const float *xyz, int32_t *idx0, int32_t *idx1, gp_stream_t s);
 int gp_ball_query_msg_arith(int arith, int b, int n, int m, float radius0, int nsample0, float radius1, int nsample1, const float *new_xyz,

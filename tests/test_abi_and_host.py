@@ -61,6 +61,27 @@ def test_arithmetic_convention_defaults_agree():
     assert _lib.lib().gp_ball_query_msg_arith(-1, 1, 8, 2, 0.1, 4, 0.2, 4, None, None, None, None, None) == -1
 
 
+def test_ball_query_msg_fits_is_declared_bound_and_owns_the_limit():
+    """gp_ball_query_msg_fits (host only: no device): the header's arity in _lib.SIGNATURES, and the limit the header documents -
+    12 n + 16 (nsample0 + nsample1 + 2) bytes within 60 KiB - at its edge for the encoder's neighbourhood sizes.  The fused entry
+    refuses exactly what it says does not fit (before it looks at the device)."""
+    from genpose_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "genpose_hip.h")).read(), flags=re.S)
+    args = re.search(r"\bint\s+gp_ball_query_msg_fits\s*\(([^)]*)\)\s*;", hdr).group(1).split(",")
+    assert len(args) == 3 and all(a.split()[0] == "int" and "*" not in a for a in args)
+    assert _lib.SIGNATURES["gp_ball_query_msg_fits"] == [ctypes.c_int] * 3
+    fits = _lib.lib().gp_ball_query_msg_fits
+    for ns0, ns1 in [(16, 32), (32, 64), (8, 16), (5, 70)]:
+        edge = (60 * 1024 - 16 * (ns0 + ns1 + 2)) // 12
+        assert fits(edge, ns0, ns1) == 1 and fits(edge + 1, ns0, ns1) == 0, (ns0, ns1, edge)
+    assert fits(5053, 16, 32) == 1 and fits(5054, 16, 32) == 0
+    assert fits(1, 1, 1) == 1 and fits(0, 16, 32) == 0 and fits(1024, 0, 32) == 0 and fits(1024, 16, -1) == 0
+    assert fits(2**31 - 1, 16, 32) == 0  # sized in size_t: no wrap-around into "fits"
+    one = ctypes.c_void_p(16)  # (never dereferenced: the entry returns before any launch)
+    assert _lib.lib().gp_ball_query_msg_arith(1, 1, 5054, 2, 0.1, 16, 0.2, 32, one, one, one, one, None) == -1
+    assert _lib.lib().gp_ball_query_msg(1, 5054, 2, 0.1, 16, 0.2, 32, one, one, one, one, None) == -1
+
+
 def test_pointnet2_cuda_surface_matches_reference_names():
     """The nine pybind names of pointnet2_api.cpp:10-24."""
     import genpose_amd.pointnet2_cuda as m
