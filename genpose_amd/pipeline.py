@@ -42,6 +42,7 @@ class PipelinedPCPredictor:
         32-row tiles (MFMA-bound) instead of 16-row tiles (weight-stream-bound): 21 vs 26 us per batch and step."""
         _lib.check_device()
         self.net = score_agent.net
+        self.net.pointnet2_encoder(type(self).__name__)  # refuses an agent whose features are not the PointNet++ encoder's alone
         self.net._need_weights()
         self.G = batches_per_launch
         self.B1 = B                      # clouds per batch (the unit of the batch-global coupling)
@@ -200,6 +201,7 @@ class GroupedODEPredictor:
         from .samplers import ODESampler
         _lib.check_device()
         self.net = score_agent.net
+        self.net.pointnet2_encoder(type(self).__name__)  # refuses an agent whose features are not the PointNet++ encoder's alone
         self.net._need_weights()
         self.B1, self.K, self.G = B, K, batches_per_launch
         self.T0 = self.net.T if T0 is None else T0
@@ -268,6 +270,8 @@ class FullPipelinePredictor:
         of the CUs (the second round 56 % full); five batches are 2000 tiles = 7.8 rounds."""
         _lib.check_device()
         self.snet, self.enet = score_agent.net, energy_agent.net
+        for net in (self.snet, self.enet):
+            net.pointnet2_encoder(type(self).__name__)  # refuses an agent whose features are not the PointNet++ encoder's alone
         self.snet._need_weights()
         self.enet._need_weights()
         if self.enet.cfg.posenet_mode != "energy" or self.snet.cfg.posenet_mode != "score":

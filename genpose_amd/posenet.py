@@ -15,6 +15,7 @@ import torch
 from .config import encoder_precision_of
 from .encoder import Pointnet2EncoderHIP
 from .lru import ShapeCache
+from .pointnet_encoder import ACT_RELU, PointNetEncoderHIP, dense_rows
 from .samplers import ODESampler, PCSampler
 from .scorenet import ScoreNetHIP
 from .sde import SIGMA_MAX, SIGMA_MIN
@@ -29,8 +30,11 @@ class GFObjectPose:
         self.device = torch.device(cfg.device)
         self.prior_fn, self.marginal_prob_fn, self.sde_fn = prior_fn, marginal_prob_fn, sde_fn
         self.sampling_eps, self.T = sampling_eps, T
-        if cfg.pts_encoder != "pointnet2":
-            raise NotImplementedError(f"pts_encoder '{cfg.pts_encoder}': only the default PointNet++ encoder is on the MI355X hot path")
+        if cfg.pts_encoder == "pointnet":
+            raise NotImplementedError("pts_encoder 'pointnet': the encoder exists as genpose_amd.pointnet_encoder.PointNetEncoderHIP, but this agent value "
+                                      "is not wired yet (use 'pointnet2' or 'pointnet_and_pointnet2')")
+        if cfg.pts_encoder not in ("pointnet2", "pointnet_and_pointnet2"):
+            raise NotImplementedError(f"pts_encoder '{cfg.pts_encoder}': 'pointnet2' (default) or 'pointnet_and_pointnet2'")
         if getattr(cfg, "regression_head", "Rx_Ry_and_T") != "Rx_Ry_and_T" or getattr(cfg, "pose_mode", "rot_matrix") != "rot_matrix":
             raise NotImplementedError("only regression_head='Rx_Ry_and_T' with pose_mode='rot_matrix' is implemented")
         if cfg.posenet_mode not in ("score", "energy"):
@@ -40,6 +44,8 @@ class GFObjectPose:
                 if getattr(cfg, k, v) != v:
                     raise NotImplementedError(f"{k}='{getattr(cfg, k)}' (only the shipped default '{v}')")
         self.pts_encoder = None
+        # cfg.pts_encoder == 'pointnet_and_pointnet2' (posenet.py:40-44): the reference's attribute names; pts_encoder stays None
+        self.pts_pointnet_encoder = self.pts_pointnet2_encoder = self.fusion_layer = None
         self.pose_score_net = None
         # samplers (captured launch chains + noise / solver-state buffers) and pinned staging buffers per batch geometry: bounded,
         # least recently used first (lru.py) - a ragged tail per category / a new object count per image must not accumulate
@@ -51,7 +57,16 @@ class GFObjectPose:
     def load_state_dict(self, state_dict, strict=True):
         sd = {k[7:] if k.startswith("module.") else k: v for k, v in state_dict.items()}
         params = getattr(self.cfg, "pointnet2_params", "light")
-        self.pts_encoder = Pointnet2EncoderHIP(sd, self.device, params, arith=getattr(self.cfg, "dist_arith", None), precision=encoder_precision_of(self.cfg))
+        if self.cfg.pts_encoder == "pointnet_and_pointnet2":
+            self.pts_pointnet2_encoder = Pointnet2EncoderHIP(sd, self.device, params, prefix="pts_pointnet2_encoder.", arith=getattr(self.cfg, "dist_arith", None),
+                                                             precision=encoder_precision_of(self.cfg))
+            self.pts_pointnet_encoder = PointNetEncoderHIP(sd, self.device, prefix="pts_pointnet_encoder.")
+            W, b = sd["fusion_layer.weight"].detach().float().cpu().contiguous(), sd["fusion_layer.bias"].detach().float().cpu().contiguous()
+            if tuple(W.shape) != (1024, 2048) or b.numel() != 1024:
+                raise ValueError(f"fusion_layer.weight is {tuple(W.shape)}, expected (1024, 2048)")
+            self.fusion_layer = (W.to(self.device), b.to(self.device))
+        else:
+            self.pts_encoder = Pointnet2EncoderHIP(sd, self.device, params, arith=getattr(self.cfg, "dist_arith", None), precision=encoder_precision_of(self.cfg))
         self.pose_score_net = ScoreNetHIP(sd, self.device)
         self._samplers.clear()
         return self
@@ -67,13 +82,31 @@ class GFObjectPose:
         if self.pose_score_net is None:
             raise RuntimeError("GFObjectPose has no weights: call load_state_dict()/PoseNet.load_ckpt() first")
 
+    def pointnet2_encoder(self, who):
+        """The PointNet++ encoder for code that drives its stages itself (request batching, frame graphs, shared grouping across two
+        agents): such code would silently drop the PointNet half of a fused agent, so it is refused there."""
+        if self.fusion_layer is not None or self.cfg.pts_encoder != "pointnet2":
+            raise NotImplementedError(f"{who} drives the PointNet++ encoder's stages directly and does not serve pts_encoder='{self.cfg.pts_encoder}': "
+                                      "use the agent's pred_func / get_energy")
+        return self.pts_encoder
+
     # ------------------------------------------------------------------ pieces
     def extract_pts_feature(self, data, use_graph=True):
         """posenet.py:71-91.  The sampled centres and ball-query neighbourhoods depend on the coordinates only, so the SCORE agent
         leaves a ticket for them in the dict (`_grouping`) and the ENERGY agent, called next with the same dict and the same clouds
         (evaluation_single.py:339-343, evaluation_tracking.py:316-321), takes them over instead of recomputing them."""
         self._need_weights()
-        enc, pts = self.pts_encoder, data["pts"]
+        if self.fusion_layer is not None:
+            # posenet.py:85-88: relu(fusion_layer(cat(pointnet_feat, pointnet2_feat))) - PointNet first; the concatenation is never built
+            # (gp_dense_rows takes the two halves).  The PointNet++ half keeps the grouping ticket: centres and neighbourhoods depend on
+            # the coordinates only, whatever else the agent encodes.
+            f2 = self._pointnet2_feature(self.pts_pointnet2_encoder, data, use_graph)
+            f1 = self.pts_pointnet_encoder.encode(data["pts"], use_graph=use_graph)
+            return dense_rows(f1, self.fusion_layer[0], self.fusion_layer[1], ACT_RELU, xb=f2)
+        return self._pointnet2_feature(self.pts_encoder, data, use_graph)
+
+    def _pointnet2_feature(self, enc, data, use_graph):
+        pts = data["pts"]
         if self.cfg.posenet_mode == "energy" and enc.ticket_valid(data.get("_grouping"), pts, enc.grouping_key()):
             return enc.encode(pts, grouping=data["_grouping"]["ws"], use_graph=use_graph and data["_grouping"].get("use_graph", True))
         feat, ws = enc.encode(pts, use_graph=use_graph)  # one hipGraph replay per input shape from the second call on (encoder.py)

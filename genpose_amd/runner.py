@@ -140,6 +140,8 @@ class _FrameGraphs:
     def __init__(self, snet, enet, K, sel, T_energy=1e-5):
         from .sde import SIGMA_MAX, SIGMA_MIN
         self.snet, self.enet, self.K, self.sel = snet, enet, K, sel
+        for net in (snet, enet):
+            net.pointnet2_encoder("the frame-graph runner")  # refuses an agent whose features are not the PointNet++ encoder's alone
         dev = snet.device
         t = torch.full((1,), float(T_energy), device=dev)
         self.tvec_e = enet.pose_score_net.time_embed(t)[0].contiguous()
@@ -241,6 +243,9 @@ class TrackingRunner:
         self.repeat_num, self.T0, self.ratio = repeat_num, T0, ratio
         self.buffer = {"model_name": [], "pred_sRT": None}
         self.use_graphs = use_graphs
+        if use_graphs:  # the frame graphs drive the PointNet++ encoder's stages themselves: refused here, not at the first frame
+            for a in (score_agent, energy_agent):
+                a.net.pointnet2_encoder("TrackingRunner(use_graphs=True)")
         self._graphs = None
 
     def reset(self):

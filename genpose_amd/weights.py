@@ -3,7 +3,8 @@
 Accepts exactly the reference's `model_state_dict` key schema (posenet_agent.py:143-173):
   pts_encoder.SA_modules.{k}.mlps.{i}.layer{l}.conv.weight [Cout,Cin,1,1], ....bn.bn.{weight,bias,running_mean,running_var}
   pose_score_net.{pose_encoder.{0,2}, t_encoder.0.W, t_encoder.1, fusion_tail_{rot_x,rot_y,trans}.{0,2}}.{weight,bias}
-so a real `ckpt_genpose.pth` drops in.  Host-side work here is layout only: BatchNorm (eval) folding into the
+so a real `ckpt_genpose.pth` drops in; for cfg.pts_encoder = 'pointnet_and_pointnet2' (posenet.py:40-44) the same PointNet++ keys under
+`pts_pointnet2_encoder.`, PointNetfeat's under `pts_pointnet_encoder.` (PointNetWeights) and `fusion_layer.{weight,bias}`.  Host-side work here is layout only: BatchNorm (eval) folding into the
 1x1 conv, input-channel permutation [dx,dy,dz,feat] -> [feat,dx,dy,dz], and the MFMA
 fragment packing of gp_pack_weight (include/genpose_hip.h).
 """
@@ -233,6 +234,33 @@ class EncoderWeights:
             self.z_weights.append(pack_weight(torch.cat([sc.w1_feat for sc in scales], dim=0)).to(device) if cin > 0 else None)
             cin = sum(s.couts[-1] for s in scales)
         self.out_dim = cin
+
+
+class PointNetWeights:
+    """Device blocks of the vanilla PointNet encoder, PointNetfeat(num_points, out_dim=1024) (networks/pts_encoder/pointnets.py:83-123), from the
+    reference's keys {prefix}stn.conv{1,2,3}, {prefix}stn.fc{1,2,3}, {prefix}conv{1..4} (.weight / .bias; Conv1d weights [Cout, Cin, 1]).
+    Host-side work is layout only: the convolutions in the MFMA fragment order of gp_pack_weight, the fully connected layers of the transform
+    net's head as trained ([out, in] row-major, gp_dense_rows), and the `+ iden` of STNkd.forward (pointnets.py:70-77) folded into fc3's bias."""
+    STN_CONVS = ((3, 64), (64, 128), (128, 1024))
+    STN_FCS = ((1024, 512), (512, 256), (256, 9))
+    CONVS = ((3, 64), (64, 128), (128, 512), (512, 1024))
+
+    def __init__(self, sd, device, prefix="pts_encoder."):
+        def conv(name, cin, cout):
+            W = sd[f"{prefix}{name}.weight"].detach().float().cpu()
+            W = W.reshape(W.shape[0], -1)
+            b = sd[f"{prefix}{name}.bias"].detach().float().cpu()
+            if tuple(W.shape) != (cout, cin) or b.numel() != cout:
+                raise ValueError(f"{prefix}{name}.weight is {tuple(W.shape)}, expected {(cout, cin)} (PointNetfeat with in_dim=3, out_dim=1024)")
+            return W, b
+
+        self.stn_convs = [(pack_weight(W).to(device), pad_bias(b).to(device)) for W, b in (conv(f"stn.conv{i + 1}", *s) for i, s in enumerate(self.STN_CONVS))]
+        fcs = [conv(f"stn.fc{i + 1}", *s) for i, s in enumerate(self.STN_FCS)]
+        W3, b3 = fcs[2]
+        fcs[2] = (W3, b3 + torch.eye(3).reshape(9))
+        self.stn_fcs = [(W.contiguous().to(device), b.contiguous().to(device)) for W, b in fcs]
+        self.convs = [(pack_weight(W).to(device), pad_bias(b).to(device)) for W, b in (conv(f"conv{i + 1}", *s) for i, s in enumerate(self.CONVS))]
+        self.out_dim = self.CONVS[-1][1]
 
 
 class ScoreNetWeights:

@@ -25,10 +25,13 @@ def mlp_specs(mlps=LIGHT_MLPS, input_channels=0):
     return out
 
 
-def make_state_dict(seed=0, mode="score", params="light"):
+def make_state_dict(seed=0, mode="score", params="light", pts_encoder="pointnet2"):
     """Random weights with the reference's shapes and key names; output layers (zero-initialised by the
     reference, scorenet.py:156-170) re-drawn N(0,0.05), BN statistics randomised so BN folding is exercised.
-    params: the encoder configuration (--pointnet2_params: 'light' | 'dense' | 'lighter', pointnet2.py:47-78)."""
+    params: the encoder configuration (--pointnet2_params: 'light' | 'dense' | 'lighter', pointnet2.py:47-78).
+    pts_encoder (--pts_encoder, networks/posenet.py:36-46): 'pointnet' puts PointNetfeat's keys under `pts_encoder.` in place of the
+    PointNet++ ones; 'pointnet_and_pointnet2' the reference's fused layout - PointNet++ under
+    `pts_pointnet2_encoder.`, PointNetfeat under `pts_pointnet_encoder.`, and `fusion_layer.{weight,bias}` [1024, 2048]."""
     g = torch.Generator().manual_seed(seed + (0 if mode == "score" else 7919))
     sd = {}
 
@@ -64,4 +67,34 @@ def make_state_dict(seed=0, mode="score", params="light"):
     for h in ("rot_x", "rot_y", "trans"):
         lin(f"fusion_tail_{h}.0", 1408, 256)
         lin(f"fusion_tail_{h}.2", 256, 3, std=0.05)
+    if pts_encoder == "pointnet2":
+        return sd
+    if pts_encoder not in ("pointnet", "pointnet_and_pointnet2"):
+        raise ValueError(f"pts_encoder {pts_encoder!r}: 'pointnet2', 'pointnet' or 'pointnet_and_pointnet2'")
+    # the extra tensors come from a SECOND generator, after every draw above: the default call returns the bytes it always returned
+    g2 = torch.Generator().manual_seed(104729 + seed + (0 if mode == "score" else 7919))
+
+    def rn2(*shape, std=1.0):
+        return torch.randn(*shape, generator=g2) * std
+
+    fused = pts_encoder == "pointnet_and_pointnet2"
+    if fused:  # networks/posenet.py:40-43: the PointNet++ encoder under its second name
+        sd = {("pts_pointnet2_encoder." + k[len("pts_encoder."):] if k.startswith("pts_encoder.") else k): v for k, v in sd.items()}
+    else:  # PointNetfeat alone owns `pts_encoder.`
+        sd = {k: v for k, v in sd.items() if not k.startswith("pts_encoder.")}
+    p = "pts_pointnet_encoder." if fused else "pts_encoder."
+    # PointNetfeat (networks/pts_encoder/pointnets.py:45-56, 83-94): non-zero biases throughout
+    for name, cin, cout in (("stn.conv1", 3, 64), ("stn.conv2", 64, 128), ("stn.conv3", 128, 1024), ("conv1", 3, 64), ("conv2", 64, 128),
+                            ("conv3", 128, 512), ("conv4", 512, 1024)):
+        sd[p + name + ".weight"] = rn2(cout, cin, 1, std=math.sqrt(2.0 / cin))
+        sd[p + name + ".bias"] = 0.1 * rn2(cout)
+    for name, cin, cout in (("stn.fc1", 1024, 512), ("stn.fc2", 512, 256)):
+        sd[p + name + ".weight"] = rn2(cout, cin, std=math.sqrt(2.0 / cin))
+        sd[p + name + ".bias"] = 0.1 * rn2(cout)
+    # fc3 wide enough that trans is visibly NOT the identity (entries of order 0.3): an almost-identity transform hides a transposed bmm
+    sd[p + "stn.fc3.weight"] = rn2(9, 256, std=0.02)
+    sd[p + "stn.fc3.bias"] = 0.3 * rn2(9)
+    if fused:
+        sd["fusion_layer.weight"] = rn2(1024, 2048, std=math.sqrt(2.0 / 2048))
+        sd["fusion_layer.bias"] = 0.1 * rn2(1024)
     return sd

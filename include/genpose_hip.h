@@ -195,6 +195,35 @@ int gp_sa_pre_mlp_max_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c
                              const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w23_x9, const float *bias2,
                              const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s);
 
+/* Vanilla PointNet encoder, PointNetfeat(num_points, out_dim=1024) without BatchNorm (networks/pts_encoder/pointnets.py:83-123; the agent's
+ * cfg.pts_encoder = 'pointnet' | 'pointnet_and_pointnet2', networks/posenet.py:36-46, 79-90).  csrc/pointnet.hip: per-point MLP chains on
+ * fp32 MFMA over 48-point tiles, bias after the product, ReLU where the reference has it; the [b, n, 1024] and [b, n, 512] activations of
+ * the reference never reach memory.  Any n >= 1; all weights wpack* from gp_pack_weight ([Cout, Cin] of the Conv1d's [Cout, Cin, 1]),
+ * biases as trained; outputs 16-byte aligned.  The output buffer doubles as the scratch of the cross-tile maximum (atomic max on
+ * order-preserving integer keys, zeroed and decoded by the entry point itself): it holds no meaningful value until the call's last
+ * kernel has run.
+ *
+ * gp_pointnet_stn_pool: the convolutions of the input transform net STNkd(k=3) and its pooling (pointnets.py:60-64)
+ *     g[b, 1024] = max over the cloud's n points of relu(conv3(relu(conv2(relu(conv1(xyz))))))       widths 3 -> 64 -> 128 -> 1024
+ * gp_pointnet_feat_pool: the trunk (pointnets.py:101-118), trans [b, 3, 3] = the transform net's output
+ *     x' = torch.bmm(x, trans), i.e. x'[j] = sum_i x[i] trans[i][j]                                    (pointnets.py:102-104)
+ *     feat[b, 1024] = max over the n points of conv4(relu(conv3(relu(conv2(relu(conv1(x')))))))       widths 3 -> 64 -> 128 -> 512 -> 1024
+ *     conv4 has NO ReLU (pointnets.py:116): the pooled values are signed. */
+int gp_pointnet_stn_pool(int b, int n, const float *xyz, const float *wpack1, const float *bias1, const float *wpack2, const float *bias2,
+                         const float *wpack3, const float *bias3, float *g, gp_stream_t s);
+int gp_pointnet_feat_pool(int b, int n, const float *xyz, const float *trans, const float *wpack1, const float *bias1, const float *wpack2,
+                          const float *bias2, const float *wpack3, const float *bias3, const float *wpack4, const float *bias4, float *feat,
+                          gp_stream_t s);
+
+/* Small-row dense layer with bias and activation: out[rows, n_out] = act([xa | xb] . W^T + bias), W [n_out, k_a + k_b] row-major as trained
+ * (NOT packed), xa [rows, k_a], xb [rows, k_b] or NULL with k_b = 0; k_a, k_b multiples of 4; act = GP_ACT_NONE | GP_ACT_RELU.
+ * Serves the transform net's head fc1 -> fc2 -> fc3 (pointnets.py:66-68; the caller folds `+ iden`, :70-77, into fc3's bias) and the
+ * agent's fusion_layer over cat(pointnet_feat, pointnet2_feat) without materialising the concatenation (posenet.py:87-88).
+ * gp_point_linear above (no bias, no activation, packed weights, many rows) is unchanged. */
+#define GP_ACT_NONE 0
+#define GP_ACT_RELU 1
+int gp_dense_rows(int rows, int k_a, int k_b, int n_out, const float *xa, const float *xb, const float *W, const float *bias, int act, float *out,
+                  gp_stream_t s);
 
 /* Weight packing for the MFMA layers (host-callable helpers operating on HOST memory):
  * W is [n_out, k_in] row-major (torch Linear / 1x1 conv layout).  Packed size in floats = gp_pack_weight_size(). */
