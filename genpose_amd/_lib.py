@@ -14,6 +14,7 @@ c_int, c_float, c_void_p, c_int64 = ctypes.c_int, ctypes.c_float, ctypes.c_void_
 P = c_void_p
 PLAN_SHARED = 0x200     # GP_PLAN_SHARED: the RK45 driver's shared-chunk plan (16 | or 48 |), see include/genpose_hip.h
 PLAN_FLAGS = 0x300
+RK45_MODEL_LIKELIHOOD_EXACT = 4  # GP_RK45_MODEL_LIKELIHOOD_EXACT: the likelihood ODE with the exact divergence (3 stays an unknown model)
 PLAN_HEADSPLIT = 0x100  # GP_PLAN_HEADSPLIT (include/genpose_hip.h): OR-ed onto a 16-row tile plan = three workgroups per tile, one head each
 
 
@@ -69,6 +70,7 @@ SIGNATURES = {
     "gp_cloud_sample": [c_int, c_int, c_int, P, P, P, P, P],
     "gp_score_div": [c_int, c_int, NETP, P, P, P, P, P, P, P, P],
     "gp_energy_score": [c_int, c_int, NETP, P, P, P, P, P, P, P],
+    "gp_score_div_exact": [c_int, c_int, NETP, P, P, P, P, P, P, P],
     "gp_pc_tile_rows": [c_int, c_int, c_int],
     "gp_pc_layout": [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
     "gp_pc_step_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 12 + [c_int, P],

@@ -101,10 +101,13 @@ struct OdeArgs {
 //   0  probability-flow ODE of the score network           dx/dt = -g^2/2 . f / (sigma + 1e-7)                 (samplers.py:163-227)
 //   1  the same ODE driven by the ENERGY network's score    ... . d/dx <x, f(x)/sigma>                          (posenet.py:94-130, energynet.py:200-222)
 //   2  likelihood ODE of the score network                  d[x, logp]/dt = -g^2/2 . [score, probe^T J_score probe]   (samplers.py:22-99)
-// Models 1 and 2 need the backward pass of the trunk (score_bwd.h) and run on 16-row tiles.
+//   4  the same with the EXACT divergence                   d[x, logp]/dt = -g^2/2 . [score, tr J_score]   (MODEL_EXACT; no probe; tile form only)
+// Models 1, 2 and 4 need the backward pass of the trunk (score_bwd.h) and run on 16-row tiles.
+constexpr int MODEL_EXACT = GP_RK45_MODEL_LIKELIHOOD_EXACT;
+static inline bool ode_model_known(int model) { return (model >= 0 && model <= 2) || model == MODEL_EXACT; }
 template <int MODEL>
 struct OdeModel {
-    static constexpr int NC = MODEL == 2 ? 10 : POSE;
+    static constexpr int NC = (MODEL == 2 || MODEL == MODEL_EXACT) ? 10 : POSE;
     static constexpr bool BWD = MODEL != 0;
 };
 
@@ -278,6 +281,9 @@ __device__ __forceinline__ bool rk45_stage_body(const OdeArgs &a, const gp_score
         // (ORD8: the shared-chunk plan's tiles - the output sums in the order of the 32- / 64-row tiles, score_trunk.h)
         trunk_ftheta<P, false, TrunkNoEmit, SPLIT, ORD8 || P == 48>(lds, net, a.cvec, tvec, row0, rend, a.kcand, pre, TrunkNoEmit(), hsel);
         F = lds + L::OFF_H1, ldf = L::LDH;
+    } else if constexpr (MODEL == MODEL_EXACT) {
+        F = gp_bwd::score_div_exact_tile(lds, net, a.cvec, tvec, row0, rend, a.kcand, pre, sigma);
+        ldf = gp_bwd::LDS_OUT;
     } else {
         F = gp_bwd::score_vjp_tile<MODEL == 1 ? gp_bwd::ENERGY : gp_bwd::SCORE_DIV>(lds, net, a.cvec, tvec, row0, rend, a.kcand, pre, sigma);
         ldf = gp_bwd::LDS_OUT;
@@ -924,7 +930,7 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
                            const gp_split::SplitNet *x9 = nullptr) {
     const size_t chain_lds = MODEL == 0 ? gp_chain::Cfg<2>::LDS_BYTES : gp_chain::CfgV<2>::LDS_BYTES;
     const double *y = a.y;
-    const size_t lds = MODEL == 0 ? trunk_lds_bytes<P>() : gp_bwd::LDS_BYTES;
+    const size_t lds = MODEL == 0 ? trunk_lds_bytes<P>() : (MODEL == MODEL_EXACT ? gp_bwd::LDS_BYTES_EXACT : gp_bwd::LDS_BYTES);
     static bool attr_done = false;
     if (!attr_done) {
         if constexpr (CHAIN) {
@@ -939,7 +945,7 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
             set_lds(rk45_stage_kernel<P, 4, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 5, MODEL, SPLIT>, lds) ||
             set_lds(rk45_stage_kernel<P, 6, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 7, MODEL, SPLIT>, lds))
             return GP_ELAUNCH;
-        if constexpr (MODEL != 2) {
+        if constexpr (OdeModel<MODEL>::NC == POSE) {
             if (set_lds(rk45_finish_kernel<P, MODEL>, lds)) return GP_ELAUNCH;
         }
         if constexpr (!CHAIN && !SPLIT && P == 16) {
@@ -1048,7 +1054,7 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
             break;
         case 5:
             if (!x_out) return GP_EINVAL;
-            if constexpr (MODEL == 2) {
+            if constexpr (OdeModel<MODEL>::NC != POSE) {
                 hipLaunchKernelGGL(rk45_copy_final_kernel, dim3(32, a.ngroups), blk1, 0, st, a, x_out);
             } else {
                 OdeArgs af = a;  // (the denoising evaluation runs on whole tiles, one workgroup each, under every plan)
@@ -1136,21 +1142,28 @@ int gp_rk45_state_layout(int64_t *out, int n) {
     return GP_OK;
 }
 
+// plan 0 of a model: a whole-tile plan (score_trunk.h); the exact-divergence likelihood runs on 16-row tiles only
+static int ode_plan_auto(int model, int ngroups, int rg, int k) {
+    if (model == MODEL_EXACT) return (ngroups > 1 && rg % 16 != 0) ? -1 : 16;
+    return model == 0 ? score_plan_rows(ngroups * rg, ngroups > 1 ? rg : 0, k) : score_plan_rows_vjp(ngroups * rg, ngroups > 1 ? rg : 0, k);
+}
+
 static int ode_args(OdeArgs *a, int *tile, int plan, int model, const float *probe, int ngroups, int nclouds_per_group, int k, const float *cvec, float *tvec,
                     const float *centre, void *state, double *y, double *ynew, double *K, double *partials, double *traj, float *x32) {
     if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !cvec || !tvec || !centre || !state || !y || !ynew || !K || !partials) return GP_EINVAL;
-    if (model < 0 || model > 2 || (model == 2 && !probe)) return GP_EINVAL;
+    if (!ode_model_known(model) || (model == 2 && !probe) || (model == MODEL_EXACT && probe)) return GP_EINVAL;
     const int rg = nclouds_per_group * k;
     // launch plan of the stage kernels (score_trunk.h: score_plan_rows): 16 / 32-row tiles or the 128-row chain form; plan != 0 forces one
     // plan = 0: a WHOLE-tile plan (one partial sum per tile).  The head-split and shared-chunk plans keep more partial sums and are taken
     // only when the caller asks for them by name - gp_rk45_plan_rows() recommends, gp_rk45_partials_count() sizes the buffer.
-    if (plan == 0) plan = model == 0 ? score_plan_rows(ngroups * rg, ngroups > 1 ? rg : 0, k) : score_plan_rows_vjp(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    if (plan == 0) plan = ode_plan_auto(model, ngroups, rg, k);
     if (plan < 0) return GP_EINVAL;
     const int P = plan & ~GP_PLAN_HEADSPLIT;
     a->hsplit = (plan & GP_PLAN_HEADSPLIT) ? 3 : 1;
     if (a->hsplit == 3 && (model != 0 || P != 16)) return GP_EINVAL;  // one head per workgroup: score model, 16-row tiles
     if (P != 16 && P != 32 && P != 64 && P != 128) return GP_EINVAL;
     if (model != 0 && (P == 32 || P == 64)) return GP_EINVAL;  // forward + backward: 16-row tiles (score_bwd.h) or the 128-row chain form (trunk_chain_vjp.h)
+    if (model == MODEL_EXACT && P != 16) return GP_EINVAL;     // the exact divergence has no chain form
     if (P == 128 && !gp_chain::Cfg<2>::fits(k)) return GP_EINVAL;
     if (ngroups > 1 && rg % P != 0) return GP_EINVAL;  // workgroups must not straddle groups
     a->nrows = ngroups * rg, a->kcand = k;
@@ -1158,7 +1171,7 @@ static int ode_args(OdeArgs *a, int *tile, int plan, int model, const float *pro
     a->blk_info = nullptr, a->grp_info = nullptr;
     a->cvec = cvec, a->tvec = tvec, a->centre = centre, a->st = (Rk45State *)state;
     a->y = y, a->ynew = ynew, a->K = K, a->partials = partials, a->traj = traj, a->x32 = x32;
-    a->probe = probe, a->ncomp = model == 2 ? 10 : 9;
+    a->probe = probe, a->ncomp = (model == 2 || model == MODEL_EXACT) ? 10 : 9;
     a->ext_sums = nullptr, a->ext_rows = 0;
     *tile = P;
     return GP_OK;
@@ -1214,6 +1227,7 @@ int gp_rk45_phase_model(int model, int plan, const float *probe, int phase, int 
     rk45_phase_impl<16, MM, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out, (hipStream_t)s)
     if (model == 1) return P == 128 ? GP_RK45_CHAIN(1) : GP_RK45_CALL(16, 1);
     if (model == 2) return P == 128 ? GP_RK45_CHAIN(2) : GP_RK45_CALL(16, 2);
+    if (model == MODEL_EXACT) return GP_RK45_CALL(16, MODEL_EXACT);
 #undef GP_RK45_CHAIN
     if (P == 128)
         return rk45_phase_impl<32, 0, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out,
@@ -1248,9 +1262,9 @@ int gp_rk45_phase_bf16x9(int phase, int ngroups, int nclouds_per_group, int k, c
 }
 
 int gp_rk45_plan_rows(int model, int ngroups, int nclouds_per_group, int k) {
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || model < 0 || model > 2) return GP_EINVAL;
+    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !ode_model_known(model)) return GP_EINVAL;
     const int rg = nclouds_per_group * k;
-    if (model != 0) return score_plan_rows_vjp(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    if (model != 0) return ode_plan_auto(model, ngroups, rg, k);
     SharedPlan sp;
     if (ngroups == 1 && shared_plan(rg, k, &sp)) return sp.pw | GP_PLAN_SHARED;  // a few chunks more than whole rounds of the CUs
     return score_plan_latency(ngroups * rg, ngroups > 1 ? rg : 0, k);
@@ -1258,18 +1272,18 @@ int gp_rk45_plan_rows(int model, int ngroups, int nclouds_per_group, int k) {
 
 /* gp_rk45_plan_rows without the shared-chunk plan (a batch sharded over several GPUs: its controller runs on all-reduced per-group sums) */
 int gp_rk45_plan_rows_unshared(int model, int ngroups, int nclouds_per_group, int k) {
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || model < 0 || model > 2) return GP_EINVAL;
+    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !ode_model_known(model)) return GP_EINVAL;
     const int rg = nclouds_per_group * k;
-    if (model != 0) return score_plan_rows_vjp(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    if (model != 0) return ode_plan_auto(model, ngroups, rg, k);
     return score_plan_latency(ngroups * rg, ngroups > 1 ? rg : 0, k);
 }
 
 /* Doubles the `partials` buffer of gp_rk45_phase_model must hold under `plan` (0 = what plan 0 resolves to), every phase included. */
 int gp_rk45_partials_count(int model, int plan, int ngroups, int nclouds_per_group, int k) {
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || model < 0 || model > 2) return GP_EINVAL;
+    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !ode_model_known(model)) return GP_EINVAL;
     const int rg = nclouds_per_group * k;
     auto whole = [&](int p) { return 3 * ngroups * ((rg + p - 1) / p); };
-    if (plan == 0) plan = model == 0 ? score_plan_rows(ngroups * rg, ngroups > 1 ? rg : 0, k) : score_plan_rows_vjp(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    if (plan == 0) plan = ode_plan_auto(model, ngroups, rg, k);
     if (plan < 0) return GP_EINVAL;
     if (plan & GP_PLAN_SHARED) {
         SharedPlan sp;

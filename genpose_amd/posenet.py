@@ -232,23 +232,26 @@ class GFObjectPose:
             return out
         raise NotImplementedError(sampler)
 
-    def calc_likelihood(self, data, atol=1e-5, rtol=1e-5):
+    def calc_likelihood(self, data, atol=1e-5, rtol=1e-5, divergence="hutchinson"):
         """posenet.py:133-147: log-likelihood (bits) of data['sampled_pose'] under the score model, one probe per row drawn from
-        the prior.  data['pts_feat'] must be there (mode 'pts_feature')."""
-        from .likelihood import cond_ode_likelihood
+        the prior.  data['pts_feat'] must be there (mode 'pts_feature').
+        divergence='exact' (ours): the exact trace instead of the one-probe estimate - no prior draw (prior_fn is not called, the CPU
+        generator does not move), a deterministic function of (cloud, pose)."""
+        from .likelihood import cond_ode_likelihood, solver_model
+        model = solver_model(divergence)
         self._need_weights()
         if self.cfg.posenet_mode != "score":
             raise NotImplementedError("likelihoods come from the score model")
         cvec, K = self._rows(data)
         x = data["sampled_pose"].float().contiguous()
-        epsilon = self.prior_fn((x.shape[0], 9)).to(self.device)
+        epsilon = self.prior_fn((x.shape[0], 9)).to(self.device) if divergence == "hutchinson" else None
         self.last_likelihood_stats = {}
-        key = ("likelihood", cvec.shape[0], K)
+        key = ("likelihood", cvec.shape[0], K) if divergence == "hutchinson" else ("likelihood", cvec.shape[0], K, divergence)
         solver = self._samplers.get(key)
         if solver is None:
-            solver = self._samplers[key] = ODESampler(self.pose_score_net, cvec.shape[0], K, self.device, model="likelihood")
+            solver = self._samplers[key] = ODESampler(self.pose_score_net, cvec.shape[0], K, self.device, model=model)
         _, ll = cond_ode_likelihood(self.pose_score_net, cvec, K, x, epsilon, eps=self.sampling_eps, rtol=rtol, atol=atol,
-                                    stats=self.last_likelihood_stats, solver=solver)
+                                    stats=self.last_likelihood_stats, solver=solver, divergence=divergence)
         return ll
 
     @staticmethod
@@ -286,7 +289,7 @@ class GFObjectPose:
             sigma = (SIGMA_MIN * (SIGMA_MAX / SIGMA_MIN) ** t0).contiguous()
             return self.pose_score_net.evaluate(cvec, K, data["sampled_pose"].float().contiguous(), tvec[0], sigma, mode)
         if mode == "likelihood":
-            return self.calc_likelihood(data)
+            return self.calc_likelihood(data, divergence=getattr(self.cfg, "likelihood_divergence", "hutchinson"))
         if mode == "pc_sample":
             return self.sample(data, "pc", init_x=init_x)
         if mode == "ode_sample":

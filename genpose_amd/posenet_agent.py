@@ -92,6 +92,25 @@ class PoseNet:
                 return [pred_pose, in_process_sample]
             return pred_pose
 
+    # ------------------------------------------------------------------ likelihood of candidate poses (ours; beside get_energy)
+    def get_likelihood(self, data, pose_samples, extract_pts_feature=True, atol=1e-5, rtol=1e-5):
+        """pose_samples [B,K,9] (the layout pred_func returns) -> [B,K] log-likelihood in bits (float64) under the SCORE model, from the
+        likelihood ODE with the exact divergence (GFObjectPose.calc_likelihood(divergence='exact')): deterministic, no probe, no energy
+        model.  The translation is re-centred by data['pts_center'] as get_energy re-centres it.  Fed as both columns of the [n,K,2]
+        energy array it drives the existing ranking (reward.sort_poses_by_energy / gp_rank_aggregate): higher = more likely = first.
+        Deterministic means: the same call returns the same bits.  All B*K rows of a call share ONE adaptive step sequence and one error
+        norm (as in the reference's solve), so a candidate's value depends, within rtol / atol, on the other candidates of the call: compare
+        candidates of one call, and tighten rtol / atol where values of different calls are set side by side."""
+        self.is_testing = True
+        self.net.eval()
+        bs, repeat_num = pose_samples.shape[0], pose_samples.shape[1]
+        with torch.no_grad():
+            pts_feat = data["pts_feat"] if not extract_pts_feature else self.net(data, mode="pts_feature")
+            pose = pose_samples.clone().view(bs * repeat_num, -1).type_as(pts_feat)
+            pose[:, -3:] -= data["pts_center"].unsqueeze(1).repeat(1, repeat_num, 1).view(bs * repeat_num, -1)
+            rows = {"pts_feat": pts_feat, "sampled_pose": pose, "_repeat": repeat_num}
+            return self.net.calc_likelihood(rows, atol=atol, rtol=rtol, divergence="exact").reshape(bs, repeat_num)
+
     # ------------------------------------------------------------------ energy (posenet_agent.py:471-527)
     def get_energy(self, data, pose_samples, T=None, mode="test", extract_pts_feature=True):
         if mode != "test":

@@ -287,7 +287,8 @@ class ODESampler:
     CHUNKS = (8, 12, 16, 24, 32, 40, 48, 64, 80, 96, 128)  # attempts per first replay
 
     MAX_GRAPHS = 12  # captured attempt graphs kept per kind (each holds chunk x 8 kernel nodes)
-    MODELS = {"score": 0, "energy": 1, "likelihood": 2}
+    MODELS = {"score": 0, "energy": 1, "likelihood": 2, "likelihood_exact": _lib.RK45_MODEL_LIKELIHOOD_EXACT}
+    LIKELIHOOD_MODELS = (2, _lib.RK45_MODEL_LIKELIHOOD_EXACT)  # ten state components per row: pose + log-density change
 
     def __init__(self, net, B, K, device, use_graph=True, poll=8, groups=1, group_clouds=None, model="score", coupling_group=None, tile=0,
                  trunk=None):
@@ -297,7 +298,9 @@ class ODESampler:
 
         model: what the driver integrates (gp_rk45_phase_model) - 'score' the probability-flow ODE of the score network; 'energy' the
         same ODE with the ENERGY network's score (`net` holds its weights; forward + vector-Jacobian product inside the stage
-        kernels); 'likelihood' the [pose, log-density] ODE of cond_ode_likelihood (run_likelihood).
+        kernels); 'likelihood' the [pose, log-density] ODE of cond_ode_likelihood (run_likelihood) with its one-probe Hutchinson
+        divergence; 'likelihood_exact' the same ODE with the exact divergence tr(d score / d x) (nine unit seeds per row inside the stage
+        kernel, csrc/score_bwd.h: no probe, 16-row tiles only).
 
         coupling_group (a torch.distributed process group; "faithful" multi-GPU mode, SURVEY §8e caveat): this rank's B clouds are one
         SHARD of a batch spread over the ranks of the group (equal shards).  scipy's error norm - and the norms of its initial-step
@@ -315,7 +318,7 @@ class ODESampler:
         if trunk not in (None, "f32mfma", "bf16x9"):
             raise ValueError(f"trunk {trunk!r}: 'f32mfma' or 'bf16x9'")
         self.model = self.MODELS[model]
-        self.ncomp = 10 if self.model == 2 else 9
+        self.ncomp = 10 if self.model in self.LIKELIHOOD_MODELS else 9
         self.ragged = group_clouds is not None
         self.shared = False
         if self.ragged and self.model != 0:
@@ -352,6 +355,8 @@ class ODESampler:
             #                           | GP_PLAN_SHARED (one workgroup per CU, the left-over 16-row chunks shared across the stages of an attempt)
             self.tile, self.hsplit = self.plan & ~_lib.PLAN_FLAGS, (3 if self.plan & _lib.PLAN_HEADSPLIT else 1)
             self.shared = bool(self.plan & _lib.PLAN_SHARED)
+            if self.model == _lib.RK45_MODEL_LIKELIHOOD_EXACT and self.plan != 16:
+                raise ValueError(f"model 'likelihood_exact' runs on 16-row tiles (plan {self.plan:#x}; several batches: rows per batch a multiple of 16)")
             if ((self.hsplit == 3 and (self.tile != 16 or self.model != 0)) or self.tile not in (16, 32, 48, 64, 128) or (self.tile == 48 and not self.shared)
                     or (self.model != 0 and self.tile in (32, 48, 64)) or (groups > 1 and (R // groups) % self.tile)):
                 raise ValueError(f"{B // groups} clouds x {K} candidates per batch do not split into workgroups of plan {tile or 'auto'}; "
@@ -400,7 +405,7 @@ class ODESampler:
         self.cvec = torch.empty(B, 768, device=self.dev)
         self.centre = torch.empty(B, 3, device=self.dev)
         self.traj = None
-        if self.model == 2 and poll == 8:
+        if self.model in self.LIKELIHOOD_MODELS and poll == 8:
             poll = 64  # the likelihood ODE runs from eps to 1 at rtol 1e-5: thousands of attempts, fewer status reads
         self.use_graph, self.poll = use_graph, poll
         self._graphs = {}        # kind ('graph' | 'graph_traj' | 'graph_dense') -> {attempts per replay: captured graph}
@@ -551,18 +556,25 @@ class ODESampler:
         self.last_replays = {"first_chunk": first, "attempts_launched": n_done}
         return sts
 
-    def run_likelihood(self, cvec, x, probe, eps=EPS, rtol=1e-5, atol=1e-5, max_attempts=16384):
+    def run_likelihood(self, cvec, x, probe=None, eps=EPS, rtol=1e-5, atol=1e-5, max_attempts=16384):
         """cond_ode_likelihood's integration (samplers.py:73-93) on the device: state [x, logp] from t = eps to t = 1 with the fixed
-        Hutchinson probe.  cvec [B,768]; x, probe [B*K,9].  Returns (z [R,9] f64, delta_logp [R] f64); evaluation count in
-        last_stats['nfev'] (2 for the initial step + 6 per attempt, like solve_ivp)."""
-        if self.model != 2:
-            raise RuntimeError("ODESampler(model='likelihood') required")
+        Hutchinson probe (model 'likelihood') or the exact divergence (model 'likelihood_exact': probe must be None).  cvec [B,768];
+        x, probe [B*K,9].  Returns (z [R,9] f64, delta_logp [R] f64); evaluation count in last_stats['nfev'] (2 for the initial step +
+        6 per attempt, like solve_ivp)."""
+        if self.model not in self.LIKELIHOOD_MODELS:
+            raise RuntimeError("ODESampler(model='likelihood' | 'likelihood_exact') required")
+        exact = self.model != 2
+        if exact and probe is not None:
+            raise ValueError("model 'likelihood_exact' takes no probe: its divergence is the exact trace")
+        if not exact and probe is None:
+            raise ValueError("model 'likelihood' needs the Hutchinson probe [B*K,9]")
         R = self.R
-        if cvec.shape[0] != self.B or x.shape[0] != R or probe.shape[0] != R:
+        if cvec.shape[0] != self.B or x.shape[0] != R or (probe is not None and probe.shape[0] != R):
             raise ValueError(f"likelihood solver set up for {self.B} clouds x {self.K} rows got {cvec.shape[0]} clouds / {x.shape[0]} rows")
         self.cvec.copy_(cvec)
         self.centre.zero_()
-        self.probe.copy_(probe.float())
+        if not exact:
+            self.probe.copy_(probe.float())
         y0 = self.y.view(R, 10)
         y0[:, :9].copy_(x.double())   # solve_ivp casts the initial state to float64
         y0[:, 9].zero_()
@@ -579,7 +591,7 @@ class ODESampler:
             max_attempts=4096):
         """Returns (xs [R,S,9] f64 or None, x [R,9] f64).  With num_steps=None the in-process samples are the accepted
         states (like solve_ivp without t_eval)."""
-        if self.model == 2:
+        if self.model in self.LIKELIHOOD_MODELS:
             raise RuntimeError("ODESampler(model='likelihood') integrates the likelihood ODE: call run_likelihood()")
         dense = return_process and num_steps is not None
         if self.groups > 1 and return_process and not dense:

@@ -58,6 +58,16 @@ class ScoreNetHIP:
         _lib.call("gp_score_div", B, k, self.w.ref(), ptr(cvec), ptr(tvec), ptr(x), ptr(eps), ptr(sigma_dev), ptr(score), ptr(div), stream_ptr())
         return score, div
 
+    def score_and_exact_divergence(self, cvec, k, x, tvec, sigma_dev):
+        """score [B*k,9] (gp_score_div's bits) and the exact divergence tr(d score / d x) [B*k] in one launch (gp_score_div_exact)."""
+        _lib.check_device()
+        B = cvec.shape[0]
+        R = B * k
+        score = torch.empty(R, 9, device=self.device)
+        div = torch.empty(R, device=self.device)
+        _lib.call("gp_score_div_exact", B, k, self.w.ref(), ptr(cvec), ptr(tvec), ptr(x), ptr(sigma_dev), ptr(score), ptr(div), stream_ptr())
+        return score, div
+
     def energy_score(self, cvec, k, x, tvec, sigma_dev, with_energy=False):
         """Score of the energy model = d/dx <x, f(x)/sigma> [B*k,9] (+ that energy [B*k]) in one launch (gp_energy_score)."""
         _lib.check_device()

@@ -276,6 +276,17 @@ int gp_score_eval(int nclouds, int k, const gp_scorenet *net, const float *cvec,
 int gp_score_div(int nclouds, int k, const gp_scorenet *net, const float *cvec, const float *tvec, const float *x, const float *eps,
                  const float *sigma_dev, float *score, float *div, gp_stream_t s);
 
+/* Score and the EXACT divergence of the score field in one launch - what gp_score_div estimates with one probe:
+ *   score[R,9] = f_theta(x)/(sigma+1e-7), the bits gp_score_div writes;  div[R] = tr(d score / d x) = sum_{i<9} d score_i / d x_i.
+ * One forward pass per 16-row tile, then the backward pass for the nine unit seeds: seed e_i selects row i mod 3 of the 256 -> 3 output
+ * layer of head i / 3 (rot_x, rot_y, trans) and runs through that head's 256 pose-feature columns of w_headx_t, then w_pose2_t and
+ * w_pose0_t; the three seeds of a head are three 16-row MFMA tiles of one pass over those weights (csrc/score_bwd.h).  Same fp32 MFMA
+ * arithmetic and transposed packs as gp_score_div; no probe.  x [R,9] f32; tvec [768]; sigma = *sigma_dev.  Null pointers, k <= 0 or a
+ * net without the transposed packs: GP_EINVAL, nothing written; R == 0: GP_OK.  Cost (MI355X, profiles/exact_likelihood.txt): 2.45 x the
+ * time of gp_score_div, 103.7 against 42.3 us at 800 rows and 821 against 335 us at 32 000 rows; bound by the matrix pipe. */
+int gp_score_div_exact(int nclouds, int k, const gp_scorenet *net, const float *cvec, const float *tvec, const float *x, const float *sigma_dev,
+                       float *score, float *div, gp_stream_t s);
+
 /* Score of the ENERGY model (PoseEnergyNet.forward(return_item='score'), energynet.py:200-222): the gradient of the un-decoupled
  * inner-product energy <x, f_theta(x)/sigma> with respect to the pose, which the reference obtains by autograd:
  *   score[R,9] = f_theta/sigma + J_f^T (x/sigma);  energy[R] (may be NULL) = <x, f_theta/sigma>.  `net` = the energy net's block. */
@@ -436,7 +447,7 @@ int gp_rk45_phase_grouped(int phase, int ngroups, int nclouds_per_group, int k, 
                           const float *centre, void *state, double *y, double *ynew, double *K, double *partials, double *traj, int traj_cap,
                           double t0, double t_bound, double rtol, double atol, double denoise_scale, int do_denoise, int nstates, double *x_out,
                           gp_stream_t s);
-/* The same driver for the three right-hand sides it can integrate (`model`):
+/* The same driver for the right-hand sides it can integrate (`model`):
  *   0  gp_rk45_phase_grouped: probability-flow ODE of the score network;
  *   1  the same ODE driven by the ENERGY network's score, the gradient of its inner-product energy (posenet.py:94-130 on a
  *      PoseEnergyNet, energynet.py:200-222; `net` = the energy net's block) - forward + vector-Jacobian product inside the stage kernel;
@@ -444,7 +455,10 @@ int gp_rk45_phase_grouped(int phase, int ngroups, int nclouds_per_group, int k, 
  *      d logp / dt = -g^2/2 probe^T (d score / d x) probe with the fixed Skilling-Hutchinson `probe` [R][9] (device); y, ynew [R*10],
  *      K [7][R*10]; one error norm over all R*10 components (scipy integrates the concatenated vector); phase 5 copies the final
  *      state to x_out [R][10] (no denoise / normalisation); phases 4 and the trajectory arguments are unused.
- * Models 1 and 2 run on 16-row tiles: partials [3][ngroups * ceil(rows_per_group / 16)].
+ *   4  GP_RK45_MODEL_LIKELIHOOD_EXACT: model 2 with the EXACT divergence, d logp / dt = -g^2/2 tr(d score / d x) (the stage arithmetic of
+ *      gp_score_div_exact): the same ten-component state, controller, error norm, status words and phase 5; `probe` must be NULL; plan 16
+ *      (or 0) only - it has no chain form.  (3 stays an unknown model: GP_EINVAL.)
+ * Models 1, 2 and 4 run on 16-row tiles: partials [3][ngroups * ceil(rows_per_group / 16)].
  * A batch SHARDED over several GPUs (SURVEY §8e caveat: scipy's error norm runs over the whole batch): ext_sums [2][ngroups] (device,
  * f64) and ext_rows_per_group = rows of a group over all ranks.  Phases 1, 2, 3 then stop after writing this rank's per-group sums of
  * squares to ext_sums; the caller all-reduces ext_sums (RCCL: capturable with the launches) and runs phase 11, 12 or 13 = the step
@@ -458,6 +472,7 @@ int gp_rk45_phase_grouped(int phase, int ngroups, int nclouds_per_group, int k, 
  * one); recommended by gp_rk45_plan_rows() while tiles x 3 <= CUs (gp_plan_headsplit_pays).  0 = a whole-tile plan is picked.
  * partials: gp_rk45_partials_count() doubles ([3][ngroups * ceil(rows_per_group / rows per workgroup) * (3 under the head-split plan)]). */
 #define GP_PLAN_HEADSPLIT 0x100
+#define GP_RK45_MODEL_LIKELIHOOD_EXACT 4
 /* 16 | GP_PLAN_SHARED or 48 | GP_PLAN_SHARED (round 6; score model, one group; picked by gp_rk45_plan_rows() when it applies): the SHARED-CHUNK plan for
  * launches whose 16-row chunks do not divide over the CUs - T chunks on C CUs with T / C = 1 or 3 and 6 (T mod C) <= C, e.g. the 12 800 rows
  * of scripts/eval_single.sh's batches (800 chunks on 256 CUs).  An attempt is ONE launch of C workgroups: each owns T / C whole chunks for
