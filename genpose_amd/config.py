@@ -29,6 +29,7 @@ DEFAULTS = dict(
     sampler_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products in the PC sampler's score network (csrc/trunk_bf16x3.hip)
     sampler_seed=None,  # (ours) an integer: opt-in seeded noise drawn inside the PC step kernels (csrc/philox.h), reproducible per row; None: torch's generator
     likelihood_divergence="hutchinson",  # (ours) 'exact': net(data, mode='likelihood') integrates the exact trace of the score Jacobian instead of the reference's one-probe Skilling-Hutchinson estimate (csrc/score_bwd.h: score_div_exact_tile) - deterministic, no prior draw
+    heun_grid="geometric",  # (ours) sampler_mode ['heun'] (the fixed-step Heun solver of the probability-flow ODE, samplers.HeunSampler; sampling_steps = its N): the sigma grid - 'geometric' (t uniform) or 'edm' (cond_edm_sampler's rho = 7 discretisation)
     ode_trunk=None,  # (ours) 'bf16x9': opt-in exact-product split-bf16 trunk in the ODE sampler's chain-plan stage kernels (ODESampler(trunk=)); None / 'f32mfma': the fp32 MFMA kernels
     encoder_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products on the 128-196-256 grouping level (csrc/sa_bf16x3.hip)
     encoder_level2="auto",  # (ours) under encoder_precision 'f32', the arithmetic of grouping level 2 (128-196-256): 'bf16x9' = exact-product split bf16 on the BF16 matrix pipe (csrc/sa_bf16x9.hip, the fp32 kernels' error class), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the adaptive ODE sampler (its goldens pin RK45 attempt counts that move with the last bits of the features); encoder_precision='bf16x9' forces it

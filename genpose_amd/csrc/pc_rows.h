@@ -55,6 +55,61 @@ static inline PcArgs pc_args(int ngroups, int rg, int k, int step, int nsteps, i
     return a;
 }
 
+// The fixed-step Heun solver of the probability-flow ODE (cond_edm_sampler's second-order method, samplers.py:230-290, on the VE score
+// model): the same launch shape with a ROW-LOCAL update (heun_update_row, score_trunk.h) - no noise operands, no partial sums, no gn; one
+// more [R,9] buffer holds the slope d_i between a step's two launches.  `step` is the LAUNCH index and `nsteps` the index of the last
+// launch, which finishes only - so `step > 0` (there is an update), `step < nsteps` (there is an evaluation) and `step == nsteps` read as
+// they do in PcArgs.  With N steps: launch 0 evaluates score(x_0, t_0); launch 2i+1 forms and stores d_i, evaluates the Euler point at
+// t_{i+1}; launch 2i+2 forms and stores x_{i+1}, evaluates it at t_{i+1}; launch 2N's evaluation at (x_N, eps) is the denoising one and
+// launch 2N+1 applies it (without denoising launch 2N finishes).  The kernels know nothing about the grid: everything comes from `sched`.
+struct HeunArgs {
+    int nrows, kcand, step, nsteps;
+    const float *cvec, *tvec_all;  // tvec_all [N+1][768]: one row per evaluated time, launch l evaluates at row (l + 1) / 2
+    const float *sched;            // [launches][4]: sigma of the launch's evaluation (the score's divisor), slope factor c, step h, kind (HEUN_*)
+    const float *centre;           // [clouds][3]
+    float *x, *d, *score, *out, *traj;  // x, d, score, out [R,9]; traj [N][R][9] or null: x_1 .. x_N, rotations normalised, centres added
+};
+static inline HeunArgs heun_args(int nrows, int k, int launch, int last_launch, const float *cvec, const float *tvec_all, const float *sched,
+                                 const float *centre, float *x, float *d, float *score, float *out, float *traj) {
+    HeunArgs a;
+    a.nrows = nrows, a.kcand = k, a.step = launch, a.nsteps = last_launch;
+    a.cvec = cvec, a.tvec_all = tvec_all, a.sched = sched, a.centre = centre;
+    a.x = x, a.d = d, a.score = score, a.out = out, a.traj = traj;
+    return a;
+}
+// the row of tvec_all a launch evaluates at
+template <bool HEUN>
+__device__ __forceinline__ int pc_time_row(int step) {
+    return HEUN ? (step + 1) >> 1 : step;
+}
+// what a Heun launch stores for a live row after heun_update_row (one thread per row)
+__device__ __forceinline__ void heun_store_row(const HeunArgs &a, int kind, int r, const float (&xv)[9], const float (&dv)[9], const float (&cen)[3]) {
+    if (kind == HEUN_PREDICT) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) a.d[(size_t)r * 9 + j] = dv[j];
+        return;
+    }
+    float o[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) o[j] = xv[j];
+    normalize_rot6(o);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[6 + j] += cen[j];
+    if (kind != HEUN_DENOISE) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) a.x[(size_t)r * 9 + j] = xv[j];
+        if (a.traj) {
+            float *tr = a.traj + ((size_t)((a.step - 2) >> 1) * a.nrows + r) * 9;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) tr[j] = o[j];
+        }
+    }
+    if (kind != HEUN_CORRECT) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) a.out[(size_t)r * 9 + j] = o[j];
+    }
+}
+
 // A wave's rows through one launch: lane (pt, g) = (lane & 15, lane >> 4) carries row 16 * (wave * PT + p) + pt of the workgroup for
 // each tile p.  Every lane of a row's four lane groups carries the row's 9-vector (the update is ~150 VALU instructions per wave,
 // computed redundantly by the four groups - cheaper than any exchange), lane group 0 stores.  The three phases keep one issue order
@@ -62,15 +117,19 @@ static inline PcArgs pc_args(int ngroups, int rg, int k, int step, int nsteps, i
 // it, finish_previous() then runs the update while the weights are still on their way.
 // SEEDED: the two 9-vectors of noise are not loaded but drawn (gp_philox::draw9: seed state behind a.z_lang, global row = its row base
 // + the row of the launch) right before the update - the same values gp_pc_noise_fill writes, the same update expression after them.
+// HEUN: the Heun solver's launches (HeunArgs) - the overloads of request / finish_previous below; zz1 carries d_i, gdiff the slope factor,
+// dt the step.
 struct PcNoSeed {};
-template <int PT, bool SEEDED = false>
+template <int PT, bool SEEDED = false, bool HEUN = false>
 struct PcRows {
+    static_assert(!(SEEDED && HEUN), "the Heun update draws no noise");
     int row[PT];
     float xv[PT][9], gr[PT][9], zz1[PT][9], zz2[PT][9], cen[PT][3];
     typename std::conditional<SEEDED, gp_philox::Seed, PcNoSeed>::type seed;
     float gdiff, dt, sqdt, gn, sigma;
     float psum[4];    // the batch's first 256 partial sums, one per lane and quarter
     const float *pp;  // the batch's partial sums of step i-1
+    int kind;         // HEUN: the launch's kind (HEUN_*)
 
     // (1) the rows' operands, then the schedule and the batch's partial sums (or the statistic from outside), then sigma(t_i)
     template <int NW>
@@ -168,11 +227,49 @@ struct PcRows {
         }
         return i == a.nsteps;
     }
+
+    // HEUN (1): the rows' state, the stored score and, for a corrector launch, d_i; the launch's row of the schedule
+    template <int NW>
+    __device__ __forceinline__ void request(const HeunArgs &a, int wave, int lane) {
+        static_assert(HEUN, "HeunArgs drive the HEUN instantiations");
+        const int i = a.step, pt = lane & 15, wg_row0 = blockIdx.x * (16 * PT * NW);
+        const float *sc = a.sched + (size_t)i * 4;
+        const int kind_ = (int)sc[3];
+#pragma unroll
+        for (int p = 0; p < PT; ++p) row[p] = wg_row0 + (wave * PT + p) * 16 + pt;
+#pragma unroll
+        for (int p = 0; p < PT; ++p) {
+            const int r = row[p] < a.nrows ? row[p] : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
+#pragma unroll
+            for (int j = 0; j < 9; ++j) xv[p][j] = a.x[(size_t)r * 9 + j];
+            if (i > 0) {
+#pragma unroll
+                for (int j = 0; j < 9; ++j) gr[p][j] = a.score[(size_t)r * 9 + j];
+#pragma unroll
+                for (int j = 0; j < 9; ++j) zz1[p][j] = kind_ == HEUN_CORRECT || kind_ == HEUN_CORRECT_LAST ? a.d[(size_t)r * 9 + j] : 0.f;
+                const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
+                cen[p][0] = cp[0], cen[p][1] = cp[1], cen[p][2] = cp[2];
+            }
+        }
+        sigma = sc[0], gdiff = sc[1], dt = sc[2], kind = kind_;
+    }
+
+    // HEUN (3): the update and the stores.  True when the launch is the finish-only one: the caller returns.
+    __device__ __forceinline__ bool finish_previous(const HeunArgs &a, int lane) {
+        static_assert(HEUN, "HeunArgs drive the HEUN instantiations");
+        if (a.step == 0) return false;
+#pragma unroll
+        for (int p = 0; p < PT; ++p) {
+            heun_update_row(kind, xv[p], zz1[p], gr[p], gdiff, dt);
+            if (row[p] < a.nrows && (lane >> 4) == 0) heun_store_row(a, kind, row[p], xv[p], zz1[p], cen[p]);
+        }
+        return a.step == a.nsteps;
+    }
 };
 
 // Components j0 .. j0 + N - 1 of a row's score are final: stored by lane group 0, their squares summed into q in component order.
-template <int N>
-__device__ __forceinline__ void pc_store_score(const PcArgs &a, int row, int lane, int j0, const float (&sc)[N], float &q) {
+template <int N, class Args>
+__device__ __forceinline__ void pc_store_score(const Args &a, int row, int lane, int j0, const float (&sc)[N], float &q) {
 #pragma unroll
     for (int c = 0; c < N; ++c) q += sc[c] * sc[c];
     if (row < a.nrows && lane < 16) {

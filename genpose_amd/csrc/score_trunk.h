@@ -456,4 +456,36 @@ __device__ __forceinline__ void pc_update_row(float (&xv)[9], const float (&gr)[
     normalize_rot6(xv);
 }
 
+// One launch's row update of the fixed-step Heun solver of the probability-flow ODE, integrated in sigma (cond_edm_sampler,
+// samplers.py:230-290, driven by the VE score model through denoised = x + sigma^2 score: the slope is d = -sigma score).  Row-local: no
+// noise, no batch statistic.  The operation order is written here once (tests/heun_reference.py restates it in float64).  sc: the score
+// the previous launch stored; c, h: the launch's slope factor and step from the device schedule; no renormalisation between steps.
+//   HEUN_PREDICT               c = -sigma_i,      h = sigma_{i+1} - sigma_i: dv <- d_i = c sc (the caller stores it); xv <- the Euler point
+//                              x_i + h d_i, which the launch evaluates at t_{i+1} and never stores
+//   HEUN_CORRECT[_LAST]        c = -sigma_{i+1},  the same h: d' = c sc; xv <- x_{i+1} = x_i + h (0.5 d_i + 0.5 d')
+//   HEUN_DENOISE               c = g(eps), h = the predictor's step: xv <- x_N + (0 - c^2 sc) h, the reverse-diffusion predictor of
+//                              cond_ode_sampler (:209-218) in the f32 order of rk45_finish_kernel
+enum { HEUN_EVAL = 0, HEUN_PREDICT = 1, HEUN_CORRECT = 2, HEUN_CORRECT_LAST = 3, HEUN_DENOISE = 4 };
+__device__ __forceinline__ void heun_update_row(int kind, float (&xv)[9], float (&dv)[9], const float (&sc)[9], float c, float h) {
+    if (kind == HEUN_PREDICT) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            dv[j] = c * sc[j];
+            xv[j] = xv[j] + h * dv[j];
+        }
+    } else if (kind == HEUN_CORRECT || kind == HEUN_CORRECT_LAST) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const float dp = c * sc[j];
+            xv[j] = xv[j] + h * (0.5f * dv[j] + 0.5f * dp);
+        }
+    } else if (kind == HEUN_DENOISE) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const float drift = 0.f - (c * c) * sc[j];  // sign as written in the reference (samplers.py:216)
+            xv[j] = xv[j] + drift * h;
+        }
+    }
+}
+
 }  // namespace gp_trunk

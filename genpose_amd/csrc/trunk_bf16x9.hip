@@ -32,13 +32,16 @@ using namespace gp_trunk;
 using namespace gp_x9trunk;
 
 // SEEDED (pc_step_chain_seeded_kernel_bf16x9): PcRows draws the noise (pc_rows.h); the rest is the same text.
-template <bool SEEDED>
-__device__ __forceinline__ void pc_step_chain_bf16x9(const PcArgs &a, const SplitNet &w) {
+// HEUN (heun_step_chain_kernel_bf16x9; Args = HeunArgs): a launch of the fixed-step Heun solver of the probability-flow ODE
+// (cond_edm_sampler's method, samplers.py:230-290) - PcRows runs the row-local update, the score is stored, there is no partial sum.
+template <bool SEEDED, bool HEUN = false, class Args = PcArgs>
+__device__ __forceinline__ void pc_step_chain_bf16x9(const Args &a, const SplitNet &w) {
+    static_assert(HEUN == std::is_same<Args, HeunArgs>::value && !(HEUN && SEEDED), "HeunArgs drive the HEUN instantiation");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), i = a.step;
     const int wg_row0 = blockIdx.x * X9_ROWS;
     // ---- the rows' operands first, the ring prologue behind them (memory returns in order)
-    PcRows<X9_RT, SEEDED> rs;
+    PcRows<X9_RT, SEEDED, HEUN> rs;
     rs.template request<X9_NW>(a, wave, lane);
     bf16x8 first[X9_PER_T], hold[X9_PER_T];
     if (i < a.nsteps) request(w, tid, first, hold);
@@ -46,16 +49,17 @@ __device__ __forceinline__ void pc_step_chain_bf16x9(const PcArgs &a, const Spli
     // each head's three score components are final once its epilogue is done: stored there, their squares summed in component order
     const float sden = rs.sigma + 1e-7f;
     float q[X9_RT] = {};
-    run(lds, w, a.cvec, a.tvec_all + (size_t)i * HEADS, wg_row0, a.nrows, a.kcand, first, hold, rs.xv, rs.row,
+    run(lds, w, a.cvec, a.tvec_all + (size_t)pc_time_row<HEUN>(i) * HEADS, wg_row0, a.nrows, a.kcand, first, hold, rs.xv, rs.row,
         [&](int h, int p, const float (&out)[3]) __attribute__((always_inline)) {
             const float sc[3] = {out[0] / sden, out[1] / sden, out[2] / sden};
             pc_store_score(a, rs.row[p], lane, 3 * h, sc, q[p]);
         });
-    pc_store_partial<X9_RT, X9_NW>(a, rs.row, q, wave, lane);
+    if constexpr (!HEUN) pc_store_partial<X9_RT, X9_NW>(a, rs.row, q, wave, lane);
 }
 
 __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<false>(a, w); }
 __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_seeded_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<true>(a, w); }
+__global__ __launch_bounds__(X9_NT, 1) void heun_step_chain_kernel_bf16x9(HeunArgs a, SplitNet w) { pc_step_chain_bf16x9<false, true>(a, w); }
 
 // What the two entry points share: the chain plan's rules, PcArgs / SplitNet, the once-per-kernel LDS attribute and the launch.
 // z_lang carries the Langevin noise or, for the seeded kernel, the seed state (PcArgs).
@@ -108,6 +112,29 @@ int gp_pc_step_bf16x9_seeded(int ngroups, int nclouds_per_group, int k, int step
     return launch_pc_bf16x9(pc_step_chain_seeded_kernel_bf16x9, done, ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched,
                             reinterpret_cast<const float *>(seed_state), nullptr, centre, x, mean_x, score, partials, traj, gn_ext, gn_rows_total, w_pose0_x9,
                             w_pose2_x9, w_headx_x9, s);
+}
+
+int gp_heun_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                        const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                        const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_heun_launches(nsteps, denoise) || !net || !cvec ||
+        !tvec_all || !sched || !centre || !x || !d || !score || !out || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9)
+        return GP_EINVAL;
+    const int rg = nclouds_per_group * k;
+    if (ngroups * rg == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(X9_ROWS, ngroups, nclouds_per_group, k, &P);  // the chain plan's rules
+    if (rc != GP_OK) return rc;
+    const HeunArgs a = heun_args(ngroups * rg, k, launch, gp_heun_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
+                        reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(heun_step_chain_kernel_bf16x9, X9Lds::BYTES)) return GP_ELAUNCH;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(heun_step_chain_kernel_bf16x9, dim3(ngroups * ((rg + X9_ROWS - 1) / X9_ROWS)), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
+    return gp_launch_status();
 }
 
 }  // extern "C"

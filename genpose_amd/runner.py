@@ -244,6 +244,9 @@ class TrackingRunner:
         self.buffer = {"model_name": [], "pred_sRT": None}
         self.use_graphs = use_graphs
         if use_graphs:  # the frame graphs drive the PointNet++ encoder's stages themselves: refused here, not at the first frame
+            if score_agent.cfg.sampler_mode[0] == "heun":
+                raise NotImplementedError("TrackingRunner(use_graphs=True) builds its frame graphs around the adaptive ODE solve and does not serve "
+                                          "sampler_mode ['heun']: use use_graphs=False (the agent's pred_func)")
             for a in (score_agent, energy_agent):
                 a.net.pointnet2_encoder("TrackingRunner(use_graphs=True)")
         self._graphs = None

@@ -1,5 +1,5 @@
 """Samplers on the HIP kernels: cond_pc_sampler / cond_ode_sampler of networks/gf_algorithms/samplers.py:102-227
-(pose_mode 'rot_matrix', VE SDE).  Host code only builds schedule tables, owns buffers and replays hipGraphs;
+(pose_mode 'rot_matrix', VE SDE), and cond_edm_sampler's fixed-step Heun method (:230-290) on the same probability-flow ODE.  Host code only builds schedule tables, owns buffers and replays hipGraphs;
 every per-step operation runs in csrc/scorenet.hip / csrc/rk45.hip.
 """
 import numpy as np
@@ -262,6 +262,175 @@ def philox_raw(counters, keys):
     out = torch.empty_like(counters)
     _lib.call("gp_philox_raw", counters.shape[0], ptr(counters), ptr(keys), ptr(out), stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------------------------------------- PF-ODE (fixed-step Heun)
+HEUN_GRIDS = ("geometric", "edm")
+_HEUN_G_FACTOR = np.float32(4.1272735595703125)  # (float)sqrt(2 (ln 50 - ln 0.01)): g(t) = sigma(t) * this, in f32 like the RK45 driver's denoise
+
+
+def heun_launches(nsteps, denoise=True):
+    """Launches of a Heun chain (gp_heun_launches): 2 N + 1, one more with denoise.  NFE = launches - 1."""
+    if int(nsteps) < 1:
+        raise ValueError(f"nsteps {nsteps}: at least one step")
+    return 2 * int(nsteps) + 1 + (1 if denoise else 0)
+
+
+def heun_grid(nsteps, T0=1.0, eps=EPS, grid="geometric", rho=7.0):
+    """Times t_0 = T0 > ... > t_N = eps and their sigma_i = sigma_min (sigma_max / sigma_min)^t_i, float64.
+    'geometric': t uniform from T0 to eps (sigma geometric); 'edm': cond_edm_sampler's rho discretisation (samplers.py:241-242) between
+    sigma(T0) and sigma(eps), mapped back to t.  Both end exactly at eps."""
+    N = int(nsteps)
+    if N < 1:
+        raise ValueError(f"nsteps {nsteps}: at least one step")
+    if grid not in HEUN_GRIDS:
+        raise ValueError(f"heun grid {grid!r}: one of {HEUN_GRIDS}")
+    if not 0.0 < eps < T0:
+        raise ValueError(f"need 0 < eps < T0, got eps {eps}, T0 {T0}")
+    ratio = SIGMA_MAX / SIGMA_MIN
+    if grid == "geometric":
+        t = np.linspace(float(T0), float(eps), N + 1)
+    else:
+        s_hi, s_lo = SIGMA_MIN * ratio ** float(T0), SIGMA_MIN * ratio ** float(eps)
+        idx = np.arange(N + 1, dtype=np.float64)
+        s = (s_hi ** (1.0 / rho) + idx / N * (s_lo ** (1.0 / rho) - s_hi ** (1.0 / rho))) ** rho
+        t = np.log(s / SIGMA_MIN) / np.log(ratio)
+    t[0], t[-1] = float(T0), float(eps)
+    return t, SIGMA_MIN * ratio ** t
+
+
+def heun_schedule(nsteps, T0=1.0, eps=EPS, grid="geometric", rho=7.0, denoise=True):
+    """Host schedule of a Heun chain: (t [N+1] f64, sched [launches,4] f32) - per launch the sigma of its evaluation (the score's divisor),
+    the slope factor, the step h and the launch kind (include/genpose_hip.h: gp_heun_step_plan), computed in float64 and rounded once."""
+    N = int(nsteps)
+    t, sig = heun_grid(N, T0, eps, grid, rho)
+    h = sig[1:] - sig[:-1]
+    sched = np.zeros((heun_launches(N, denoise), 4), dtype=np.float64)
+    sched[0] = (sig[0], 0.0, 0.0, 0.0)
+    for i in range(N):
+        sched[2 * i + 1] = (sig[i + 1], -sig[i], h[i], 1.0)
+        sched[2 * i + 2] = (sig[i + 1], -sig[i + 1], h[i], 2.0)
+    if denoise:
+        # the reverse-diffusion predictor at eps (samplers.py:209-218) with cond_ode_sampler's divisor rule for num_steps = N
+        g = np.float32(sig[N]) * _HEUN_G_FACTOR
+        sched[2 * N + 1] = (sig[N], g, (1.0 - float(eps)) / N, 4.0)
+    else:
+        sched[2 * N, 3] = 3.0
+    return t, sched.astype(np.float32)
+
+
+class HeunSampler:
+    """Fixed-step Heun solver of the probability-flow ODE, integrated in sigma: cond_edm_sampler's second-order method
+    (samplers.py:230-290) driven by the VE score model (slope d = -sigma score), state in fp32.  Deterministic, fixed NFE = 2 N (+ 1 with
+    denoise), row-local: one captured launch chain per geometry, nothing read back, the same latency on every frame; N trades accuracy for
+    time.  T0 and eps are run-time values: the schedule and the time-embedding table are device buffers refilled in stream order before a
+    replay, so a tracker that changes T0 per frame never recaptures.
+
+    B clouds in `groups` batches laid out back to back share each launch (a workgroup never straddles two of them); the result of a row
+    does not depend on its neighbours.  trunk: as PCSampler - 'bf16x9' on the chain plan by default, 'f32mfma' for A/B.  tile: forces a
+    plan (16 / 32 / 64 tiles, 128 chain form); the head-split plan, the energy model and bf16x3 have no Heun kernel."""
+
+    def __init__(self, net, B, K, nsteps, device, groups=1, grid="geometric", rho=7.0, trunk=None, tile=None, record_traj=False, denoise=True,
+                 use_graph=True):
+        import ctypes
+        if B % groups:
+            raise ValueError(f"{B} clouds do not split into {groups} equal batches")
+        if grid not in HEUN_GRIDS:
+            raise ValueError(f"heun grid {grid!r}: one of {HEUN_GRIDS}")
+        if trunk not in (None, "bf16x9", "f32mfma"):
+            raise ValueError(f"trunk {trunk!r}: 'bf16x9' or 'f32mfma'")
+        if tile and int(tile) & _lib.PLAN_HEADSPLIT:
+            raise NotImplementedError("the head-split plan has no Heun kernel: whole 16-row tiles serve such sizes (tile=16)")
+        self.net, self.B, self.K, self.n, self.groups = net, B, K, int(nsteps), groups
+        self.grid, self.rho, self.denoise = grid, float(rho), bool(denoise)
+        self.nlaunch = heun_launches(self.n, self.denoise)
+        self.dev = torch.device(device)
+        R = self.R = B * K
+        t_out = ctypes.c_int(0)
+        if _lib.lib().gp_heun_layout(int(tile or 0), groups, B // groups, K, ctypes.byref(t_out)) != 0:
+            raise ValueError(f"{B // groups} clouds x {K} candidates per batch do not split into workgroups of plan {tile or 'auto'}; "
+                             "run the batches separately")
+        self.plan = self.tile = t_out.value
+        self.trunk = None
+        if self.tile == 128:
+            self.trunk = trunk or "bf16x9"
+            if self.trunk == "bf16x9":
+                self._x9 = net.w.bf16x9_packs()
+        self.kernel_name = ("heun_step_chain_kernel<bf16x9>" if self.trunk == "bf16x9" else "heun_step_chain_kernel<2>" if self.tile == 128
+                            else f"heun_step_kernel<{self.tile}>")
+        f = lambda *s: torch.empty(*s, device=self.dev)
+        self.x, self.d, self.score, self.out = f(R, 9), f(R, 9), f(R, 9), f(R, 9)
+        self.cvec, self.centre = f(B, 768), f(B, 3)
+        self.traj = f(self.n, R, 9) if record_traj else None
+        # run-time schedule: [launches][4] + the N + 1 times, one pinned block -> one device block -> the time-embedding table
+        self._sched_len = self.nlaunch * 4
+        self._table = torch.zeros(self._sched_len + self.n + 1, device=self.dev)
+        self._table_host = torch.zeros(self._sched_len + self.n + 1).pin_memory()
+        self._table_ev = None
+        self._table_key = None
+        self.sched = self._table[: self._sched_len]
+        self.t_dev = self._table[self._sched_len:]
+        self.tvec_all = f(self.n + 1, 768)
+        self.use_graph = use_graph
+        self.graph = None
+        self.captures = 0
+        self.last_stats = {}
+
+    def _write_schedule(self, T0, eps):
+        key = (float(T0), float(eps))
+        if key != self._table_key:
+            t, sched = heun_schedule(self.n, T0, eps, self.grid, self.rho, self.denoise)
+            if self._table_ev is not None:
+                self._table_ev.synchronize()  # the previous copy out of the pinned block has completed
+            else:
+                self._table_ev = torch.cuda.Event()
+            h = self._table_host.numpy()
+            h[: self._sched_len] = sched.reshape(-1)
+            h[self._sched_len:] = t.astype(np.float32)
+            self._table.copy_(self._table_host, non_blocking=True)
+            self._table_ev.record(torch.cuda.current_stream(self.dev))
+            self.net.time_embed(self.t_dev, out=self.tvec_all)
+            self._table_key = key
+
+    def launch_step(self, l):
+        """Launch l of the chain (0 <= l < nlaunch) on the current stream."""
+        shape = (self.groups, self.B // self.groups, self.K, l, self.n, int(self.denoise))
+        bufs = (ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
+                ptr(self.traj))
+        if self.trunk == "bf16x9":
+            _lib.call("gp_heun_step_bf16x9", *shape, self.net.w.ref(), *bufs, *(ptr(w) for w in self._x9), stream_ptr())
+        else:
+            _lib.call("gp_heun_step_plan", self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
+
+    def _launch_all(self):
+        for l in range(self.nlaunch):
+            self.launch_step(l)
+
+    def run(self, cvec, centre, x0, T0=1.0, eps=EPS):
+        """cvec [B,768], centre [B,3], x0 [R,9] (the state at T0).  Returns (xs [R,N,9] or None, pose [R,9]) float32: x_1 .. x_N and the
+        final pose, rotations normalised and cloud centres added."""
+        if cvec.shape[0] != self.B or x0.shape[0] != self.R:
+            raise ValueError(f"Heun sampler set up for {self.B} clouds x {self.K} candidates got {cvec.shape[0]} clouds / {x0.shape[0]} rows")
+        self.cvec.copy_(cvec)
+        self.centre.copy_(centre)
+        self.x.copy_(x0)
+        self._write_schedule(T0, eps)
+        if not self.use_graph:
+            self._launch_all()
+        else:
+            if self.graph is None:
+                # warm-up launch outside capture (sets kernel attributes), then capture the chain once
+                self._launch_all()
+                torch.cuda.synchronize()
+                self.x.copy_(x0)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._launch_all()
+                self.captures += 1
+            self.graph.replay()
+        self.last_stats = {"nfev": self.nlaunch - 1, "plan": self.plan, "launches": self.nlaunch, "kernel": self.kernel_name}
+        xs = self.traj.permute(1, 0, 2) if self.traj is not None else None
+        return xs, self.out
 
 
 # ---------------------------------------------------------------------------------------------- PF-ODE (RK45)

@@ -402,6 +402,38 @@ int gp_pc_noise_fill(const void *seed_state, int step0, int nsteps, int64_t row0
 /* Raw Philox4x32-10 blocks (tests: bit-exactness against the published generator): counters [n][4], keys [n][2] -> out [n][4], uint32. */
 int gp_philox_raw(int64_t n, const void *counters, const void *keys, void *out, gp_stream_t s);
 
+/* FIXED-STEP HEUN SOLVER of the probability-flow ODE (opt-in).  Heun's second-order method on a sigma grid - the algorithm of
+ * cond_edm_sampler (samplers.py:230-290), which the reference wires to a decoder only - driven by the VE score model through
+ * denoised = x + sigma^2 score: slope d = -sigma score, fp32 state, no rotation renormalisation between steps, and after the last step the
+ * reverse-diffusion predictor at eps, normalize_rotation and the cloud centre of cond_ode_sampler (:209-226).  Deterministic and ROW-LOCAL
+ * (no noise, no batch statistic): a row's result does not depend on the rows that share its launch.  A solve of nsteps steps is a chain of
+ * gp_heun_launches(nsteps, denoise) = 2 nsteps + 1 (+ 1 with denoise) launches, NFE = launches - 1:
+ *     launch 0       evaluates score(x_0, t_0)
+ *     launch 2i + 1  d_i = c score -> d;  evaluates score(x_i + h d_i, t_{i+1})                                  (kind 1)
+ *     launch 2i + 2  x_{i+1} = x_i + h (0.5 d_i + 0.5 c score) -> x (and traj[i], rotation normalised, centre added);
+ *                    evaluates score(x_{i+1}, t_{i+1})                                                            (kind 2)
+ *     launch 2 nsteps      without denoise: the same update, finishes: -> out, no evaluation                      (kind 3)
+ *     launch 2 nsteps + 1  with denoise: out = normalise(x + (0 - c^2 score) h) + centre                          (kind 4)
+ * The kernels know nothing about the grid.  sched [launches][4] (device, f32): the sigma of the launch's evaluation (the score's divisor),
+ * the slope factor c, the step h, the kind as above (0 for launch 0); tvec_all [nsteps + 1][768]: gp_time_embed of t_0 .. t_nsteps (launch l
+ * evaluates at row (l + 1) / 2).  x [R,9] in / state; d, score [R,9] scratch; out [R,9]; traj [nsteps][R][9] or NULL; centre [clouds][3].
+ * Plans: 16 / 32 / 64-row tiles and the 128-row chain form (tile as in gp_pc_layout, 0 = gp_heun_layout's choice); every launch of a
+ * chain uses the same plan.  Not served: the head-split plan (GP_EINVAL; gp_heun_layout gives such sizes whole 16-row tiles), the energy
+ * model, bf16x3.  GP_EINVAL with nothing written for nsteps < 1, launch outside [0, launches), null buffers or a plan that does not fit. */
+int gp_heun_launches(int nsteps, int denoise);
+/* The plan of a Heun chain (samplers.py:230-290): gp_pc_layout's row thresholds for the score model minus head-split; tile = 0 asks for
+ * the choice, else 16 / 32 / 64 / 128.  GP_EINVAL when a workgroup of the plan would straddle two groups. */
+int gp_heun_layout(int tile, int ngroups, int nclouds_per_group, int k, int *tile_out);
+/* One launch of the chain (samplers.py:230-290) on plan `tile`; the chain plan (128) runs the fp32 MFMA chain kernel. */
+int gp_heun_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                      const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                      gp_stream_t s);
+/* The chain plan's launch (samplers.py:230-290) with the trunk as exact-product split bf16 (as gp_pc_step_bf16x9 is to gp_pc_step_plan):
+ * the same buffers, w_*_x9 as there. */
+int gp_heun_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                        const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                        const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s);
+
 /* The same launch with the batch-mean gradient norm SUPPLIED: gn_ext [nsteps][ngroups] (device) holds, for step i, the mean of
  * |score_i| over ALL rows of the batch each group belongs to.  For a batch that is sharded over several GPUs (SURVEY §8e caveat): the
  * host sums this rank's `partials` of step i, all-reduces the sum across the ranks and writes gn_ext[i] before launching step i+1, so
