@@ -29,6 +29,9 @@ DEFAULTS = dict(
     sampler_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products in the PC sampler's score network (csrc/trunk_bf16x3.hip)
     sampler_seed=None,  # (ours) an integer: opt-in seeded noise drawn inside the PC step kernels (csrc/philox.h), reproducible per row; None: torch's generator
     likelihood_divergence="hutchinson",  # (ours) 'exact': net(data, mode='likelihood') integrates the exact trace of the score Jacobian instead of the reference's one-probe Skilling-Hutchinson estimate (csrc/score_bwd.h: score_div_exact_tile) - deterministic, no prior draw
+    likelihood_solver="rk45",  # (ours) 'heun': likelihoods (mode 'likelihood', calc_likelihood, PoseNet.get_likelihood) from the fixed-step Heun solve of the exact-divergence ODE (samplers.HeunLikelihood) instead of the adaptive RK45 driver; needs likelihood_divergence / divergence 'exact' and likelihood_steps
+    likelihood_steps=None,  # (ours) N of likelihood_solver 'heun' (NFE = 2 N)
+    likelihood_grid="geometric",  # (ours) sigma grid of likelihood_solver 'heun': 'geometric' or 'edm' (heun_grid's two)
     heun_grid="geometric",  # (ours) sampler_mode ['heun'] (the fixed-step Heun solver of the probability-flow ODE, samplers.HeunSampler; sampling_steps = its N): the sigma grid - 'geometric' (t uniform) or 'edm' (cond_edm_sampler's rho = 7 discretisation)
     ode_trunk=None,  # (ours) 'bf16x9': opt-in exact-product split-bf16 trunk in the ODE sampler's chain-plan stage kernels (ODESampler(trunk=)); None / 'f32mfma': the fp32 MFMA kernels
     encoder_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products on the 128-196-256 grouping level (csrc/sa_bf16x3.hip)

@@ -108,7 +108,7 @@ def sort_sRT_by_energy(sRT, energy=None, RT_overlaps=None, ranker="energy_ranker
     m = max(1, int(K * ratio))
     if n == 0:
         return sRT[:, :m], None, None
-    if ranker == "energy_ranker":
+    if ranker in ("energy_ranker", "likelihood_ranker"):  # 'likelihood_ranker' (ours): rank by the array passed in `energy` (log-likelihoods in both columns)
         e = energy
     elif ranker == "gt_ranker":
         e = -np.min(RT_overlaps, axis=1)

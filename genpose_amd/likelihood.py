@@ -11,12 +11,15 @@ one status word per replayed chunk of attempts.
 divergence='exact' (ours; not in the reference): the same ODE with the exact trace tr(d score / d x) = sum_i (e_i^T J)_i in place of the
 one-probe estimate - nine unit seeds per row behind one forward pass (csrc/score_bwd.h: score_div_exact_tile; RK45 model
 'likelihood_exact').  The likelihood is then a deterministic function of (cloud, pose): no probe, no draw.
+
+solver='heun' (ours): the same exact-divergence ODE by Heun's method on a fixed sigma grid instead of the adaptive driver
+(samplers.HeunLikelihood, csrc/heun_likelihood.hip): 2 N evaluations in one captured launch chain, nothing read back, row-local.
 """
 import math
 
 import torch
 
-from .samplers import ODESampler
+from .samplers import HeunLikelihood, ODESampler
 from .sde import SIGMA_MAX
 
 
@@ -36,17 +39,48 @@ def solver_model(divergence):
     return DIVERGENCES[divergence]
 
 
-def cond_ode_likelihood(net, cvec, k, x, epsilon=None, eps=1e-5, rtol=1e-5, atol=1e-5, stats=None, solver=None, divergence="hutchinson"):
+SOLVERS = ("rk45", "heun")
+
+
+def cond_ode_likelihood(net, cvec, k, x, epsilon=None, eps=1e-5, rtol=1e-5, atol=1e-5, stats=None, solver=None, divergence="hutchinson", steps=None,
+                        grid="geometric"):
     """net: ScoreNetHIP; cvec [B,768] (gp_cloud_embed); x [B*k,9] poses whose likelihood is wanted; epsilon [B*k,9] the fixed
-    Hutchinson probe (the reference draws it from the prior, samplers.py:39).  Returns (z [R,9] f64, log-likelihood in bits [R] f64)
-    on the device.  solver: an ODESampler of the right shape and model to reuse (buffers, captured attempts).
-    divergence: 'hutchinson' (default: the reference's estimator, needs epsilon) or 'exact' (the trace itself; epsilon must be None)."""
+    Hutchinson probe (the reference draws it from the prior, samplers.py:39).  Returns (z [R,9], log-likelihood in bits [R] f64)
+    on the device (z: f64 under 'rk45', the solver's f32 state under 'heun').
+    divergence: 'hutchinson' (default: the reference's estimator, needs epsilon) or 'exact' (the trace itself; epsilon must be None).
+    solver: 'rk45' (default, also None: the adaptive Dormand-Prince driver at rtol / atol), 'heun' (ours: the fixed-step Heun solve in
+    sigma, samplers.HeunLikelihood - `steps` = its N, `grid` its sigma grid; needs divergence='exact'; rtol / atol are not used; row-local:
+    a row's value does not depend on the other rows of the call), or a solver OBJECT of the right shape to reuse (buffers, captured
+    launches): an ODESampler of the right model, or a HeunLikelihood (its own steps and grid hold).
+    stats: 'nfev' (heun: 2 N) and 'attempts' (heun: N, the steps)."""
     model = solver_model(divergence)
+    if solver is None or isinstance(solver, str):
+        method, solver = ("rk45" if solver is None else solver), None
+        if method not in SOLVERS:
+            raise NotImplementedError(f"likelihood solver {method!r}: one of {SOLVERS}")
+    else:
+        method = "heun" if isinstance(solver, HeunLikelihood) else "rk45"
+    if method == "heun" and divergence != "exact":
+        raise NotImplementedError(f"solver='heun' with divergence={divergence!r}: the fixed-step solve integrates the exact trace only "
+                                  "(divergence='exact'); the one-probe estimate keeps solver='rk45'")
     if divergence == "exact" and epsilon is not None:
         raise ValueError("divergence='exact' takes no probe (epsilon=None): the trace is computed, not estimated")
     if divergence == "hutchinson" and epsilon is None:
         raise ValueError("divergence='hutchinson' needs the probe epsilon [B*k,9]")
     B = cvec.shape[0]
+    if method == "heun":
+        if solver is None:
+            if steps is None:
+                raise ValueError("solver='heun' needs steps= (the number of Heun steps N; NFE = 2 N)")
+            solver = HeunLikelihood(net, B, k, cvec.device, int(steps), grid=grid)
+        elif steps is not None and int(steps) != solver.n:
+            raise RuntimeError(f"HeunLikelihood of {solver.n} steps given for steps={steps}")
+        z, delta_logp = solver.run(cvec, x.float().contiguous(), eps=eps)
+        nll = (global_prior_likelihood(z.double(), SIGMA_MAX) + delta_logp) / math.log(2)
+        if stats is not None:
+            stats["nfev"] = int(solver.last_stats["nfev"])
+            stats["attempts"] = int(solver.n)
+        return z.clone(), nll
     if solver is None:
         solver = ODESampler(net, B, k, cvec.device, model=model)
     elif solver.model != ODESampler.MODELS[model]:

@@ -263,11 +263,14 @@ class FullPipelinePredictor:
     score_agent / energy_agent : genpose_amd.posenet_agent.PoseNet with weights loaded (sampler_mode ['pc'] on the score agent)
     """
 
-    def __init__(self, score_agent, energy_agent, B, K, num_steps, ratio=0.6, T_energy=1e-5, overlap=True, batches_per_launch=1):
+    def __init__(self, score_agent, energy_agent, B, K, num_steps, ratio=0.6, T_energy=1e-5, overlap=True, batches_per_launch=1, ranker="energy"):
         """batches_per_launch = G (run_many): G consecutive batches of B clouds share every encoder pass, the sampler launch chain
         (each batch keeps its own batch-global coupling, gp_pc_step_grouped), the energy evaluation and the ranking launch - the
         request batching of PipelinedPCPredictor applied to the whole pipeline.  At B = 256 one batch is 400 32-row tiles = 1.56 rounds
         of the CUs (the second round 56 % full); five batches are 2000 tiles = 7.8 rounds."""
+        if ranker != "energy":
+            raise NotImplementedError(f"FullPipelinePredictor(ranker={ranker!r}): this pipeline overlaps the ENERGY model's encoder with the sampler and "
+                                      "ranks by its energies only; the likelihood ranker lives in SingleFrameRunner(ranker='likelihood')")
         _lib.check_device()
         self.snet, self.enet = score_agent.net, energy_agent.net
         for net in (self.snet, self.enet):

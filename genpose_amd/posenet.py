@@ -256,13 +256,29 @@ class GFObjectPose:
             return out
         raise NotImplementedError(sampler)
 
-    def calc_likelihood(self, data, atol=1e-5, rtol=1e-5, divergence="hutchinson"):
+    def calc_likelihood(self, data, atol=1e-5, rtol=1e-5, divergence="hutchinson", solver=None, steps=None):
         """posenet.py:133-147: log-likelihood (bits) of data['sampled_pose'] under the score model, one probe per row drawn from
         the prior.  data['pts_feat'] must be there (mode 'pts_feature').
         divergence='exact' (ours): the exact trace instead of the one-probe estimate - no prior draw (prior_fn is not called, the CPU
-        generator does not move), a deterministic function of (cloud, pose)."""
-        from .likelihood import cond_ode_likelihood, solver_model
+        generator does not move), a deterministic function of (cloud, pose).
+        solver / steps (ours; None: cfg.likelihood_solver / cfg.likelihood_steps): 'rk45' the adaptive driver, 'heun' the fixed-step Heun
+        solve of the exact-divergence ODE on cfg.likelihood_grid (samplers.HeunLikelihood: 2 x steps evaluations, row-local; atol / rtol unused)."""
+        from .likelihood import SOLVERS, cond_ode_likelihood, solver_model
+        from .samplers import HeunLikelihood
         model = solver_model(divergence)
+        solver = getattr(self.cfg, "likelihood_solver", "rk45") if solver is None else solver
+        steps = getattr(self.cfg, "likelihood_steps", None) if steps is None else steps
+        grid = getattr(self.cfg, "likelihood_grid", "geometric")
+        if solver not in SOLVERS:
+            raise NotImplementedError(f"likelihood solver {solver!r}: one of {SOLVERS}")
+        if solver == "heun":
+            # what the fixed-step solve cannot serve is said before anything is computed
+            if divergence != "exact":
+                raise NotImplementedError(f"solver='heun' with divergence={divergence!r}: the fixed-step solve integrates the exact trace only (divergence='exact')")
+            if steps is None:
+                raise ValueError("solver='heun' needs steps= or cfg.likelihood_steps (the number of Heun steps N)")
+            if grid not in HEUN_GRIDS:
+                raise ValueError(f"likelihood_grid {grid!r}: one of {HEUN_GRIDS}")
         self._need_weights()
         if self.cfg.posenet_mode != "score":
             raise NotImplementedError("likelihoods come from the score model")
@@ -270,12 +286,18 @@ class GFObjectPose:
         x = data["sampled_pose"].float().contiguous()
         epsilon = self.prior_fn((x.shape[0], 9)).to(self.device) if divergence == "hutchinson" else None
         self.last_likelihood_stats = {}
-        key = ("likelihood", cvec.shape[0], K) if divergence == "hutchinson" else ("likelihood", cvec.shape[0], K, divergence)
-        solver = self._samplers.get(key)
-        if solver is None:
-            solver = self._samplers[key] = ODESampler(self.pose_score_net, cvec.shape[0], K, self.device, model=model)
+        if solver == "heun":
+            key = ("likelihood", cvec.shape[0], K, divergence, solver, int(steps), grid)
+            smp = self._samplers.get(key)
+            if smp is None:
+                smp = self._samplers[key] = HeunLikelihood(self.pose_score_net, cvec.shape[0], K, self.device, int(steps), grid=grid)
+        else:
+            key = ("likelihood", cvec.shape[0], K) if divergence == "hutchinson" else ("likelihood", cvec.shape[0], K, divergence)
+            smp = self._samplers.get(key)
+            if smp is None:
+                smp = self._samplers[key] = ODESampler(self.pose_score_net, cvec.shape[0], K, self.device, model=model)
         _, ll = cond_ode_likelihood(self.pose_score_net, cvec, K, x, epsilon, eps=self.sampling_eps, rtol=rtol, atol=atol,
-                                    stats=self.last_likelihood_stats, solver=solver, divergence=divergence)
+                                    stats=self.last_likelihood_stats, solver=smp, divergence=divergence)
         return ll
 
     @staticmethod
@@ -313,7 +335,7 @@ class GFObjectPose:
             sigma = (SIGMA_MIN * (SIGMA_MAX / SIGMA_MIN) ** t0).contiguous()
             return self.pose_score_net.evaluate(cvec, K, data["sampled_pose"].float().contiguous(), tvec[0], sigma, mode)
         if mode == "likelihood":
-            return self.calc_likelihood(data, divergence=getattr(self.cfg, "likelihood_divergence", "hutchinson"))
+            return self.calc_likelihood(data, divergence=getattr(self.cfg, "likelihood_divergence", "hutchinson"))  # solver / steps: cfg.likelihood_*
         if mode == "pc_sample":
             return self.sample(data, "pc", init_x=init_x)
         if mode == "ode_sample":

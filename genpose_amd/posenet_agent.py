@@ -93,14 +93,19 @@ class PoseNet:
             return pred_pose
 
     # ------------------------------------------------------------------ likelihood of candidate poses (ours; beside get_energy)
-    def get_likelihood(self, data, pose_samples, extract_pts_feature=True, atol=1e-5, rtol=1e-5):
+    def get_likelihood(self, data, pose_samples, extract_pts_feature=True, atol=1e-5, rtol=1e-5, solver=None, steps=None):
         """pose_samples [B,K,9] (the layout pred_func returns) -> [B,K] log-likelihood in bits (float64) under the SCORE model, from the
         likelihood ODE with the exact divergence (GFObjectPose.calc_likelihood(divergence='exact')): deterministic, no probe, no energy
         model.  The translation is re-centred by data['pts_center'] as get_energy re-centres it.  Fed as both columns of the [n,K,2]
         energy array it drives the existing ranking (reward.sort_poses_by_energy / gp_rank_aggregate): higher = more likely = first.
-        Deterministic means: the same call returns the same bits.  All B*K rows of a call share ONE adaptive step sequence and one error
-        norm (as in the reference's solve), so a candidate's value depends, within rtol / atol, on the other candidates of the call: compare
-        candidates of one call, and tighten rtol / atol where values of different calls are set side by side."""
+        Deterministic means: the same call returns the same bits.
+        solver / steps (None: cfg.likelihood_solver / cfg.likelihood_steps):
+          'rk45'  all B*K rows of a call share ONE adaptive step sequence and one error norm (as in the reference's solve), so a candidate's
+                  value depends, within rtol / atol, on the other candidates of the call: compare candidates of one call, and tighten rtol /
+                  atol where values of different calls are set side by side;
+          'heun'  the fixed-step Heun solve (samplers.HeunLikelihood, `steps` = N, 2 N evaluations, atol / rtol unused): row-local - a
+                  candidate's value no longer depends on the rest of the call; it is a function of (cloud, pose, N, grid) alone, bit for bit,
+                  so values of different calls can be set side by side."""
         self.is_testing = True
         self.net.eval()
         bs, repeat_num = pose_samples.shape[0], pose_samples.shape[1]
@@ -109,7 +114,7 @@ class PoseNet:
             pose = pose_samples.clone().view(bs * repeat_num, -1).type_as(pts_feat)
             pose[:, -3:] -= data["pts_center"].unsqueeze(1).repeat(1, repeat_num, 1).view(bs * repeat_num, -1)
             rows = {"pts_feat": pts_feat, "sampled_pose": pose, "_repeat": repeat_num}
-            return self.net.calc_likelihood(rows, atol=atol, rtol=rtol, divergence="exact").reshape(bs, repeat_num)
+            return self.net.calc_likelihood(rows, atol=atol, rtol=rtol, divergence="exact", solver=solver, steps=steps).reshape(bs, repeat_num)
 
     # ------------------------------------------------------------------ energy (posenet_agent.py:471-527)
     def get_energy(self, data, pose_samples, T=None, mode="test", extract_pts_feature=True):

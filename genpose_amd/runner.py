@@ -36,10 +36,18 @@ class _one_cpu_thread:
 
 
 class SingleFrameRunner:
-    """inference_pose + inference_energy (evaluation_single.py:356-489) without the pickle round trip in between."""
+    """inference_pose + inference_energy (evaluation_single.py:356-489) without the pickle round trip in between.
 
-    def __init__(self, score_agent, energy_agent=None, repeat_num=50, T0=0.55, batch_size=256, ratio=0.6):
-        self.score_agent, self.energy_agent = score_agent, energy_agent
+    ranker: 'energy' (default: the energy agent's two energies rank the hypotheses, as the reference) or 'likelihood' (ours: the SCORE
+    agent's own exact-divergence log-likelihood, PoseNet.get_likelihood under the agent's cfg.likelihood_solver / likelihood_steps, fills
+    both columns of the [n,K,2] array, cast to float32, and goes through the same ranking - no energy agent needed)."""
+
+    RANKERS = ("energy", "likelihood")
+
+    def __init__(self, score_agent, energy_agent=None, repeat_num=50, T0=0.55, batch_size=256, ratio=0.6, ranker="energy"):
+        if ranker not in self.RANKERS:
+            raise NotImplementedError(f"ranker {ranker!r}: one of {self.RANKERS}")
+        self.score_agent, self.energy_agent, self.ranker = score_agent, energy_agent, ranker
         self.repeat_num, self.T0, self.batch_size, self.ratio = repeat_num, T0, batch_size, ratio
 
     def infer_tensors(self, clouds):
@@ -51,8 +59,13 @@ class SingleFrameRunner:
             pred = self.score_agent.pred_func(data=sample, repeat_num=self.repeat_num, save_path=None, T0=self.T0)
             out["pred_pose"].append(pred)
             out["multi_hypothesis_pred_RTs"].append(rotation.pose9_to_RT(pred))
-            if self.energy_agent is not None:
-                energy = self.energy_agent.get_energy(data=sample, pose_samples=pred, T=1e-5)  # evaluation_single.py:339-343
+            if self.ranker == "likelihood" or self.energy_agent is not None:
+                if self.ranker == "likelihood":
+                    # (pred_func left the clouds' features in the dict) higher = more likely = first, in both columns
+                    ll32 = self.score_agent.get_likelihood(sample, pred, extract_pts_feature=False).float()
+                    energy = torch.stack([ll32, ll32], dim=-1).contiguous()
+                else:
+                    energy = self.energy_agent.get_energy(data=sample, pose_samples=pred, T=1e-5)  # evaluation_single.py:339-343
                 r = reward.rank_aggregate(pred, energy, ratio=self.ratio)
                 out["energy"].append(energy)
                 out["sorted_RTs"].append(rotation.pose9_to_RT(r["sorted_poses"]))
@@ -72,7 +85,10 @@ class SingleFrameRunner:
         instance's K hypotheses (ranked by energy, as pred_energy_batch stores them) and energies in place, then computes mAP
         with the reference's threshold grids.  Returns (iou_aps, pose_aps, iou_acc, pose_acc, store)."""
         from . import evaluation
-        if self.energy_agent is None:
+        if self.ranker == "likelihood":
+            if ranker == "energy_ranker":
+                ranker = "likelihood_ranker"  # the array stored as 'energy' holds the log-likelihoods: ranked as it stands
+        elif self.energy_agent is None:
             raise ValueError("evaluation needs the energy agent (hypotheses are ranked by energy)")
         store = evaluation.DetectionResults(detect_result, self.repeat_num)
         for cat in store.by_category:
@@ -238,7 +254,10 @@ class TrackingRunner:
     (_FrameGraphs) - same kernels, same results as the agents' pred_func -> get_energy -> rank_aggregate called one after the other
     (use_graphs=False), a third fewer microseconds per frame at tracking sizes, where launch overhead dominates."""
 
-    def __init__(self, score_agent, energy_agent, repeat_num=50, T0=0.15, ratio=0.6, use_graphs=True):
+    def __init__(self, score_agent, energy_agent, repeat_num=50, T0=0.15, ratio=0.6, use_graphs=True, ranker="energy"):
+        if ranker != "energy":
+            raise NotImplementedError(f"TrackingRunner(ranker={ranker!r}): tracking ranks by the energy model only; the likelihood ranker "
+                                      "(SingleFrameRunner(ranker='likelihood')) is not wired into the frame loop")
         self.score_agent, self.energy_agent = score_agent, energy_agent
         self.repeat_num, self.T0, self.ratio = repeat_num, T0, ratio
         self.buffer = {"model_name": [], "pred_sRT": None}

@@ -433,6 +433,117 @@ class HeunSampler:
         return xs, self.out
 
 
+# ---------------------------------------------------------------------------------------------- likelihood ODE (fixed-step Heun)
+def heun_likelihood_launches(nsteps):
+    """Launches of a Heun likelihood chain (gp_heun_likelihood_launches): 2 N + 1.  NFE = 2 N."""
+    if int(nsteps) < 1:
+        raise ValueError(f"nsteps {nsteps}: at least one step")
+    return 2 * int(nsteps) + 1
+
+
+def heun_likelihood_schedule(nsteps, eps=EPS, T=1.0, grid="geometric", rho=7.0):
+    """Host schedule of a Heun solve of the likelihood ODE, which runs from eps UP to T: (t [N+1] f64 ascending, sched [2N+1,4] f32).  The
+    times are heun_grid's points in ascending order (they end exactly at eps and T); per launch the sigma of its evaluation, the factor
+    c = -sigma, the step h = sigma_{i+1} - sigma_i > 0 and the launch kind (include/genpose_hip.h: gp_heun_likelihood_step), computed in
+    float64 and rounded once."""
+    N = int(nsteps)
+    t, sig = heun_grid(N, T, eps, grid, rho)
+    t, sig = np.ascontiguousarray(t[::-1]), np.ascontiguousarray(sig[::-1])
+    h = sig[1:] - sig[:-1]
+    sched = np.zeros((heun_likelihood_launches(N), 4), dtype=np.float64)
+    sched[0] = (sig[0], 0.0, 0.0, 0.0)
+    for i in range(N):
+        sched[2 * i + 1] = (sig[i + 1], -sig[i], h[i], 1.0)
+        sched[2 * i + 2] = (sig[i + 1], -sig[i + 1], h[i], 2.0)
+    sched[2 * N, 3] = 3.0
+    return t, sched.astype(np.float32)
+
+
+class HeunLikelihood:
+    """Fixed-step Heun solve of the likelihood ODE with the exact divergence (cond_ode_likelihood's system, samplers.py:22-99), integrated
+    in sigma from sigma(eps) up to sigma(T) on heun_schedule's grids: x and the slopes in fp32, the log-density change in float64
+    (csrc/heun_likelihood.hip).  Deterministic, fixed NFE = 2 N, ROW-LOCAL: the value of (cloud, pose) is a function of (cloud, pose, N, grid,
+    eps) alone, bit for bit, whatever else shares the call.  One captured chain of 2 N + 1 launches per geometry, nothing read back; eps is a
+    run-time value (the schedule and the time-embedding table are device buffers refilled in stream order), so a new eps never recaptures.
+    16-row tiles only."""
+
+    def __init__(self, net, B, K, device, nsteps, grid="geometric", rho=7.0, use_graph=True):
+        if grid not in HEUN_GRIDS:
+            raise ValueError(f"heun grid {grid!r}: one of {HEUN_GRIDS}")
+        self.net, self.B, self.K, self.n = net, B, K, int(nsteps)
+        self.grid, self.rho = grid, float(rho)
+        self.nlaunch = heun_likelihood_launches(self.n)
+        self.dev = torch.device(device)
+        R = self.R = B * K
+        self.kernel_name = "heun_likelihood_step_kernel"
+        f = lambda *s: torch.empty(*s, device=self.dev)
+        self.x, self.d, self.score, self.div, self.z = f(R, 9), f(R, 10), f(R, 9), f(R), f(R, 9)
+        self.logp = torch.zeros(R, dtype=torch.float64, device=self.dev)
+        self.cvec = f(B, 768)
+        # run-time schedule: [launches][4] + the N + 1 times, one pinned block -> one device block -> the time-embedding table
+        self._sched_len = self.nlaunch * 4
+        self._table = torch.zeros(self._sched_len + self.n + 1, device=self.dev)
+        self._table_host = torch.zeros(self._sched_len + self.n + 1).pin_memory()
+        self._table_ev = None
+        self._table_key = None
+        self.sched = self._table[: self._sched_len]
+        self.t_dev = self._table[self._sched_len:]
+        self.tvec_all = f(self.n + 1, 768)
+        self.use_graph = use_graph
+        self.graph = None
+        self.captures = 0
+        self.last_stats = {}
+
+    def _write_schedule(self, eps, T):
+        key = (float(eps), float(T))
+        if key != self._table_key:
+            t, sched = heun_likelihood_schedule(self.n, eps, T, self.grid, self.rho)
+            if self._table_ev is not None:
+                self._table_ev.synchronize()  # the previous copy out of the pinned block has completed
+            else:
+                self._table_ev = torch.cuda.Event()
+            h = self._table_host.numpy()
+            h[: self._sched_len] = sched.reshape(-1)
+            h[self._sched_len:] = t.astype(np.float32)
+            self._table.copy_(self._table_host, non_blocking=True)
+            self._table_ev.record(torch.cuda.current_stream(self.dev))
+            self.net.time_embed(self.t_dev, out=self.tvec_all)
+            self._table_key = key
+
+    def launch_step(self, l):
+        """Launch l of the chain (0 <= l < nlaunch) on the current stream."""
+        _lib.call("gp_heun_likelihood_step", self.B, self.K, l, self.n, self.net.w.ref(), ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched),
+                  ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.div), ptr(self.logp), ptr(self.z), stream_ptr())
+
+    def _launch_all(self):
+        for l in range(self.nlaunch):
+            self.launch_step(l)
+
+    def run(self, cvec, x, eps=EPS, T=1.0):
+        """cvec [B,768], x [R,9] (the poses whose likelihood is wanted, the state at eps).  Returns (z [R,9] f32: x at T, delta_logp [R] f64)
+        on the device - the solver's own buffers, which the next run overwrites."""
+        if cvec.shape[0] != self.B or x.shape[0] != self.R:
+            raise ValueError(f"Heun likelihood solver set up for {self.B} clouds x {self.K} candidates got {cvec.shape[0]} clouds / {x.shape[0]} rows")
+        self.cvec.copy_(cvec)
+        self.x.copy_(x)
+        self._write_schedule(eps, T)
+        if not self.use_graph:
+            self._launch_all()
+        else:
+            if self.graph is None:
+                # warm-up launch outside capture (sets kernel attributes), then capture the chain once
+                self._launch_all()
+                torch.cuda.synchronize()
+                self.x.copy_(x)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._launch_all()
+                self.captures += 1
+            self.graph.replay()
+        self.last_stats = {"nfev": self.nlaunch - 1, "launches": self.nlaunch, "kernel": self.kernel_name, "n_attempts": self.n}
+        return self.z, self.logp
+
+
 # ---------------------------------------------------------------------------------------------- PF-ODE (RK45)
 _STATE_FIELDS = ("t", "h_abs", "status", "n_attempts", "n_accepted", "nfev", "err_norm", "log_t", "log_h", "log_err", "log_acc",
                  "stage_t", "last_accepted")

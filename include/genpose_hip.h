@@ -434,6 +434,28 @@ int gp_heun_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, i
                         const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                         const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s);
 
+/* FIXED-STEP HEUN SOLVE OF THE EXACT-LIKELIHOOD ODE (opt-in; csrc/heun_likelihood.hip).  cond_ode_likelihood's system (samplers.py:22-99)
+ * d[x; logp]/dt = -g^2/2 [score; div_x score] with the exact divergence of gp_score_div_exact, integrated in sigma from sigma(eps) UP to
+ * sigma(T) by Heun's method on a fixed grid (-g^2/2 dt = -sigma dsigma: slope d = -sigma [score; div]).  x and the slopes are fp32, the
+ * log-density change is accumulated in float64; no rotation renormalisation, no denoise step, no centre.  Deterministic and ROW-LOCAL: the
+ * result of a row is a function of its cloud, its pose and the schedule alone, whatever rows share the launch.  A solve of nsteps steps is
+ * a chain of gp_heun_likelihood_launches(nsteps) = 2 nsteps + 1 launches, NFE = 2 nsteps (stream order is the only synchronisation):
+ *     launch | update from the stored score / div                      | stores        | evaluates
+ *     0      | -                                                       | -             | (x_0, t_0)
+ *     2i + 1 | d = c (score, div), c = -sigma_i                        | d [R,10]      | (x_i + h_i d[x], t_{i+1})      (kind 1)
+ *     2i + 2 | x, l += h_i (0.5 d + 0.5 c (score, div)), c = -sigma_{i+1} | x, logp    | (x_{i+1}, t_{i+1})             (kind 2)
+ *     2N     | the same update                                         | z_out, logp   | nothing                        (kind 3)
+ * The kernel knows nothing about the grid.  sched [launches][4] (device, f32): the sigma of the launch's evaluation (the divisor of score and
+ * div), the factor c, the step h = sigma_{i+1} - sigma_i > 0, the kind as above (0 for launch 0); tvec_all [nsteps + 1][768]: gp_time_embed of
+ * the ascending times t_0 = eps .. t_nsteps = T (launch l evaluates at row (l + 1) / 2).  x [R,9] in / state; d [R,10], score [R,9], div [R]
+ * scratch; logp [R] f64: the log-density change, l_0 = 0 is part of the chain (launch 2 does not read it); z_out [R,9]: x at T.
+ * 16-row tiles only.  GP_EINVAL with nothing written for null buffers, k <= 0, nsteps < 1, launch outside [0, launches) or a net without
+ * the transposed packs; R == 0: GP_OK.  Stateless, capturable. */
+int gp_heun_likelihood_launches(int nsteps);
+/* One launch of that chain (samplers.py:22-99; the table above). */
+int gp_heun_likelihood_step(int nclouds, int k, int launch, int nsteps, const gp_scorenet *net, const float *cvec, const float *tvec_all,
+                            const float *sched, float *x, float *d, float *score, float *div, double *logp, float *z_out, gp_stream_t s);
+
 /* The same launch with the batch-mean gradient norm SUPPLIED: gn_ext [nsteps][ngroups] (device) holds, for step i, the mean of
  * |score_i| over ALL rows of the batch each group belongs to.  For a batch that is sharded over several GPUs (SURVEY §8e caveat): the
  * host sums this rank's `partials` of step i, all-reduces the sum across the ranks and writes gn_ext[i] before launching step i+1, so
