@@ -17,7 +17,8 @@ using namespace gp_trunk;
 struct SplitNet {
     const bf16x8 *w0;  // pose_encoder.0 [1][16][NTERM][64]   k = component index (natural order, zero padded to 32)
     const bf16x8 *w2;  // pose_encoder.2 [8][16][NTERM][64]   k order of the register chain
-    const bf16x8 *wh;  // stacked heads  [8][48][NTERM][64]
+    const bf16x8 *wh;  // stacked heads  NTERM = 2: [8][48][NTERM][64] (k-block, output chunk);  NTERM = 3: [3][8][2][8][NTERM][64]
+                       // (head, chunk pair, chunk of the pair, k-block) - the order trunk_bf16x9.h consumes (weights.pack_heads_bf16x9)
     const float *b0, *b2, *w_out, *b_out;  // fp32: biases [256], [256]; output layers [9][256], [9]
 };
 
@@ -27,7 +28,7 @@ constexpr int NCL = 4;       // clouds a workgroup's 128 rows may span (gp_pc_la
 // LDS (floats): ring [SLOTS][SLICE] bf16x8 | w_out [9][256] | b0 [256] | b2 [256] | cvt [NCL][768] = cvec[cloud] + tvec
 template <int NTERM, int SLOTS>
 struct SplitLds {
-    static constexpr int SLICE = 16 * NTERM * 64;  // bf16x8 (16 B) per slice = (one 32-wide k-block) x (16 output chunks) x NTERM terms
+    static constexpr int SLICE = 16 * NTERM * 64;  // bf16x8 (16 B) per slice = 16 (k-block, output chunk) sub-blocks x NTERM terms
     static constexpr int OFF_WOUT = SLOTS * SLICE * 4, OFF_B0 = OFF_WOUT + POSE * HID, OFF_B2 = OFF_B0 + HID, OFF_CVT = OFF_B2 + HID,
                          TOTAL = OFF_CVT + NCL * HEADS;
     static constexpr size_t BYTES = (size_t)TOTAL * sizeof(float);
@@ -39,6 +40,7 @@ __device__ __forceinline__ const bf16x8 *split_slice(const SplitNet &w, int s) {
     s = s < NSLICES ? s : NSLICES - 1;  // the ring runs ahead: requests past the end re-read the last slice (never used)
     if (s == 0) return w.w0;
     if (s <= 8) return w.w2 + (size_t)(s - 1) * (16 * NTERM * 64);
+    if constexpr (NTERM == 3) return w.wh + (size_t)(s - 9) * (16 * NTERM * 64);  // chunk-major: slice (head, chunk pair) as consumed
     const int h = (s - 9) >> 3, kb = (s - 9) & 7;
     return w.wh + ((size_t)kb * 48 + 16 * h) * NTERM * 64;
 }

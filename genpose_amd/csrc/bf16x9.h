@@ -39,16 +39,18 @@ __device__ __forceinline__ Split8 split8(const f32x4 a, const f32x4 b) {
 // (lo.lo; lo.mid, mid.lo; lo.hi, mid.mid, hi.lo; mid.hi, hi.mid; hi.hi), so the small terms meet the accumulator before the large
 // ones; the tiles are interleaved product by product (independent accumulation chains for the pipe).
 // TRANSPOSED: acc[p] += X[p] . W, the activations as the A operand - the same nine products in the same order.
+// `first`: acc[p] = W . X[p] - the first product starts from a literal-zero C operand (the bits of 0 + product), no zeroed registers.
 template <int NT, bool TRANSPOSED = false>
-__device__ __forceinline__ void mma9(const bf16x8 (&w)[3], const Split8 (&x)[NT], f32x4 (&acc)[NT]) {
+__device__ __forceinline__ void mma9(const bf16x8 (&w)[3], const Split8 (&x)[NT], f32x4 (&acc)[NT], bool first = false) {
     constexpr int WA[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0};  // term of W
     constexpr int XB[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0};  // term of X
 #pragma unroll
     for (int q = 0; q < 9; ++q)
 #pragma unroll
         for (int p = 0; p < NT; ++p) {
-            if constexpr (TRANSPOSED) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[p].t[XB[q]], w[WA[q]], acc[p], 0, 0, 0);
-            else acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[WA[q]], x[p].t[XB[q]], acc[p], 0, 0, 0);
+            const f32x4 c = first && q == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[p];
+            if constexpr (TRANSPOSED) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[p].t[XB[q]], w[WA[q]], c, 0, 0, 0);
+            else acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[WA[q]], x[p].t[XB[q]], c, 0, 0, 0);
         }
 }
 
@@ -65,9 +67,10 @@ __device__ __forceinline__ void ring_barrier() {
 // of acc), the three weight terms (read one chunk ahead) x the two row tiles' split k-block = 18 MFMAs; beside chunk n < PER_T, element
 // n of the next slice goes from the registers (`hold`, requested a step ago) to the other slot `dst` (last read one step ago) and
 // element n of the slice after it, `src`, is requested; one barrier.  The caller keeps the ring's position and names the three slices.
+// `first`: the step opens its accumulators (acc = W . X, mma9).
 template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NA>
 __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], const Split8 (&xs)[2],
-                                          f32x4 (&acc)[2][NA], int tid, int lane) {
+                                          f32x4 (&acc)[2][NA], int tid, int lane, bool first = false) {
     static_assert(NCH >= PER_T && N0 + NCH <= NA, "every slice element moves beside a chunk");
     bf16x8 wf[2][3];
 #pragma unroll
@@ -83,11 +86,51 @@ __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const
             hold[n] = src[tid + n * NTH];
         }
         f32x4 an[2] = {acc[0][N0 + n], acc[1][N0 + n]};
-        mma9<2, TRANSPOSED>(wf[n & 1], xs, an);
+        mma9<2, TRANSPOSED>(wf[n & 1], xs, an, first);
         acc[0][N0 + n] = an[0], acc[1][N0 + n] = an[1];
         __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the step
     }
     ring_barrier();
+}
+
+// Half a step of the same ring over a CHUNK-MAJOR slice = (two output chunks) x (KB k-blocks) x (hi, mid, lo): chunk C of the slice in
+// `slot` against the KB split k-blocks of the whole input, acc[p] = sum over kb ascending of W[C][kb] . X[kb][p] - each accumulator takes
+// its k-blocks in the order of the k-major step, from a literal zero.  Sub-block u = C KB + kb: the weight terms of u + 1 are read, element
+// u < PER_T of the next slice moves and the slice after it is requested as in ring_step, and `side(kb)` is the caller's piece of other
+// work for this sub-block (an epilogue of accumulators that are already final); the sub-block's 18 MFMAs take at most two other
+// instructions behind each, so what side() adds goes BETWEEN them (trunk_chain.h's placement: one wave per SIMD, nothing else fills a
+// burst).  Chunk 0 reads chunk 1's first weight terms ahead into `w1`; the barrier follows chunk 1.
+template <int NTH, int PER_T, int KB, int C, class Side>
+__device__ __forceinline__ void ring_half_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], bf16x8 (&w1)[3],
+                                               const Split8 (&xs)[KB][2], f32x4 (&acc)[2], int tid, int lane, Side side) {
+    static_assert(C == 0 || C == 1, "two chunks per slice");
+    bf16x8 wf[2][3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) wf[0][t] = C == 0 ? slot[t * 64 + lane] : w1[t];
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+        const int u = C * KB + kb;
+        if (kb + 1 < KB) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) wf[(kb + 1) & 1][t] = slot[((u + 1) * 3 + t) * 64 + lane];
+        } else if (C == 0) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) w1[t] = slot[((u + 1) * 3 + t) * 64 + lane];
+        }
+        if (u < PER_T) {
+            dst[tid + u * NTH] = hold[u];
+            hold[u] = src[tid + u * NTH];
+        }
+        side(kb);
+        mma9<2>(wf[kb & 1], xs[kb], acc, kb == 0);
+#pragma unroll
+        for (int i = 0; i < 18; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);  // VALU | SALU | VMEM | DS
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (C == 1) ring_barrier();
 }
 
 }  // namespace gp_bf16x9

@@ -9,19 +9,22 @@
 //
 // Form: 4 waves per workgroup (one per SIMD, the whole 512-entry register file), each carrying TWO 16-row B tiles = 32 rows, 128 rows
 // per workgroup, one workgroup per CU.  The D fragment of a layer is the next layer's B operand (two chunks per k-block of
-// v_mfma_f32_16x16x32_bf16); activations stay in fp32 registers and are split into hi / mid / lo one k-block at a time.  All weights
-// stream through a 2-slot LDS ring in 33 slices of 48 KB = (one 32-wide k-block) x (16 output chunks) x (hi, mid, lo): pose_encoder.0
-// (1), pose_encoder.2 (8), three heads (8 each); slice s + 1 (held in registers since step s - 1) is written into the other slot while
-// slot s is multiplied, slice s + 2 is requested, one barrier per slice.
+// v_mfma_f32_16x16x32_bf16).  All weights stream through a 2-slot LDS ring in 33 slices of 48 KB: pose_encoder.0 (1) and pose_encoder.2
+// (8) as (one 32-wide k-block) x (16 output chunks) x (hi, mid, lo), the fp32 activations split one k-block at a time; the three heads
+// (8 each) as (two output chunks) x (eight k-blocks) x (hi, mid, lo) against pose_encoder.2's output split ONCE (trunk_bf16x9.h); slice
+// s + 1 (held in registers since step s - 1) is written into the other slot while slot s is multiplied, slice s + 2 is requested, one
+// barrier per slice.
 // Budget per workgroup and launch (MI355X: LDS 256 B/clk/CU for conflict-free ds_read_b128, v_mfma_f32_16x16x32_bf16 16 cycles):
 //   LDS fragment reads  33 slices x 48 KB x 4 waves = 6.3 MB  -> 24.8 k cycles (49.5 k at 128 B/clk)
 //   MFMA                33 x 16 chunks x 9 products x 2 tiles = 9 504 per wave x 16 cycles = 152 k cycles per SIMD (63 us at the 2.4 GHz
 //                       peak clock; dense BF16 MFMA loops on random data sustain 1.5-1.95 GHz on this part: 80 us at 1.9 GHz)
 // so the matrix pipe bounds it, not LDS (bf16x3's 8 waves x 16 rows read the same 1.5 MB weight stream twice as often per row) and not
 // the fp32 peak: 9 bf16 products per fp32 product at 16x the fp32 rate = 1.8x the fp32 MFMA FLOP rate.
-// Measured (MI355X, 32 000 rows, rocprofv3): 118.0 us per launch against 142.7 us for pc_step_chain_kernel<2, 0> (102.7 us by HIP events
-// since); the rest of the gap to the floor - 80 us at a sustained 1.9 GHz, not the 63 us of the peak clock, so the kernel runs near 0.8 of
-// what the clock allows - is barrier drains (one wave per SIMD), the head epilogues (not overlapped with MFMAs) and a few spilled registers.
+// Measured (MI355X, 32 000 rows, HIP events around the PC-100 graph, profiles/x9_heads_chunk_major.txt): 100.3 us per launch, against
+// 103.8 us with k-major heads in the same session (118.0 us under rocprofv3 when it replaced the 142.7 us of pc_step_chain_kernel<2, 0>).
+// The head epilogues now sit between the MFMAs of the following chunk; what is left of the gap to the floor - 80 us at a sustained
+// 1.9 GHz (the clock inside the kernel has not been measured) - is barrier drains (one wave per SIMD), the splits of the two k-major
+// layers, pose_encoder.2's bias + ReLU + split tail (one run of ~800 instructions without an MFMA) and the last head's last chunk.
 #include "pc_rows.h"
 #include "trunk_bf16x9.h"
 #include "trunk_chain.h"

@@ -203,6 +203,15 @@ def pack_bf16x9(W, n_chunks, k_blocks, chain=True):
     return _gather_fragments(split_bf16x9(_pad_for_fragments(W, n_chunks, k_blocks)), n_chunks, k_blocks, chain)
 
 
+def pack_heads_bf16x9(W):
+    """The three stacked 256-wide heads [768, 256] -> int16 [head 3][chunk pair 8][chunk 2][k-block 8][3][64][8]: the stream of
+    csrc/trunk_bf16x9.h's chunk-major head slices in the order they are consumed - a slice is (two output chunks 2 j, 2 j + 1 of a head) x
+    (all eight k-blocks) x (hi, mid, lo).  A permutation of pack_bf16x9(W, 48, 8): fragments, k order and the exactness check are its."""
+    if tuple(W.shape) != (768, 256):
+        raise ValueError(f"stacked heads [768, 256] expected, got {tuple(W.shape)}")
+    return pack_bf16x9(W, 48, 8).view(8, 3, 8, 2, 3, 64, 8).permute(1, 2, 3, 0, 4, 5, 6).contiguous()  # [kb][h][j][c] -> [h][j][c][kb]
+
+
 def pack_sa_bf16x9(W2, W3):
     """Level 2's layer-2 [196, 128] and layer-3 [256, 196 (or zero padded up to 224)] weights -> int16 [22 slices][8 chunks][3][64][8]: the
     stream of csrc/sa_bf16x9.hip's ring in the order it is consumed.  Slices 0-7: layer 2 as (k-block kb, chunk half h) = 2 kb + h, output
@@ -310,13 +319,14 @@ class ScoreNetWeights:
         return self._bf16x3
 
     def bf16x9_packs(self):
-        """Operands of the default chain-plan PC step (csrc/trunk_bf16x9.hip): the three dense layers of the trunk as exact hi / mid / lo
-        bf16 triples in the fragment order of v_mfma_f32_16x16x32_bf16 (pack_bf16x9)
-        -> (w_pose0 [1][16][3][64][8], w_pose2 [8][16][3][64][8], w_headx [8][48][3][64][8]) as int16 device tensors."""
+        """Operands of the bf16x9 chain kernels (csrc/trunk_bf16x9.h: PC step, Heun step, RK45 stage): the three dense layers of the trunk as
+        exact hi / mid / lo bf16 triples in the fragment order of v_mfma_f32_16x16x32_bf16 (pack_bf16x9), the heads in the order the ring
+        consumes them (pack_heads_bf16x9)
+        -> (w_pose0 [1][16][3][64][8], w_pose2 [8][16][3][64][8], w_headx [3][8][2][8][3][64][8]) as int16 device tensors."""
         if self._bf16x9 is None:
             r = self._raw
             self._bf16x9 = (pack_bf16x9(r["pose0"], 16, 1, chain=False).to(self._device), pack_bf16x9(r["pose2"], 16, 8).to(self._device),
-                            pack_bf16x9(r["headx"], 48, 8).to(self._device))
+                            pack_heads_bf16x9(r["headx"]).to(self._device))
         return self._bf16x9
 
     def ref(self):

@@ -345,7 +345,9 @@ int gp_pc_layout_bf16x3(int ngroups, int nclouds_per_group, int k, int *nparts_o
  * v_mfma_f32_16x16x32_bf16, fp32 accumulation).  gp_pc_step_plan's contract with tile = 128: the same buffers, gn_ext / gn_rows_total
  * coupling, partials [nsteps][*nparts_out of gp_pc_layout(0, 128, ...)]; GP_EINVAL where that plan does not apply.  w_*_x9: hi / mid / lo
  * bf16 triples in the fragment order of v_mfma_f32_16x16x32_bf16 (genpose_amd/weights.py: pack_bf16x9 - pose_encoder.0 [1][16][3][64][8]
- * in natural k order, pose_encoder.2 [8][16]..., stacked heads [8][48]... in the register chain's k order); biases and output layers
+ * in natural k order, pose_encoder.2 [8][16][3][64][8] (k-block, output chunk) in the register chain's k order; the stacked heads in the
+ * order the kernel consumes them, [head 3][chunk pair 8][chunk 2][k-block 8][3][64][8] - pack_heads_bf16x9, a permutation of
+ * pack_bf16x9(W, 48, 8); this w_headx_x9 layout holds for every gp_*_bf16x9 entry point); biases and output layers
  * from `net`.  The default for that plan (genpose_amd/samplers.py); gp_pc_step_plan keeps the fp32-MFMA chain kernel. */
 int gp_pc_step_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec, const float *tvec_all,
                       const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score,
