@@ -82,10 +82,13 @@ SIGNATURES = {
     "gp_pc_step_bf16x9_seeded": [c_int] * 5 + [NETP] + [P] * 11 + [c_int] + [P] * 3 + [P],
     "gp_pc_noise_fill": [P, c_int, c_int, c_int64, c_int64, P, P, P],
     "gp_philox_raw": [c_int64, P, P, P, P],
+    "gp_track_warm_start": [c_int, c_int] + [P] * 7 + [P],
+    "gp_track_prior_fill": [P, c_int64, c_int64, P, P],
     "gp_heun_launches": [c_int, c_int],
     "gp_heun_layout": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "gp_heun_step_plan": [c_int] * 7 + [NETP] + [P] * 9 + [P],
     "gp_heun_step_bf16x9": [c_int] * 6 + [NETP] + [P] * 9 + [P] * 3 + [P],
+    "gp_heun_solve_tile": [c_int] * 6 + [NETP] + [P] * 9 + [P],
     "gp_heun_likelihood_launches": [c_int],
     "gp_heun_likelihood_step": [c_int] * 4 + [NETP] + [P] * 9 + [P],
     "gp_pc_step_grouped": [c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 11 + [P],

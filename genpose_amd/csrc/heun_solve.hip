@@ -1,0 +1,134 @@
+// The whole fixed-step Heun solve of the probability-flow ODE (cond_edm_sampler's method, samplers.py:230-290; HeunArgs, pc_rows.h) in ONE
+// launch, tile plans.  The update is row-local, so between two evaluations a workgroup's tile depends on no other workgroup: the
+// workgroup that owns rows [blockIdx.x * P, +P) takes them through every launch index l = 0 .. last of the per-launch chain
+// (scorenet.hip: heun_step_tile) itself.  Per index it runs that launch's code - heun_update_row, heun_store_row's effects on x, out and
+// traj, the hand-over of the evaluation point through LDS, trunk_begin / trunk_ftheta, the score divided by sigma + 1e-7f - on the same
+// operands in the same order, so the result is the chain's bit for bit (tests/test_gpu_heun_solve.py).  What the chain passes from launch
+// to launch through global memory stays on chip: x_i, d_i and the cloud centre in a private LDS slot of the row's thread (tid < P) behind
+// the trunk's block (21 floats per row, component-major: kept in registers they stay live across the whole trunk and the 64-row tile
+// spills), the score in the trunk's block itself, where the row thread divides it.  No global store of this kernel is read back by it, so nothing here needs an ordering
+// beyond the workgroup barriers below.  d and score are not written.
+#include "pc_rows.h"
+
+namespace {
+
+using namespace gp_trunk;
+
+// A pointer the compiler knows nothing about from here on.  Every index re-requests the trunk's weights, biases and epilogue operands as its
+// launch of the chain does; without this the loads that do not depend on the index are hoisted out of the loop and stay live across the
+// whole trunk (256 VGPRs and up to 118 spilled registers per lane, against the per-launch kernels' 128 - 184 and none).
+__device__ __forceinline__ void opaque(const float *&p) { asm volatile("" : "+s"(p)); }
+
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a, const gp_scorenet net0) {
+    using L = TrunkLds<P>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int row0 = blockIdx.x * P, tid = threadIdx.x, last = a.nsteps;
+    const bool live = row0 + tid < a.nrows;
+    const int r = live ? row0 + tid : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
+    float *mine = lds + L::TOTAL + tid;  // this row thread's slot: x_i at [j * P], d_i at [(9 + j) * P], the cloud centre at [(18 + j) * P]
+    if (tid < P) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) mine[j * P] = a.x[(size_t)r * 9 + j];
+        const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) mine[(18 + j) * P] = cp[j];
+    }
+    float sigma_prev = 1.f;  // the divisor of the score that sits in LDS
+    for (int l = 0; l <= last; ++l) {
+        const float *tvec = a.tvec_all + (size_t)pc_time_row<true>(l) * HEADS;
+        gp_scorenet net = net0;
+        opaque(net.w_pose0), opaque(net.b_pose0), opaque(net.w_pose2), opaque(net.b_pose2), opaque(net.w_headx), opaque(net.w_out), opaque(net.b_out);
+        opaque(a.cvec);
+        TrunkPre<P> pre;
+        float sigma = 1.f;
+        if (l < last) {
+            trunk_begin<P>(net, pre, a.cvec, tvec, row0, a.nrows, a.kcand);
+            sigma = a.sched[(size_t)l * 4 + 0];  // requested now, used after the trunk
+            gp_pin(sigma);
+        }
+        if (tid < P) {
+            float ev[9];  // x_i in, the point this index evaluates out
+#pragma unroll
+            for (int j = 0; j < 9; ++j) ev[j] = mine[j * P];
+            if (l > 0) {
+                const float *sc = a.sched + (size_t)l * 4;
+                const int kind = (int)sc[3];
+                const float c = sc[1], h = sc[2];
+                // the previous index's f_theta (all of trunk_ftheta's barriers are behind us); the chain stores this quotient and reloads it
+                const float *F = lds + L::OFF_H1 + tid * L::LDH;
+                float gr[9], dv[9];
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    gr[j] = F[j] / (sigma_prev + 1e-7f);
+                    dv[j] = kind == HEUN_CORRECT || kind == HEUN_CORRECT_LAST ? mine[(9 + j) * P] : 0.f;
+                }
+                heun_update_row(kind, ev, dv, gr, c, h);
+                if (kind == HEUN_PREDICT) {  // keeps x_i (the chain never stores the Euler point) and parks d_i
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) mine[(9 + j) * P] = dv[j];
+                } else {
+                    if (kind != HEUN_DENOISE) {
+#pragma unroll
+                        for (int j = 0; j < 9; ++j) mine[j * P] = ev[j];
+                    }
+                    if (live) {
+                        const float cen[3] = {mine[18 * P], mine[19 * P], mine[20 * P]};
+                        HeunArgs al = a;
+                        al.step = l, al.d = nullptr;
+                        heun_store_row(al, kind, r, ev, dv, cen);
+                    }
+                }
+            }
+            // hand the evaluation point to the trunk through LDS
+            float *xr = lds + tid * L::LD0;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) xr[j] = ev[j];
+#pragma unroll
+            for (int j = 9; j < 16; ++j) xr[j] = 0.f;
+        }
+        if (l == last) break;
+        __syncthreads();  // X0 is complete, and the row threads have read the previous f_theta out of H1, before layer 1 overwrites it
+        trunk_ftheta<P>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre);  // (ends on a barrier: f_theta is visible to the row threads)
+        sigma_prev = sigma;
+    }
+}
+
+// the trunk's block and 21 floats per row behind it
+template <int P>
+constexpr size_t solve_lds_bytes() {
+    return trunk_lds_bytes<P>() + (size_t)21 * P * sizeof(float);
+}
+
+template <int P>
+int launch_solve(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(heun_solve_kernel<P>, solve_lds_bytes<P>())) return GP_ELAUNCH;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((heun_solve_kernel<P>), dim3(nwg), dim3(TrunkCfg<P>::NT), solve_lds_bytes<P>(), st, a, *net);
+    return gp_launch_status();
+}
+
+}  // namespace
+
+extern "C" int gp_heun_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                                  const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                                  gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
+        return GP_EINVAL;
+    const long long rg = (long long)nclouds_per_group * k, R = ngroups * rg;
+    if (R > 0x7fffffffLL / 9) return GP_EINVAL;  // row and element indices are ints up to R * 9
+    if (R == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
+    if (rc != GP_OK) return rc;
+    if (P != 16 && P != 32 && P != 64) return GP_EINVAL;  // the chain form keeps its per-launch kernels
+    const HeunArgs a = heun_args((int)R, k, 0, gp_heun_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    hipStream_t st = (hipStream_t)s;
+    const int nwg = ngroups * (int)((rg + P - 1) / P);
+    if (P == 16) return launch_solve<16>(a, net, nwg, st);
+    if (P == 32) return launch_solve<32>(a, net, nwg, st);
+    return launch_solve<64>(a, net, nwg, st);
+}

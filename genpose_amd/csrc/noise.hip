@@ -1,6 +1,8 @@
 // The seeded PC sampler's noise as plain buffers (include/genpose_hip.h: gp_pc_noise_fill, gp_philox_raw): what the seeded step kernels
 // draw in registers (philox.h: the same device function), written out - the bridge to the injected-noise path of gp_pc_step_plan /
 // gp_pc_step_bf16x9 and a dump of a run's draws.  Replaces torch.randn_like of cond_pc_sampler (samplers.py:132,149).
+// And the fixed-step tracker's prior (gp_track_warm_start, gp_track_prior_fill): the draw of samplers.py:180 on the prior's own counters
+// (philox.h) with the warm start of evaluation_tracking.py:302-310 around it.
 #include "gp_common.h"
 #include "philox.h"
 
@@ -27,6 +29,39 @@ __global__ __launch_bounds__(256) void pc_noise_fill_kernel(const uint32_t *__re
     }
 }
 
+// The tracker's warm start, one thread per row (cloud i, candidate c): x0 = init_i + sigma * z, the product and the sum rounded separately (a
+// host restatement in fp32 gives the same bits).  init_i = [R[:,0], R[:,1], t - centre[i]] of a row-major 4x4: the previous frame's
+// aggregated pose src[i] when src[i] >= 0, else the cloud's own fallback (the jittered ground truth).
+__global__ __launch_bounds__(256) void track_warm_start_kernel(int n, int k, const uint32_t *__restrict__ seed_state, const float *__restrict__ sigma,
+                                                               const float *__restrict__ prev_sRT, const int *__restrict__ src,
+                                                               const float *__restrict__ fallback_sRT, const float *__restrict__ centre,
+                                                               float *__restrict__ x0) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)n * k) return;
+    const int i = (int)(e / k);
+    const int sp = src[i];
+    const float *m = sp >= 0 ? prev_sRT + (size_t)sp * 16 : fallback_sRT + (size_t)i * 16;
+    const float *cp = centre + (size_t)i * 3;
+    const float init[9] = {m[0], m[4], m[8], m[1], m[5], m[9], m[3] - cp[0], m[7] - cp[1], m[11] - cp[2]};
+    const gp_philox::Seed sd = gp_philox::load_seed(seed_state);
+    float z[9];
+    gp_philox::draw9(sd, gp_philox::PRIOR_STEP, gp_philox::STREAM_LANGEVIN, sd.row_base + (uint64_t)e, z);
+    const float sg = *sigma;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) x0[e * 9 + j] = __fadd_rn(init[j], __fmul_rn(sg, z[j]));
+}
+
+// the prior's draws as a buffer: z_out [nrows][9], the row of the launch is row0 + r
+__global__ __launch_bounds__(256) void track_prior_fill_kernel(const uint32_t *__restrict__ seed_state, long long row0, long long nrows, float *__restrict__ z_out) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= nrows) return;
+    const gp_philox::Seed sd = gp_philox::load_seed(seed_state);
+    float z[9];
+    gp_philox::draw9(sd, gp_philox::PRIOR_STEP, gp_philox::STREAM_LANGEVIN, sd.row_base + (uint64_t)(row0 + r), z);
+#pragma unroll
+    for (int j = 0; j < 9; ++j) z_out[r * 9 + j] = z[j];
+}
+
 // raw Philox4x32-10 blocks: counters [n][4], keys [n][2] -> out [n][4]
 __global__ __launch_bounds__(256) void philox_raw_kernel(long long n, const uint32_t *__restrict__ ctr, const uint32_t *__restrict__ key,
                                                          uint32_t *__restrict__ out) {
@@ -51,6 +86,26 @@ int gp_pc_noise_fill(const void *seed_state, int step0, int nsteps, int64_t row0
     if ((n + 255) / 256 > 0x7fffffffLL) return GP_EINVAL;
     hipLaunchKernelGGL(pc_noise_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, (const uint32_t *)seed_state, step0, nsteps,
                        (long long)row0, (long long)nrows, z_lang_out, z_pred_out);
+    return gp_launch_status();
+}
+
+int gp_track_warm_start(int n, int k, const void *seed_state, const float *sigma, const float *prev_sRT, const int *src, const float *fallback_sRT,
+                        const float *centre, float *x0, gp_stream_t s) {
+    if (n < 0 || k <= 0 || !seed_state || !sigma || !prev_sRT || !src || !fallback_sRT || !centre || !x0) return GP_EINVAL;
+    const long long rows = (long long)n * k;
+    if (rows == 0) return GP_OK;
+    if ((rows + 255) / 256 > 0x7fffffffLL) return GP_EINVAL;
+    hipLaunchKernelGGL(track_warm_start_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)s, n, k, (const uint32_t *)seed_state, sigma,
+                       prev_sRT, src, fallback_sRT, centre, x0);
+    return gp_launch_status();
+}
+
+int gp_track_prior_fill(const void *seed_state, int64_t row0, int64_t nrows, float *z_out, gp_stream_t s) {
+    if (!seed_state || row0 < 0 || nrows < 0 || !z_out) return GP_EINVAL;
+    if (nrows == 0) return GP_OK;
+    if ((nrows + 255) / 256 > 0x7fffffffLL) return GP_EINVAL;
+    hipLaunchKernelGGL(track_prior_fill_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, (hipStream_t)s, (const uint32_t *)seed_state,
+                       (long long)row0, (long long)nrows, z_out);
     return gp_launch_status();
 }
 

@@ -9,6 +9,10 @@
 //     ctr[2]          = run index (32 bits)
 //     ctr[3]          = step << 3 | stream << 2 | block      step < 2^29; stream 0 = Langevin corrector, 1 = predictor; block 0..2
 // Every field has its own bits, so two different field tuples never share a (counter, key).
+// THE TRACKER'S PRIOR (gp_track_warm_start, gp_track_prior_fill: the draw of samplers.py:180; tests/track_prior_reference.py restates it) has
+// the same layout with the step field RESERVED: step = PRIOR_STEP = 2^29 - 1, stream 0, run index = the FRAME index, global row =
+// (sequence * objects per frame + object) * K + candidate.  The seeded PC samplers take nsteps < 2^29, so their steps end at 2^29 - 2:
+// no PC draw of a sampler shares a (counter, key) with the prior.
 // One row, stream and step take three blocks = 12 words w[0..11]; pair k = (w[2k], w[2k+1]) gives
 //     u1 = ((w[2k] >> 8) + 1) * 2^-24,  u2 = ((w[2k+1] >> 8) + 1) * 2^-24        both in (0, 1]
 //     z[2k] = sqrt(-2 log u1) * cos(2 pi u2),  z[2k+1] = sqrt(-2 log u1) * sin(2 pi u2)
@@ -24,6 +28,7 @@ namespace gp_philox {
 constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
 constexpr int STREAM_LANGEVIN = 0, STREAM_PREDICTOR = 1;
 constexpr uint32_t MAX_STEPS = 1u << 29;
+constexpr uint32_t PRIOR_STEP = MAX_STEPS - 1;  // the tracker's prior (header comment)
 
 // The seed state in device memory (8 words, written by the host in stream order before a replay; the kernels only read it):
 //     [0], [1] seed lo / hi   [2] run index   [3] 0   [4], [5] row base lo / hi (global row = row base + row of the launch)   [6], [7] 0

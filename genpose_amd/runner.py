@@ -439,3 +439,292 @@ class MultiSequenceTracker:
                       "nfev": int(smp.group_stats[q]["nfev"])}
         self._prev = (live, average_sRT)
         return out
+
+
+def _unpin_score_embed(key, ent):
+    for ws in ent[3]:
+        ws["_pins"] -= 1
+
+
+class _ScoreEmbedGraph:
+    """Graph A of _FrameGraphs for a tracker that has no energy agent: clouds [n,1024,3] -> centres and the score model's per-cloud
+    embedding, one hipGraph per cloud shape (static input, static outputs that the next frame of the shape overwrites)."""
+
+    SLOT = "fixed-step-tracker"
+
+    def __init__(self, snet):
+        self.snet = snet
+        self.enc = snet.pointnet2_encoder("FixedStepTracker")
+        self._a = ShapeCache(_FrameGraphs.MAX_SHAPES, on_evict=_unpin_score_embed)
+        self.ev_e = None
+
+    def _body(self, pts):
+        return pts.mean(dim=1), self.snet.pose_score_net.cloud_embed(self.enc.forward(pts, slot=self.SLOT))
+
+    def embed(self, pts):
+        key = (tuple(pts.shape), pts.dtype)
+        ent = self._a.get(key)
+        if ent is None:
+            buf = pts.clone()
+            self._body(buf)  # warm-up outside capture: workspaces, kernel attributes
+            torch.cuda.synchronize()
+            pinned = [self.enc.pin_workspaces(int(buf.shape[0]), int(buf.shape[1]), self.SLOT)]
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                centre, cvec_s = self._body(buf)
+            ent = self._a[key] = (g, buf, (centre, cvec_s, None), pinned)
+        g, buf, outs, _ = ent
+        buf.copy_(pts)
+        g.replay()
+        return outs
+
+
+class FixedStepTracker:
+    """Tracking (main_tracking, evaluation_tracking.py:262-337) on the fixed-step Heun solver, with the frame resident on the device.  The
+    solve has a fixed number of evaluations, so nothing between the clouds and the aggregated 4x4 poses needs a host decision: a step whose
+    frame layout was seen before copies the clouds into a static buffer, writes the seed state through a pinned block in stream order and
+    replays captured graphs - the encoders and cloud embeddings (_FrameGraphs' A, with A' on its side stream; one graph without an energy
+    agent), then ONE graph holding the warm start with the prior drawn on the device (gp_track_warm_start: no host draw, no upload), the
+    Heun solve (samplers.HeunSampler as a chain of 2 N + 2 launches or as one launch), the ranker and gp_rank_aggregate_rt.  No per-kernel
+    launch, no read-back: last_stats['replays'] <= 3.
+
+    step(frames): one (pts [n_i,1024,3], model_names, gt_RT [n_i,4,4]) per sequence, None where a sequence has no frame - one sequence is
+    the list of one.  The live sequences' clouds share every launch; every stage is row-local or cloud-local and the prior's draw of a
+    candidate is a function of (seed, sequence, frame of the sequence, object, candidate) - global row (sequence * max_objects_per_frame +
+    object) * K + k, the sequence's own frame count as the run word - so a sequence's result does not depend on what shares the step.
+    Returns one dict per sequence (None where there was no frame): init_x, pred_pose [n,K,9] f32, energy [n,K,2], sorted_RTs [n,K,4,4]
+    f64, average_sRT [n,4,4] and nfev; all of them the caller's own copies.
+
+    Warm start: the reference's semantics - an object continues from the previous frame's aggregated sRT of the same model_name (first
+    match of list.index, duplicates included), else from a jittered gt_RT.  The jitter (add_noise_to_RT) is drawn on the host ONLY in a
+    step that has an object without a predecessor, from a generator keyed by (seed, sequence, frame); the reference draws it every frame
+    on the global generator - this tracker claims NO random-number parity with the reference or with TrackingRunner.  In steady state the
+    source table is cached and nothing is uploaded but the seed state.
+
+    ranker: 'energy' - the energy agent's two energies at T = 1e-5; 'likelihood' - the score agent's own exact-divergence log-likelihood by
+    samplers.HeunLikelihood (cfg.likelihood_steps, else the tracker's steps; cfg.likelihood_grid) in both columns, cast to float32 as
+    SingleFrameRunner does: tracking from a score checkpoint alone.
+    launches: 'single' / 'chain' force the solve's form; None takes 'single' below SINGLE_MAX_ROWS rows where the plan is a tile plan."""
+
+    RANKERS = ("energy", "likelihood")
+    LAUNCHES = (None, "single", "chain")
+    # rows below which launches=None takes the one-launch solve.  profiles/fixed_step_tracking.txt: its median lay below the chain's minimum
+    # at 250, 800 and 3 200 rows (16-row tiles, 1.09x) and above it at 12 800 rows (64-row tiles, 0.97x); nothing was measured in between
+    SINGLE_MAX_ROWS = 3201
+    MAX_SHAPES = 8
+    RING = 4  # pinned blocks in rotation: the host rewrites one only after the copy issued four steps earlier has completed
+
+    def __init__(self, score_agent, energy_agent=None, steps=8, repeat_num=50, T0=0.15, ratio=0.6, ranker="energy", seed=0, launches=None,
+                 grid="geometric", max_objects_per_frame=8):
+        from .samplers import HEUN_GRIDS
+        if score_agent.cfg.posenet_mode != "score":
+            raise ValueError(f"FixedStepTracker: the score agent's posenet_mode is {score_agent.cfg.posenet_mode!r}, the Heun solver needs 'score'")
+        if ranker not in self.RANKERS:
+            raise ValueError(f"FixedStepTracker(ranker={ranker!r}): one of {self.RANKERS}")
+        if ranker == "energy" and energy_agent is None:
+            raise ValueError("FixedStepTracker(ranker='energy') needs energy_agent (ranker='likelihood' tracks from the score agent alone)")
+        if launches not in self.LAUNCHES:
+            raise ValueError(f"FixedStepTracker(launches={launches!r}): one of {self.LAUNCHES}")
+        if grid not in HEUN_GRIDS:
+            raise ValueError(f"FixedStepTracker(grid={grid!r}): one of {HEUN_GRIDS}")
+        if int(steps) < 1:
+            raise ValueError(f"FixedStepTracker(steps={steps}): at least one step")
+        if int(max_objects_per_frame) < 1 or int(repeat_num) < 1:
+            raise ValueError(f"FixedStepTracker(max_objects_per_frame={max_objects_per_frame}, repeat_num={repeat_num}): at least one")
+        for a in (score_agent, energy_agent) if ranker == "energy" else (score_agent,):
+            a.net.pointnet2_encoder("FixedStepTracker")  # refuses pts_encoder='pointnet_and_pointnet2': the graphs drive the PointNet++ stages
+        if getattr(score_agent.net, "coupling_group", None) is not None:
+            raise ValueError("FixedStepTracker: the score agent has a coupling_group (a batch sharded over a process group); the frame graphs build "
+                             "an uncoupled solver - use the agent's pred_func")
+        self.score_agent, self.energy_agent = score_agent, energy_agent if ranker == "energy" else None
+        self.steps, self.repeat_num, self.T0, self.ratio = int(steps), int(repeat_num), float(T0), ratio
+        self.ranker, self.seed, self.launches, self.grid = ranker, int(seed) % (1 << 64), launches, grid
+        self.max_objects = int(max_objects_per_frame)
+        self.buffers, self.frame_index = [], []
+        self._embed = self._prev = None
+        self._b = ShapeCache(self.MAX_SHAPES)
+        self.captures = 0
+        self.last_stats = {}
+
+    def reset(self, seq=None):
+        """Forget the previous poses (the next frame starts from jittered ground truth) and restart the frame count, of one sequence or all."""
+        for i in (range(len(self.buffers)) if seq is None else [seq]):
+            self.buffers[i], self.frame_index[i] = [], 0
+
+    # ------------------------------------------------------------------ host side
+    def _grow(self, nseq, dev):
+        while len(self.buffers) < nseq:
+            self.buffers.append([])
+            self.frame_index.append(0)
+        need = nseq * self.max_objects
+        if self._prev is None or self._prev.shape[0] < need:
+            # one slot per (sequence, object): the captured graphs read and write it, so a larger one means new graphs
+            prev = torch.zeros(need, 4, 4, device=dev)
+            if self._prev is not None:
+                prev[: self._prev.shape[0]] = self._prev
+            self._prev = prev
+            self._b = ShapeCache(self.MAX_SHAPES)
+
+    def _jitter(self, seq, gt_RT):
+        g = torch.Generator().manual_seed((self.seed * 1000003 + seq * 7919 + self.frame_index[seq]) % (1 << 63))
+        B = gt_RT.shape[0]
+        draws = [torch.randn(B, generator=g), torch.randn(B, 4, generator=g), torch.randn(B, generator=g), torch.randn(B, 3, generator=g)]
+        return add_noise_to_RT(gt_RT.float().cpu(), draws=draws)
+
+    def _solve_form(self, rows, plan):
+        if self.launches is not None:
+            return self.launches
+        return "single" if plan != 128 and rows < self.SINGLE_MAX_ROWS else "chain"
+
+    # ------------------------------------------------------------------ the frame's second graph
+    def _body(self, ent):
+        from . import _lib
+        from ._lib import ptr, stream_ptr
+        from .likelihood import global_prior_likelihood
+        from .sde import SIGMA_MAX
+        key, smp, K = ent["key"], ent["smp"], self.repeat_num
+        _, cvec_s, cvec_e = ent["a_outs"]
+        # the clouds' centres, reduced PER SEQUENCE: a reduction over the whole step's clouds may split its sums by the batch's shape, and a
+        # sequence's result must not depend on what shares the step (graph A's own centres, taken over all clouds, are not used)
+        lo, cen = 0, []
+        for _, c in key:
+            cen.append(torch.mean(ent["pts"][lo:lo + c][:, :, :3], dim=1))
+            lo += c
+        centre = smp.centre = torch.cat(cen, dim=0) if len(cen) > 1 else cen[0]
+        n = centre.shape[0]
+        # the poses the frame starts from (evaluation_tracking.py:302-310), for the caller; the kernel below forms them itself
+        src = ent["src"].long()
+        init_sRT = torch.where((src >= 0).view(n, 1, 1), self._prev.index_select(0, src.clamp(min=0)), ent["fallback"])
+        init_x = torch.cat([init_sRT[:, :3, 0], init_sRT[:, :3, 1], init_sRT[:, :3, 3] - centre], dim=1)
+        lo = 0
+        for q, (_, c) in enumerate(key):  # one launch per sequence: its own row base and frame index
+            _lib.call("gp_track_warm_start", c, K, ptr(ent["seed"][q]), ptr(smp.sched), ptr(self._prev), ptr(ent["src"][lo:lo + c]),
+                      ptr(ent["fallback"][lo:lo + c]), ptr(centre[lo:lo + c]), ptr(smp.x[lo * K:(lo + c) * K]), stream_ptr())
+            lo += c
+        smp._launch_all()
+        pred = smp.out.view(n, K, 9)
+        pose = pred.clone()
+        pose[:, :, 6:] -= centre.unsqueeze(1)  # posenet_agent.py:516: translations relative to the cloud centre
+        if self.ranker == "energy":
+            energy = self.energy_agent.net.pose_score_net.evaluate(cvec_e, K, pose.reshape(n * K, 9), self._embed.tvec_e, self._embed.sigma_e,
+                                                                   "energy").reshape(n, K, 2)
+        else:
+            lk = ent["lik"]
+            lk.x.copy_(pose.reshape(n * K, 9))
+            lk._launch_all()
+            ll = (global_prior_likelihood(lk.z.double(), SIGMA_MAX) + lk.logp) / math.log(2)
+            ll32 = ll.float().view(n, K)
+            energy = torch.stack([ll32, ll32], dim=-1).contiguous()
+        r = reward.rank_aggregate(pred, energy, selected_num=ent["sel"], with_rt=True)
+        self._prev.index_copy_(0, ent["dst"], r["avg_RT"])
+        return init_x, pred, energy, r["sorted_RTs"], r["avg_RT"]
+
+    def _capture(self, key, a_outs, pts):
+        from .samplers import HeunLikelihood, HeunSampler
+        net = self.score_agent.net
+        K = self.repeat_num
+        n, dev = sum(c for _, c in key), pts.device
+        probe = HeunSampler(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False)
+        form = self._solve_form(n * K, probe.plan)
+        smp = probe if form == "chain" else HeunSampler(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False, launches=form)
+        smp.cvec = a_outs[1]  # graph A's static output: nothing is copied
+        ent = {"key": key, "smp": smp, "a_outs": a_outs, "sel": max(1, int(self.ratio * K)),
+               "src": torch.full((n,), -1, dtype=torch.int32, device=dev), "fallback": torch.zeros(n, 4, 4, device=dev),
+               "seed": torch.zeros(len(key), 8, dtype=torch.int32, device=dev), "pts": pts.clone(),
+               "dst": torch.tensor([i * self.max_objects + j for i, c in key for j in range(c)], dtype=torch.int64, device=dev),
+               "src_host": None, "ring": 0,
+               "pin_seed": [torch.zeros(len(key), 8, dtype=torch.int32).pin_memory() for _ in range(self.RING)],
+               "pin_src": [torch.zeros(n, dtype=torch.int32).pin_memory() for _ in range(self.RING)],
+               "pin_fb": [torch.zeros(n, 4, 4).pin_memory() for _ in range(self.RING)],
+               "ev": [None] * self.RING}
+        smp._write_schedule(self.T0, net.sampling_eps)
+        if self.ranker == "likelihood":
+            lsteps = getattr(net.cfg, "likelihood_steps", None) or self.steps
+            lk = ent["lik"] = HeunLikelihood(net.pose_score_net, n, K, dev, int(lsteps), grid=getattr(net.cfg, "likelihood_grid", "geometric"), use_graph=False)
+            lk.cvec = a_outs[1]
+            lk._write_schedule(net.sampling_eps, 1.0)
+        keep = self._prev.clone()
+        self._body(ent)  # warm-up outside capture: kernel attributes, the allocator's blocks
+        torch.cuda.synchronize()
+        self._prev.copy_(keep)  # (the warm-up ran on placeholders and wrote its poses into the slots)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            ent["outs"] = self._body(ent)
+        ent["graph"] = g
+        self.captures += 1
+        return ent
+
+    def step(self, frames):
+        net = self.score_agent.net
+        K = self.repeat_num
+        live = [i for i, f in enumerate(frames) if f is not None and f[0].shape[0] > 0]
+        out = [None] * len(frames)
+        if not live:
+            return out
+        net._need_weights()
+        for i in live:
+            if frames[i][0].shape[0] > self.max_objects or len(frames[i][1]) != frames[i][0].shape[0]:
+                raise ValueError(f"sequence {i}: {frames[i][0].shape[0]} objects / {len(frames[i][1])} names; at most max_objects_per_frame = {self.max_objects}")
+        dev = frames[live[0]][0].device
+        self._grow(len(frames), dev)
+        if self._embed is None:
+            if self.ranker == "energy":
+                self.energy_agent.net._need_weights()
+                self._embed = _FrameGraphs(net, self.energy_agent.net, K, max(1, int(self.ratio * K)))
+            else:
+                self._embed = _ScoreEmbedGraph(net)
+        key = tuple((i, int(frames[i][0].shape[0])) for i in live)
+        pts = torch.cat([frames[i][0].float() for i in live], dim=0)
+        a_outs = self._embed.embed(pts)
+        replays = 2 if self.ranker == "energy" else 1
+        ent = self._b.get(key)
+        if ent is None or ent["a_outs"][1] is not a_outs[1]:  # (graph A of this cloud count was dropped and captured again: new static tensors)
+            ent = self._b[key] = self._capture(key, a_outs, pts)
+        # ---- warm-start table: where every object continues from
+        src, fresh = [], False
+        for i in live:
+            names = self.buffers[i]
+            for name in frames[i][1]:
+                src.append(i * self.max_objects + names.index(name) if name in names else -1)
+                fresh = fresh or src[-1] < 0
+        ent["pts"].copy_(pts)
+        slot = ent["ring"] = (ent["ring"] + 1) % self.RING
+        if ent["ev"][slot] is not None:
+            ent["ev"][slot].synchronize()  # the copies issued RING steps ago out of these pinned blocks (long completed)
+        else:
+            ent["ev"][slot] = torch.cuda.Event()
+        with _one_cpu_thread():
+            if fresh:
+                ent["pin_fb"][slot].copy_(torch.cat([self._jitter(i, frames[i][2]) for i in live], dim=0))
+                ent["fallback"].copy_(ent["pin_fb"][slot], non_blocking=True)
+            uploaded = src != ent["src_host"]
+            if uploaded:
+                ent["pin_src"][slot].copy_(torch.tensor(src, dtype=torch.int32))
+                ent["src"].copy_(ent["pin_src"][slot], non_blocking=True)
+                ent["src_host"] = src
+            words = np.zeros((len(live), 8), dtype=np.uint32)
+            for q, i in enumerate(live):
+                base = i * self.max_objects * K
+                words[q] = (self.seed & 0xFFFFFFFF, self.seed >> 32, self.frame_index[i] & 0xFFFFFFFF, 0, base & 0xFFFFFFFF, base >> 32, 0, 0)
+            ent["pin_seed"][slot].copy_(torch.from_numpy(words.view(np.int32)))
+            ent["seed"].copy_(ent["pin_seed"][slot], non_blocking=True)
+        cur = torch.cuda.current_stream(dev)
+        ent["ev"][slot].record(cur)
+        if self.ranker == "energy":
+            cur.wait_event(self._embed.ev_e)  # the energy model's embedding (side stream)
+        ent["graph"].replay()
+        replays += 1
+        init_x, pred, energy, sorted_RTs, average_sRT = (t.clone() for t in ent["outs"])
+        smp = ent["smp"]
+        self.last_stats = {"replays": replays, "captures": self.captures, "launches": smp.launches, "kernel": smp.kernel_name, "plan": smp.plan,
+                           "nfev": smp.nlaunch - 1, "rows": pts.shape[0] * K, "uploaded_src": uploaded, "uploaded_fallback": fresh}
+        lo = 0
+        for i in live:
+            c = int(frames[i][0].shape[0])
+            sl = slice(lo, lo + c)
+            lo += c
+            self.buffers[i] = list(frames[i][1])
+            self.frame_index[i] += 1
+            out[i] = {"init_x": init_x[sl], "pred_pose": pred[sl], "energy": energy[sl], "sorted_RTs": sorted_RTs[sl], "average_sRT": average_sRT[sl].clone(),
+                      "nfev": smp.nlaunch - 1}
+        return out

@@ -256,6 +256,38 @@ def pc_noise_fill(seed, run_index, num_steps, nrows, device, row_base=0, step0=0
     return z1, z2
 
 
+def _seed_state(seed, run_index, row_base, device):
+    seed = int(seed) % (1 << 64)
+    return torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, int(run_index), int(row_base), 0], dtype=torch.int64).to(device)
+
+
+def track_prior_fill(seed, frame_index, nrows, device, row_base=0, row0=0):
+    """The fixed-step tracker's prior draws as a buffer (gp_track_prior_fill: track_warm_start's own device function): standard normals
+    [nrows, 9] for rows row0 .. of a launch whose first row is global row `row_base`, frame `frame_index` (the seed state's run word)."""
+    dev = torch.device(device)
+    st = _seed_state(seed, frame_index, row_base, dev)
+    z = torch.empty(nrows, 9, device=dev)
+    _lib.call("gp_track_prior_fill", ptr(st), int(row0), int(nrows), ptr(z), stream_ptr())
+    return z
+
+
+def track_warm_start(seed_state, sigma, prev_sRT, src, fallback_sRT, centre, K, out=None):
+    """The tracker's start states on the device (gp_track_warm_start; evaluation_tracking.py:302-310 + samplers.py:180): for cloud i and
+    candidate k, x0[i K + k] = init_i + sigma z with init_i = [R[:,0], R[:,1], t - centre[i]] of prev_sRT[src[i]] (src[i] >= 0) or of
+    fallback_sRT[i], z the prior's draw for global row (row base + i K + k) of the seed state's frame.  seed_state: 8 uint32 words on the
+    device (csrc/philox.h); sigma: a one-element device tensor; prev_sRT, fallback_sRT [.,4,4] f32; src [n] int32; centre [n,3]."""
+    n = int(centre.shape[0])
+    for t, dt in ((sigma, torch.float32), (prev_sRT, torch.float32), (fallback_sRT, torch.float32), (centre, torch.float32), (src, torch.int32)):
+        if t.dtype != dt:
+            raise ValueError(f"track_warm_start: expected {dt}, got {t.dtype}")
+    if src.shape[0] != n or fallback_sRT.shape[0] != n:
+        raise ValueError(f"track_warm_start: {n} clouds, src {tuple(src.shape)}, fallback_sRT {tuple(fallback_sRT.shape)}")
+    if out is None:
+        out = torch.empty(n * int(K), 9, device=centre.device)
+    _lib.call("gp_track_warm_start", n, int(K), ptr(seed_state), ptr(sigma), ptr(prev_sRT), ptr(src), ptr(fallback_sRT), ptr(centre), ptr(out), stream_ptr())
+    return out
+
+
 def philox_raw(counters, keys):
     """Raw Philox4x32-10 blocks on the device: counters [n,4], keys [n,2] (int32 tensors holding the uint32 words) -> [n,4]."""
     counters, keys = counters.contiguous(), keys.contiguous()
@@ -328,10 +360,16 @@ class HeunSampler:
 
     B clouds in `groups` batches laid out back to back share each launch (a workgroup never straddles two of them); the result of a row
     does not depend on its neighbours.  trunk: as PCSampler - 'bf16x9' on the chain plan by default, 'f32mfma' for A/B.  tile: forces a
-    plan (16 / 32 / 64 tiles, 128 chain form); the head-split plan, the energy model and bf16x3 have no Heun kernel."""
+    plan (16 / 32 / 64 tiles, 128 chain form); the head-split plan, the energy model and bf16x3 have no Heun kernel.
+
+    launches: 'chain' (default) - one kernel launch per launch index; 'single' - the whole solve in ONE launch (gp_heun_solve_tile: a
+    workgroup takes its tile's rows through every index itself, tile plans only), the same bits in x, the pose and the trajectory.  nlaunch,
+    NFE and the schedule are those of the chain either way."""
+
+    LAUNCHES = ("chain", "single")
 
     def __init__(self, net, B, K, nsteps, device, groups=1, grid="geometric", rho=7.0, trunk=None, tile=None, record_traj=False, denoise=True,
-                 use_graph=True):
+                 use_graph=True, launches="chain"):
         import ctypes
         if B % groups:
             raise ValueError(f"{B} clouds do not split into {groups} equal batches")
@@ -341,6 +379,8 @@ class HeunSampler:
             raise ValueError(f"trunk {trunk!r}: 'bf16x9' or 'f32mfma'")
         if tile and int(tile) & _lib.PLAN_HEADSPLIT:
             raise NotImplementedError("the head-split plan has no Heun kernel: whole 16-row tiles serve such sizes (tile=16)")
+        if launches not in self.LAUNCHES:
+            raise ValueError(f"launches {launches!r}: one of {self.LAUNCHES}")
         self.net, self.B, self.K, self.n, self.groups = net, B, K, int(nsteps), groups
         self.grid, self.rho, self.denoise = grid, float(rho), bool(denoise)
         self.nlaunch = heun_launches(self.n, self.denoise)
@@ -351,13 +391,17 @@ class HeunSampler:
             raise ValueError(f"{B // groups} clouds x {K} candidates per batch do not split into workgroups of plan {tile or 'auto'}; "
                              "run the batches separately")
         self.plan = self.tile = t_out.value
+        if launches == "single" and self.tile == 128:
+            raise ValueError(f"launches='single' serves the tile plans (16 / 32 / 64 rows); {B} clouds x {K} candidates on plan {tile or 'auto'} "
+                             "take plan 128, the chain form, which keeps its per-launch kernels: force a tile or use launches='chain'")
+        self.launches = launches
         self.trunk = None
         if self.tile == 128:
             self.trunk = trunk or "bf16x9"
             if self.trunk == "bf16x9":
                 self._x9 = net.w.bf16x9_packs()
         self.kernel_name = ("heun_step_chain_kernel<bf16x9>" if self.trunk == "bf16x9" else "heun_step_chain_kernel<2>" if self.tile == 128
-                            else f"heun_step_kernel<{self.tile}>")
+                            else f"heun_solve_kernel<{self.tile}>" if launches == "single" else f"heun_step_kernel<{self.tile}>")
         f = lambda *s: torch.empty(*s, device=self.dev)
         self.x, self.d, self.score, self.out = f(R, 9), f(R, 9), f(R, 9), f(R, 9)
         self.cvec, self.centre = f(B, 768), f(B, 3)
@@ -403,6 +447,11 @@ class HeunSampler:
             _lib.call("gp_heun_step_plan", self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
 
     def _launch_all(self):
+        if self.launches == "single":
+            _lib.call("gp_heun_solve_tile", self.plan, self.groups, self.B // self.groups, self.K, self.n, int(self.denoise), self.net.w.ref(),
+                      ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
+                      ptr(self.traj), stream_ptr())
+            return
         for l in range(self.nlaunch):
             self.launch_step(l)
 
@@ -429,6 +478,8 @@ class HeunSampler:
                 self.captures += 1
             self.graph.replay()
         self.last_stats = {"nfev": self.nlaunch - 1, "plan": self.plan, "launches": self.nlaunch, "kernel": self.kernel_name}
+        if self.launches == "single":
+            self.last_stats["device_launches"] = 1
         xs = self.traj.permute(1, 0, 2) if self.traj is not None else None
         return xs, self.out
 

@@ -401,6 +401,19 @@ int gp_pc_step_bf16x9_seeded(int ngroups, int nclouds_per_group, int k, int step
  * step0 + nsteps - 1 and rows row0 .. row0 + nrows - 1 of a launch, [nsteps][nrows][9] each (either may be NULL), exactly what the seeded
  * step kernels draw for them (the same device function). */
 int gp_pc_noise_fill(const void *seed_state, int step0, int nsteps, int64_t row0, int64_t nrows, float *z_lang_out, float *z_pred_out, gp_stream_t s);
+/* THE TRACKER'S PRIOR ON THE DEVICE (opt-in; csrc/noise.hip).  The reference's tracking loop (evaluation_tracking.py:262-337) starts every
+ * frame's candidates at the previous frame's pose plus sigma(T0) times a standard normal draw (samplers.py:180); here the draw is the
+ * seeded generator's, on counters no PC draw uses: step field = 2^29 - 1 (PC steps stay below it), stream 0, the seed state's run word = the
+ * FRAME index, global row = row base + i * k + candidate (csrc/philox.h).
+ * gp_track_warm_start: for cloud i < n and candidate c < k, x0[i * k + c] = init_i + sigma * z, the product and the sum rounded separately
+ * (fp32 host arithmetic reproduces the bits), with init_i = [R[:,0], R[:,1], t - centre[i]] of prev_sRT[src[i]] when src[i] >= 0, else of
+ * fallback_sRT[i] (evaluation_tracking.py:302-310).  prev_sRT, fallback_sRT [.,4,4] f32 row-major; src [n] int32; centre [n][3]; sigma: ONE
+ * device float (the Heun schedule's first word, sigma(T0): a run-time value); x0 [n * k][9].
+ * gp_track_prior_fill: the same draws as a buffer, z_out [nrows][9] for rows row0 .. row0 + nrows - 1 of the launch.
+ * Both: GP_EINVAL on null pointers or negative sizes (k <= 0 included), GP_OK with nothing written for zero rows. */
+int gp_track_warm_start(int n, int k, const void *seed_state, const float *sigma, const float *prev_sRT, const int *src, const float *fallback_sRT,
+                        const float *centre, float *x0, gp_stream_t s);
+int gp_track_prior_fill(const void *seed_state, int64_t row0, int64_t nrows, float *z_out, gp_stream_t s);
 /* Raw Philox4x32-10 blocks (tests: bit-exactness against the published generator): counters [n][4], keys [n][2] -> out [n][4], uint32. */
 int gp_philox_raw(int64_t n, const void *counters, const void *keys, void *out, gp_stream_t s);
 
@@ -435,6 +448,18 @@ int gp_heun_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int l
 int gp_heun_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                         const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                         const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s);
+
+/* The WHOLE solve in one launch, tile plans (csrc/heun_solve.hip; samplers.py:230-290).  The update is row-local, so the workgroup that owns
+ * a tile's rows takes them through every launch index 0 .. gp_heun_launches(nsteps, denoise) - 1 of the chain above itself: the same row
+ * update, the same trunk, the same divisor per index in the same order - x, out and traj hold afterwards, BIT FOR BIT, what the chain of
+ * gp_heun_step_plan calls on the same plan leaves there (x = x_nsteps, out = the final pose, traj = x_1 .. x_nsteps).  Between the indices
+ * x_i and d_i stay in registers and the score in LDS: `d` and `score` must be valid buffers (the chain's contract) but are not written.
+ * sched and tvec_all are the chain's device buffers, so T0 and eps stay run-time values.  tile: 16 / 32 / 64, or 0 = gp_heun_layout's choice
+ * provided that is one of them; GP_EINVAL with nothing written for the 128-row chain form (it keeps its per-launch kernels), the head-split
+ * plan, nsteps < 1, null buffers or a plan that does not fit; zero rows: GP_OK.  Stateless, capturable. */
+int gp_heun_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                       const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                       gp_stream_t s);
 
 /* FIXED-STEP HEUN SOLVE OF THE EXACT-LIKELIHOOD ODE (opt-in; csrc/heun_likelihood.hip).  cond_ode_likelihood's system (samplers.py:22-99)
  * d[x; logp]/dt = -g^2/2 [score; div_x score] with the exact divergence of gp_score_div_exact, integrated in sigma from sigma(eps) UP to
