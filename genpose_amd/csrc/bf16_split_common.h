@@ -60,6 +60,56 @@ __device__ __forceinline__ void split_stage(float *lds, const SplitNet &w, const
     }
 }
 
+// split_stage in two phases, for a kernel that has other work between them (trunk_bf16x9.hip: the sampler update).  None of these
+// loads depends on that work: REQUEST them before it and before the weight ring's prologue (memory returns in order, so they arrive
+// under it and not behind 24 weight loads), STORE them to LDS after it.  16-byte loads: w_out | b0 | b2 are contiguous in LDS and
+// (POSE + 2) HID / 4 = 704 float4; cvt is NCL HEADS / 4 = 768 float4, each the sum of one float4 of cvec[cloud] and one of tvec - the
+// expression and the cloud clamp of split_stage, element by element.  All five arrays must be 16-byte aligned (rows of 256 / 768 floats
+// of an aligned base are; the launchers check).
+template <int NT>
+struct SplitStaged {
+    static constexpr int NW4 = (POSE + 2) * HID / 4, NC4 = NCL * HEADS / 4, H4 = HEADS / 4;
+    static constexpr int W_PER_T = (NW4 + NT - 1) / NT, C_PER_T = NC4 / NT;
+    static_assert(NC4 % NT == 0, "whole float4 rounds of cvt");
+    f32x4 wv[W_PER_T], cv[C_PER_T], tv[C_PER_T];
+};
+
+template <int NT>
+__device__ __forceinline__ void split_stage_request(SplitStaged<NT> &sg, const SplitNet &w, const float *cvec, const float *tvec, int wg_row0, int nrows,
+                                                    int kcand) {
+    using S = SplitStaged<NT>;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < S::W_PER_T; ++u) {
+        const int e = tid + u * NT;  // float4 index into w_out | b0 | b2
+        if (e < S::NW4) {
+            const float *src = e < POSE * HID / 4 ? w.w_out + 4 * e : e < (POSE + 1) * HID / 4 ? w.b0 + 4 * e - POSE * HID : w.b2 + 4 * e - (POSE + 1) * HID;
+            sg.wv[u] = *reinterpret_cast<const f32x4 *>(src);
+        }
+    }
+    const int cloud0 = wg_row0 / kcand, last_cloud = (nrows - 1) / kcand;
+#pragma unroll
+    for (int u = 0; u < S::C_PER_T; ++u) {
+        const int e = tid + u * NT, c = e / S::H4, o = e - c * S::H4;
+        const int cl = cloud0 + c < last_cloud ? cloud0 + c : last_cloud;
+        sg.cv[u] = reinterpret_cast<const f32x4 *>(cvec + (size_t)cl * HEADS)[o];
+        sg.tv[u] = reinterpret_cast<const f32x4 *>(tvec)[o];
+    }
+}
+
+template <int NT, typename L>
+__device__ __forceinline__ void split_stage_store(float *lds, const SplitStaged<NT> &sg) {
+    using S = SplitStaged<NT>;
+    static_assert(L::OFF_B0 == L::OFF_WOUT + POSE * HID && L::OFF_B2 == L::OFF_B0 + HID && L::OFF_WOUT % 4 == 0 && L::OFF_CVT % 4 == 0, "LDS layout");
+    const int tid = threadIdx.x;
+    f32x4 *wl = reinterpret_cast<f32x4 *>(lds + L::OFF_WOUT), *cvtl = reinterpret_cast<f32x4 *>(lds + L::OFF_CVT);
+#pragma unroll
+    for (int u = 0; u < S::W_PER_T; ++u)
+        if (tid + u * NT < S::NW4) wl[tid + u * NT] = sg.wv[u];
+#pragma unroll
+    for (int u = 0; u < S::C_PER_T; ++u) cvtl[tid + u * NT] = sg.cv[u] + sg.tv[u];
+}
+
 // pose_encoder.0's B operand: the row's nine components as the one (zero-padded) k-block, natural k order: lane group g holds
 // k = 8g .. 8g+7
 __device__ __forceinline__ void split_pose_fragment(const float (&xv)[9], int g, f32x4 &pa, f32x4 &pb) {

@@ -6,6 +6,8 @@
 // at 16 / 9 of its work rate (the BF16 pipe runs at 16x the fp32 one).  Unlike bf16x3.h (three of the nine products, hi / lo pairs),
 // nothing is dropped.
 #pragma once
+#include <type_traits>
+
 #include "bf16_split_common.h"
 
 namespace gp_bf16x9 {
@@ -15,23 +17,27 @@ struct Split8 {
     bf16x8 t[3];
 };
 
+// Values i and i + 1 (i even) of split8's eight: their hi / mid / lo terms into s.  Three v_cvt_pk_bf16_f32, two widenings back to fp32
+// (shifts), four subtractions - all exact but the conversions.  On its own it is the PIECE of a split that a caller issues beside MFMAs
+// (trunk_bf16x9.h: about eleven instructions).
+__device__ __forceinline__ void split8_pair(Split8 &s, const int i, const float x0, const float x1) {
+    const bf16x2 h = __builtin_convertvector(f32x2{x0, x1}, bf16x2);
+    const f32x2 hf = __builtin_convertvector(h, f32x2);
+    const float r0 = x0 - hf.x, r1 = x1 - hf.y;  // exact
+    const bf16x2 m = __builtin_convertvector(f32x2{r0, r1}, bf16x2);
+    const f32x2 mf = __builtin_convertvector(m, f32x2);
+    const bf16x2 l = __builtin_convertvector(f32x2{r0 - mf.x, r1 - mf.y}, bf16x2);  // r - mid is exact and has <= 8 bits: l == r - mid
+    s.t[0][i] = h.x, s.t[0][i + 1] = h.y;
+    s.t[1][i] = m.x, s.t[1][i + 1] = m.y;
+    s.t[2][i] = l.x, s.t[2][i + 1] = l.y;
+}
+
 // (a, b) = eight fp32 values of a lane (two D fragments: chunks 2m and 2m+1) -> the lane's eight k-values of k-block m as hi / mid / lo.
-// Per two values: three v_cvt_pk_bf16_f32, two widenings back to fp32 (shifts), four subtractions - all exact but the conversions.
 __device__ __forceinline__ Split8 split8(const f32x4 a, const f32x4 b) {
     const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     Split8 s;
 #pragma unroll
-    for (int i = 0; i < 8; i += 2) {
-        const bf16x2 h = __builtin_convertvector(f32x2{x[i], x[i + 1]}, bf16x2);
-        const f32x2 hf = __builtin_convertvector(h, f32x2);
-        const float r0 = x[i] - hf.x, r1 = x[i + 1] - hf.y;  // exact
-        const bf16x2 m = __builtin_convertvector(f32x2{r0, r1}, bf16x2);
-        const f32x2 mf = __builtin_convertvector(m, f32x2);
-        const bf16x2 l = __builtin_convertvector(f32x2{r0 - mf.x, r1 - mf.y}, bf16x2);  // r - mid is exact and has <= 8 bits: l == r - mid
-        s.t[0][i] = h.x, s.t[0][i + 1] = h.y;
-        s.t[1][i] = m.x, s.t[1][i + 1] = m.y;
-        s.t[2][i] = l.x, s.t[2][i + 1] = l.y;
-    }
+    for (int i = 0; i < 8; i += 2) split8_pair(s, i, x[i], x[i + 1]);
     return s;
 }
 
@@ -62,16 +68,26 @@ __device__ __forceinline__ void ring_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// no side work beside a ring step's MFMAs
+struct RingNoSide {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+
 // One step of the two-slot LDS ring every bf16x9 kernel streams its weights through (slice = chunks x (hi, mid, lo) x 64 lanes of
 // bf16x8; NTH threads, PER_T slice elements per thread), over the slice in `slot`: for chunk n < NCH of the slice (output chunk N0 + n
 // of acc), the three weight terms (read one chunk ahead) x the two row tiles' split k-block = 18 MFMAs; beside chunk n < PER_T, element
 // n of the next slice goes from the registers (`hold`, requested a step ago) to the other slot `dst` (last read one step ago) and
 // element n of the slice after it, `src`, is requested; one barrier.  The caller keeps the ring's position and names the three slices.
 // `first`: the step opens its accumulators (acc = W . X, mma9).
-template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NA>
+// `side(n)`: the caller's piece of other work for chunk n - values that are already final (the split of the NEXT k-block, an epilogue of
+// chunks < n of a layer's last step); it must not touch acc[.][N0 + n].  With a side, the chunk's 18 MFMAs take at most two other
+// instructions behind each (ring_half_step's placement), so the piece goes BETWEEN them; without one the region is left to the scheduler
+// as before (sa_bf16x9.hip's kernels: several waves per SIMD fill each other's bursts).
+template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NA, class Side = RingNoSide>
 __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], const Split8 (&xs)[2],
-                                          f32x4 (&acc)[2][NA], int tid, int lane, bool first = false) {
+                                          f32x4 (&acc)[2][NA], int tid, int lane, bool first = false, Side side = Side()) {
     static_assert(NCH >= PER_T && N0 + NCH <= NA, "every slice element moves beside a chunk");
+    constexpr bool SIDE = !std::is_same<Side, RingNoSide>::value;
     bf16x8 wf[2][3];
 #pragma unroll
     for (int t = 0; t < 3; ++t) wf[0][t] = slot[t * 64 + lane];
@@ -85,9 +101,17 @@ __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const
             dst[tid + n * NTH] = hold[n];
             hold[n] = src[tid + n * NTH];
         }
+        if constexpr (SIDE) side(n);
         f32x4 an[2] = {acc[0][N0 + n], acc[1][N0 + n]};
         mma9<2, TRANSPOSED>(wf[n & 1], xs, an, first);
         acc[0][N0 + n] = an[0], acc[1][N0 + n] = an[1];
+        if constexpr (SIDE) {
+#pragma unroll
+            for (int i = 0; i < 18; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+                __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);  // VALU | SALU | VMEM | DS
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the step
     }
     ring_barrier();

@@ -7,7 +7,17 @@
 // is split once into 192 registers that all three heads read, 16 accumulator registers are live, and a chunk's fp32 epilogue is issued
 // between the MFMAs of the next chunk.  Every accumulator takes its k-blocks ascending and every head output its chunks ascending in
 // both orders: the bits are those of k-major heads (tests/test_gpu_x9_chain_bits.py).
+// One wave per SIMD: an instruction that is not placed between MFMAs is exposed.  So the k-major layers' own fp32 work rides beside their
+// MFMAs too (ring_step's side hook, at most two other instructions behind each MFMA): pose_encoder.0's bias + ReLU chunk by chunk, the
+// split of k-block kb + 1 during step kb, and pose_encoder.2's bias + ReLU + split tail pair by pair during its last step (the last pair
+// on the first head chunk) - run<KSIDE>.  Same expressions on the same values, same summation orders: the bits do not move
+// (tests/test_gpu_x9_chain_bits.py, tests/test_gpu_x9_chain_bits_more.py).  Still exposed (profiles/x9_kmajor_under_mfma.txt): the
+// prologue up to the first MFMA (sampler update, slot 0), the part of the tail that does not fit two-per-MFMA (14 runs of 39-49
+// instructions at the chunk ends of pose_encoder.2's last step, 124 before the first head chunk), the head loop's short runs, the last
+// head's last chunk.
 //   request : slices 0 and 1 into registers - the caller places it among its own loads (memory returns in order)
+//   stage_request : the staged fp32 operands (w_out, b0, b2, cvec[cloud] + tvec) into registers, for a caller that has work of its own
+//             before run() - issued BEFORE request, they arrive under that work instead of behind the 24 weight loads
 //   run     : staged fp32 operands, slot 0, the layers, and once per head and tile, heads ascending, its fp32 Linear(256, 3) outputs
 //             handed to the caller's functor (the callers store at once: carrying the nine outputs to the end costs 27-40 more spilled
 //             registers, profiles/r9_rk45_bf16x9_resources.txt); heads 0 and 1 hand over beside the next head's first MFMAs
@@ -56,68 +66,159 @@ __device__ __forceinline__ void request(const SplitNet &w, int tid, bf16x8 (&fir
 // xv: the nine pose components of the lane's row in each of its two tiles; row: that row (rows >= nrows are clamped duplicates);
 // tvec: the step's / stage's 768 time-embedding outputs.  emit(head, tile, out): out[c] = output 3 head + c of the row, bias included, in
 // every lane of the row.
-template <class Emit>
+// sg: the staged fp32 operands in registers (stage_request) when the caller asked for them ahead of its own work, nullptr when run() is
+// to fetch them itself (split_stage).
+using X9Staged = SplitStaged<X9_NT>;
+__device__ __forceinline__ void stage_request(X9Staged &sg, const SplitNet &w, const float *cvec, const float *tvec, int wg_row0, int nrows, int kcand) {
+    split_stage_request<X9_NT>(sg, w, cvec, tvec, wg_row0, nrows, kcand);
+}
+
+// KSIDE: how much of the k-major layers' fp32 work rides beside their MFMAs.  0 (the default; rk45.hip's stage kernels): nothing, the
+// plain form - their f64 stage state leaves no room for the second live split (stages 6 and 7 would take 12-36 B more scratch).
+// 1 (the Heun step): all but pose_encoder.2's tail - with it that kernel parks 117 values in AGPRs instead of 76 and loses what the
+// rest gains.  2 (the PC kernels): all of it.  (profiles/x9_kmajor_under_mfma.txt)
+template <int KSIDE = 0, class Emit, class Staged = std::nullptr_t>
 __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *cvec, const float *tvec, int wg_row0, int nrows, int kcand,
                                     const bf16x8 (&first)[X9_PER_T], bf16x8 (&hold)[X9_PER_T], const float (&xv)[X9_RT][POSE],
-                                    const int (&row)[X9_RT], Emit emit) {
+                                    const int (&row)[X9_RT], Emit emit, const Staged &sg = nullptr) {
     bf16x8 *ring = reinterpret_cast<bf16x8 *>(lds);
     const float *woutl = lds + X9Lds::OFF_WOUT, *b0l = lds + X9Lds::OFF_B0, *b2l = lds + X9Lds::OFF_B2, *cvtl = lds + X9Lds::OFF_CVT;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
     // ---- staged epilogue operands and slot 0
-    split_stage<X9_NT, X9Lds>(lds, w, cvec, tvec, wg_row0, nrows, kcand);
+    if constexpr (std::is_same<Staged, X9Staged>::value) split_stage_store<X9_NT, X9Lds>(lds, sg);
+    else split_stage<X9_NT, X9Lds>(lds, w, cvec, tvec, wg_row0, nrows, kcand);
 #pragma unroll
     for (int u = 0; u < X9_PER_T; ++u) ring[tid + u * X9_NT] = first[u];
     __syncthreads();
     int gstep = 0;
     f32x4 acc[X9_RT][16];
-    // one ring step over slot gstep % 2: slice gstep + 1 goes from the registers to the other slot, slice gstep + 2 is requested
-    // (the position advances BEFORE the call: after it, the kernels keep 20-68 B of scratch, profiles/r11_shared_ring_stage_resources.txt)
-    auto step = [&](const Split8 (&xs)[X9_RT], bool first) {  // first: the layer's first k-block opens the accumulators (no zeroing pass)
-        const int gs = gstep++;
-        ring_step<X9_NT, X9_PER_T, false, 0, 16>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
-                                                 tid, lane, first);
-    };
-    // bias + ReLU of a 256-wide hidden layer, kept in fp32 (split one k-block at a time as the next layer consumes it)
     f32x4 act[X9_RT][16];
-    auto hidden = [&](const float *bias) {
+    if constexpr (KSIDE == 0) {
+        // the plain form (the text rk45.hip's resource table was taken with): bias + ReLU between the layers, each k-block split before its step
+        auto step = [&](const Split8 (&xs)[X9_RT], bool first) {
+            const int gs = gstep++;
+            ring_step<X9_NT, X9_PER_T, false, 0, 16>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
+                                                     tid, lane, first);
+        };
+        auto hidden = [&](const float *bias) {
 #pragma unroll
-        for (int n = 0; n < 16; ++n) {
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + 16 * n + 4 * g);
+            for (int n = 0; n < 16; ++n) {
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + 16 * n + 4 * g);
 #pragma unroll
-            for (int p = 0; p < X9_RT; ++p) act[p][n] = relu4(acc[p][n] + bv);
-        }
-    };
-    auto layer = [&]() {  // acc = W . act over the 8 k-blocks of a 256-wide input
+                for (int p = 0; p < X9_RT; ++p) act[p][n] = relu4(acc[p][n] + bv);
+            }
+        };
+        auto layer = [&]() {  // acc = W . act over the 8 k-blocks of a 256-wide input
 #pragma unroll
-        for (int kb = 0; kb < 8; ++kb) {
+            for (int kb = 0; kb < 8; ++kb) {
+                Split8 xs[X9_RT];
+#pragma unroll
+                for (int p = 0; p < X9_RT; ++p) xs[p] = split8(act[p][2 * kb], act[p][2 * kb + 1]);
+                step(xs, kb == 0);
+            }
+        };
+        {
             Split8 xs[X9_RT];
 #pragma unroll
-            for (int p = 0; p < X9_RT; ++p) xs[p] = split8(act[p][2 * kb], act[p][2 * kb + 1]);
-            step(xs, kb == 0);
+            for (int p = 0; p < X9_RT; ++p) {
+                f32x4 pa, pb;
+                split_pose_fragment(xv[p], g, pa, pb);
+                xs[p] = split8(pa, pb);
+            }
+            step(xs, true);
         }
-    };
-    // ---- pose_encoder.0
-    {
-        Split8 xs[X9_RT];
-#pragma unroll
-        for (int p = 0; p < X9_RT; ++p) {
-            f32x4 pa, pb;
-            split_pose_fragment(xv[p], g, pa, pb);
-            xs[p] = split8(pa, pb);
-        }
-        step(xs, true);
+        hidden(b0l);
+        layer();
     }
-    hidden(b0l);
-    // ---- pose_encoder.2
-    layer();
-    // ---- its output (bias + ReLU) split ONCE, all eight k-blocks: the B operand of every head chunk.  192 registers that take the place of
-    // both the fp32 activations and the 128 accumulators of a k-major head
+    // pose_encoder.2's output (bias + ReLU) split ONCE, all eight k-blocks: the B operand of every head chunk.  192 registers that take the
+    // place of both the fp32 activations and the 128 accumulators of a k-major head
     Split8 xs_all[8][X9_RT];
+    // its pieces: tail_read(m) asks LDS for the biases of chunks 2m and 2m + 1, tail_piece(m, q) is one eighth (tile q / 4, values 2 (q % 4),
+    // + 1) of xs_all[m] = split8(relu4(acc[.][2m] + ba), relu4(acc[.][2m + 1] + bb))
+    f32x4 tb[2][2];
+    auto tail_read = [&](int m) {
+        tb[m & 1][0] = *reinterpret_cast<const f32x4 *>(b2l + 32 * m + 4 * g), tb[m & 1][1] = *reinterpret_cast<const f32x4 *>(b2l + 32 * m + 16 + 4 * g);
+    };
+    auto tail_piece = [&](int m, int q) {
+        const int p = q >> 2, i = 2 * (q & 3), j = i & 3;
+        const f32x4 a = acc[p][2 * m + (i >> 2)], b = tb[m & 1][i >> 2];
+        split8_pair(xs_all[m][p], i, fmaxf(plain(a[j] + b[j]), 0.f), fmaxf(plain(a[j + 1] + b[j + 1]), 0.f));
+    };
+    if constexpr (KSIDE == 0) {  // (written out in place, after the layers: the order rk45.hip's resource table was taken with)
 #pragma unroll
-    for (int kb = 0; kb < 8; ++kb) {
-        const f32x4 ba = *reinterpret_cast<const f32x4 *>(b2l + 32 * kb + 4 * g), bb = *reinterpret_cast<const f32x4 *>(b2l + 32 * kb + 16 + 4 * g);
+        for (int kb = 0; kb < 8; ++kb) {
+            const f32x4 ba = *reinterpret_cast<const f32x4 *>(b2l + 32 * kb + 4 * g), bb = *reinterpret_cast<const f32x4 *>(b2l + 32 * kb + 16 + 4 * g);
 #pragma unroll
-        for (int p = 0; p < X9_RT; ++p) xs_all[kb][p] = split8(relu4(acc[p][2 * kb] + ba), relu4(acc[p][2 * kb + 1] + bb));
+            for (int p = 0; p < X9_RT; ++p) xs_all[kb][p] = split8(relu4(acc[p][2 * kb] + ba), relu4(acc[p][2 * kb + 1] + bb));
+        }
+    } else {
+        // one ring step over slot gstep % 2: slice gstep + 1 goes from the registers to the other slot, slice gstep + 2 is requested
+        // (the position advances BEFORE the call: after it, the kernels keep 20-68 B of scratch, profiles/r11_shared_ring_stage_resources.txt);
+        // side(n): the caller's piece of other work beside the MFMAs of output chunk n (bf16x9.h).  first: the layer's first k-block opens
+        // the accumulators (no zeroing pass)
+        auto step = [&](const Split8 (&xs)[X9_RT], bool first, auto side) {
+            const int gs = gstep++;
+            ring_step<X9_NT, X9_PER_T, false, 0, 16>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
+                                                     tid, lane, first, side);
+        };
+        // The k-major layers keep their 256-wide input in fp32 (act) and split it one k-block at a time.  Nothing of that is issued between two
+        // layers or two steps: every piece rides beside the MFMAs of a chunk that does not need it yet (one wave per SIMD - what is not placed
+        // between MFMAs is exposed).
+        //   bias0(n)        act[.][n] = relu(acc[.][n] + b0) of pose_encoder.0's chunk n, final after its own 18 MFMAs: beside chunk n + 1 (chunk
+        //                   15: beside chunk 0 of pose_encoder.2's first step, which reopens acc[.][15] only at ITS chunk 15); the bias is read
+        //                   from LDS a piece ahead
+        //   split_piece     one eighth (tile q / 4, values 2 (q % 4), + 1) of split8(act[.][2 kb], act[.][2 kb + 1]): k-block kb + 1 beside
+        //                   chunks 1-8 of step kb, k-block 0 beside chunks 3-10 of pose_encoder.0 - a step starts with its operand ready
+        // The expressions and their order per value are those of relu4(acc + b) and split8: the bits do not move.
+        f32x4 bv;
+        Split8 xs[2][X9_RT];
+        auto bias_read = [&](const float *bias, int n) { bv = *reinterpret_cast<const f32x4 *>(bias + 16 * n + 4 * g); };
+        auto bias0 = [&](int n) {
+#pragma unroll
+            for (int p = 0; p < X9_RT; ++p) act[p][n] = relu_sum4(acc[p][n], bv);
+        };
+        auto split_piece = [&](Split8 (&x)[X9_RT], int kb, int q) {
+            const int p = q >> 2, i = 2 * (q & 3);
+            const f32x4 v = act[p][2 * kb + (i >> 2)];
+            split8_pair(x[p], i, v[i & 3], v[(i & 3) + 1]);
+        };
+        // ---- pose_encoder.0
+        {
+            Split8 x0[X9_RT];
+#pragma unroll
+            for (int p = 0; p < X9_RT; ++p) {
+                f32x4 pa, pb;
+                split_pose_fragment(xv[p], g, pa, pb);
+                x0[p] = split8(pa, pb);
+            }
+            step(x0, true, [&](int n) {
+                if (n >= 1) bias0(n - 1);
+                bias_read(b0l, n);
+                if (n >= 3 && n < 11) split_piece(xs[0], 0, n - 3);
+            });
+        }
+        // ---- pose_encoder.2: acc = W . act over the 8 k-blocks of its 256-wide input
+#pragma unroll
+        for (int kb = 0; kb < 8; ++kb)
+            step(xs[kb & 1], kb == 0, [&](int n) {
+                if (kb == 0 && n == 0) bias0(15);
+                if (kb < 7 && n >= 1 && n < 9) split_piece(xs[(kb + 1) & 1], kb + 1, n - 1);
+                if (KSIDE == 2 && kb == 7) {  // the tail: pair m is final after chunk 2m + 1 - its tile 0 beside chunk 2m + 2, its tile 1 beside chunk 2m + 3
+                    if (n >= 2) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) tail_piece((n - 2) >> 1, 4 * (n & 1) + q);
+                    }
+                    if (n & 1) tail_read(n >> 1);  // a chunk ahead of its first use
+                }
+            });
+        if constexpr (KSIDE < 2) {  // the tail in one block after the layer
+#pragma unroll
+            for (int kb = 0; kb < 8; ++kb) {
+                const f32x4 ba = *reinterpret_cast<const f32x4 *>(b2l + 32 * kb + 4 * g), bb = *reinterpret_cast<const f32x4 *>(b2l + 32 * kb + 16 + 4 * g);
+#pragma unroll
+                for (int p = 0; p < X9_RT; ++p) xs_all[kb][p] = split8(relu4(acc[p][2 * kb] + ba), relu4(acc[p][2 * kb + 1] + bb));
+            }
+        }
     }
     // ---- the three heads, CHUNK-MAJOR: a slice is (two output chunks) x (eight k-blocks), a chunk's two accumulator tiles are final after
     // its 144 MFMAs, and its share of the fp32 Linear(256, 3) output layer - bias + ReLU against cvt, then o += v . w_out, chunks ascending,
@@ -170,7 +271,9 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
     };
     constexpr std::integral_constant<int, 0> c0{};
     constexpr std::integral_constant<int, 1> c1{};
-    chunk(c0, [](int) {});
+    chunk(c0, [&](int k) {  // xs_all[7] (final only now) is not read before sub-block 7
+        if (KSIDE == 2 && k < 4) tail_piece(7, 2 * k), tail_piece(7, 2 * k + 1);
+    });
 #pragma unroll 1
     for (int h = 0; h < 3; ++h) {
 #pragma unroll

@@ -20,11 +20,18 @@
 //                       peak clock; dense BF16 MFMA loops on random data sustain 1.5-1.95 GHz on this part: 80 us at 1.9 GHz)
 // so the matrix pipe bounds it, not LDS (bf16x3's 8 waves x 16 rows read the same 1.5 MB weight stream twice as often per row) and not
 // the fp32 peak: 9 bf16 products per fp32 product at 16x the fp32 rate = 1.8x the fp32 MFMA FLOP rate.
-// Measured (MI355X, 32 000 rows, HIP events around the PC-100 graph, profiles/x9_heads_chunk_major.txt): 100.3 us per launch, against
-// 103.8 us with k-major heads in the same session (118.0 us under rocprofv3 when it replaced the 142.7 us of pc_step_chain_kernel<2, 0>).
-// The head epilogues now sit between the MFMAs of the following chunk; what is left of the gap to the floor - 80 us at a sustained
-// 1.9 GHz (the clock inside the kernel has not been measured) - is barrier drains (one wave per SIMD), the splits of the two k-major
-// layers, pose_encoder.2's bias + ReLU + split tail (one run of ~800 instructions without an MFMA) and the last head's last chunk.
+// Measured (MI355X, 32 000 rows, HIP events around the PC-100 graph): 100.3 us per launch with chunk-major heads against 103.8 us with
+// k-major heads (profiles/x9_heads_chunk_major.txt); 98.2 us against 102.3 us in one session (profiles/x9_kmajor_under_mfma.txt) with
+//   - the staged fp32 operands (w_out, b0, b2, cvec[cloud] + tvec) requested BEFORE the weight ring's prologue and the sampler update
+//     and stored to LDS after it (stage_request; 16-byte loads): -2.5 us, the larger part - they used to queue behind 24 weight loads and
+//     were waited for at the first barrier;
+//   - the k-major layers' splits and pose_encoder.0's bias + ReLU between their MFMAs: -1.0 us;
+//   - pose_encoder.2's bias + ReLU + split tail in pieces beside its last step's MFMAs: -0.5 us on the PC kernels; the Heun kernel runs
+//     without it (run<1>: with it 117 values parked in AGPRs against 76 and its pass is no faster than the parent's).
+// Headline blocks 36.04-36.17 ms against 36.94-37.09 ms (-2.4 %); 98.7 against 102.9 us under rocprofv3; MFMA-busy cycles equal.
+// What is left of the gap to the floor - 80 us at a sustained 1.9 GHz (the clock inside the kernel has not been measured) - is the
+// prologue up to the first MFMA (~1 800 static instructions, both branch arms), barrier drains (one wave per SIMD), the half of the tail
+// that does not fit two-per-MFMA, the head loop's short runs and the last head's last chunk.
 #include "pc_rows.h"
 #include "trunk_bf16x9.h"
 #include "trunk_chain.h"
@@ -46,23 +53,34 @@ __device__ __forceinline__ void pc_step_chain_bf16x9(const Args &a, const SplitN
     // ---- the rows' operands first, the ring prologue behind them (memory returns in order)
     PcRows<X9_RT, SEEDED, HEUN> rs;
     rs.template request<X9_NW>(a, wave, lane);
+    const float *tvec = a.tvec_all + (size_t)pc_time_row<HEUN>(i) * HEADS;
+    X9Staged sg;
     bf16x8 first[X9_PER_T], hold[X9_PER_T];
-    if (i < a.nsteps) request(w, tid, first, hold);
+    if (i < a.nsteps) {
+        stage_request(sg, w, a.cvec, tvec, wg_row0, a.nrows, a.kcand);  // nothing of it depends on the update: it arrives under it
+        request(w, tid, first, hold);
+    }
     if (rs.finish_previous(a, lane)) return;
     // each head's three score components are final once its epilogue is done: stored there, their squares summed in component order
     const float sden = rs.sigma + 1e-7f;
     float q[X9_RT] = {};
-    run(lds, w, a.cvec, a.tvec_all + (size_t)pc_time_row<HEUN>(i) * HEADS, wg_row0, a.nrows, a.kcand, first, hold, rs.xv, rs.row,
+    run<HEUN ? 1 : 2>(lds, w, a.cvec, tvec, wg_row0, a.nrows, a.kcand, first, hold, rs.xv, rs.row,
         [&](int h, int p, const float (&out)[3]) __attribute__((always_inline)) {
             const float sc[3] = {out[0] / sden, out[1] / sden, out[2] / sden};
             pc_store_score(a, rs.row[p], lane, 3 * h, sc, q[p]);
-        });
+        }, sg);
     if constexpr (!HEUN) pc_store_partial<X9_RT, X9_NW>(a, rs.row, q, wave, lane);
 }
 
 __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<false>(a, w); }
 __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_seeded_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<true>(a, w); }
 __global__ __launch_bounds__(X9_NT, 1) void heun_step_chain_kernel_bf16x9(HeunArgs a, SplitNet w) { pc_step_chain_bf16x9<false, true>(a, w); }
+
+// stage_request reads the staged fp32 operands with 16-byte loads
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool staged_aligned(const gp_scorenet *net, const float *cvec, const float *tvec_all) {
+    return aligned16(net->b_pose0) && aligned16(net->b_pose2) && aligned16(net->w_out) && aligned16(cvec) && aligned16(tvec_all);
+}
 
 // What the two entry points share: the chain plan's rules, PcArgs / SplitNet, the once-per-kernel LDS attribute and the launch.
 // z_lang carries the Langevin noise or, for the seeded kernel, the seed state (PcArgs).
@@ -72,7 +90,7 @@ int launch_pc_bf16x9(K kern, bool &attr_done, int ngroups, int nclouds_per_group
                      float *score, float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
                      const void *w_headx_x9, gp_stream_t s) {
     if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || step < 0 || step > nsteps || !net || !cvec || !tvec_all || !sched || !z_lang || !centre || !x ||
-        !mean_x || !score || !partials || gn_rows_total < 0 || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9)
+        !mean_x || !score || !partials || gn_rows_total < 0 || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9 || !staged_aligned(net, cvec, tvec_all))
         return GP_EINVAL;
     const int rg = nclouds_per_group * k;
     if (ngroups * rg == 0) return GP_OK;
@@ -121,7 +139,7 @@ int gp_heun_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, i
                         const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                         const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
     if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_heun_launches(nsteps, denoise) || !net || !cvec ||
-        !tvec_all || !sched || !centre || !x || !d || !score || !out || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9)
+        !tvec_all || !sched || !centre || !x || !d || !score || !out || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9 || !staged_aligned(net, cvec, tvec_all))
         return GP_EINVAL;
     const int rg = nclouds_per_group * k;
     if (ngroups * rg == 0) return GP_OK;

@@ -348,7 +348,9 @@ int gp_pc_layout_bf16x3(int ngroups, int nclouds_per_group, int k, int *nparts_o
  * in natural k order, pose_encoder.2 [8][16][3][64][8] (k-block, output chunk) in the register chain's k order; the stacked heads in the
  * order the kernel consumes them, [head 3][chunk pair 8][chunk 2][k-block 8][3][64][8] - pack_heads_bf16x9, a permutation of
  * pack_bf16x9(W, 48, 8); this w_headx_x9 layout holds for every gp_*_bf16x9 entry point); biases and output layers
- * from `net`.  The default for that plan (genpose_amd/samplers.py); gp_pc_step_plan keeps the fp32-MFMA chain kernel. */
+ * from `net`.  The default for that plan (genpose_amd/samplers.py); gp_pc_step_plan keeps the fp32-MFMA chain kernel.
+ * ALIGNMENT: cvec, tvec_all and net->b_pose0, b_pose2, w_out must be 16-byte aligned (the kernel stages them with 16-byte loads; rows of
+ * 256 / 768 floats of an aligned base are); GP_EINVAL otherwise.  The same holds for gp_pc_step_bf16x9_seeded and gp_heun_step_bf16x9. */
 int gp_pc_step_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec, const float *tvec_all,
                       const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score,
                       float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
