@@ -8,6 +8,8 @@
 // the trunk's block (21 floats per row, component-major: kept in registers they stay live across the whole trunk and the 64-row tile
 // spills), the score in the trunk's block itself, where the row thread divides it.  No global store of this kernel is read back by it, so nothing here needs an ordering
 // beyond the workgroup barriers below.  d and score are not written.
+// SOLVER_DPM2M (dpm2m_solve_kernel, gp_dpm2m_solve_tile): the same loop over the launch indices of the DPM-Solver++(2M) chain (pc_rows.h;
+// dpm2m_step_kernel) - its schedule rows, dpm2m_update_row, the time row of the index itself; the slot of d_i holds D_{i-1}.
 #include "pc_rows.h"
 
 namespace {
@@ -19,9 +21,10 @@ using namespace gp_trunk;
 // whole trunk (256 VGPRs and up to 118 spilled registers per lane, against the per-launch kernels' 128 - 184 and none).
 __device__ __forceinline__ void opaque(const float *&p) { asm volatile("" : "+s"(p)); }
 
-template <int P>
-__global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a, const gp_scorenet net0) {
+template <int P, int SOLVER>
+__device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) {
     using L = TrunkLds<P>;
+    constexpr int SROW = fixed_sched_row<SOLVER>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int row0 = blockIdx.x * P, tid = threadIdx.x, last = a.nsteps;
     const bool live = row0 + tid < a.nrows;
@@ -36,7 +39,7 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a,
     }
     float sigma_prev = 1.f;  // the divisor of the score that sits in LDS
     for (int l = 0; l <= last; ++l) {
-        const float *tvec = a.tvec_all + (size_t)pc_time_row<true>(l) * HEADS;
+        const float *tvec = a.tvec_all + (size_t)pc_time_row<SOLVER>(l) * HEADS;
         gp_scorenet net = net0;
         opaque(net.w_pose0), opaque(net.b_pose0), opaque(net.w_pose2), opaque(net.b_pose2), opaque(net.w_headx), opaque(net.w_out), opaque(net.b_out);
         opaque(a.cvec);
@@ -44,7 +47,7 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a,
         float sigma = 1.f;
         if (l < last) {
             trunk_begin<P>(net, pre, a.cvec, tvec, row0, a.nrows, a.kcand);
-            sigma = a.sched[(size_t)l * 4 + 0];  // requested now, used after the trunk
+            sigma = a.sched[(size_t)l * SROW + 0];  // requested now, used after the trunk
             gp_pin(sigma);
         }
         if (tid < P) {
@@ -52,19 +55,33 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a,
 #pragma unroll
             for (int j = 0; j < 9; ++j) ev[j] = mine[j * P];
             if (l > 0) {
-                const float *sc = a.sched + (size_t)l * 4;
+                const float *sc = a.sched + (size_t)l * SROW;
                 const int kind = (int)sc[3];
                 const float c = sc[1], h = sc[2];
                 // the previous index's f_theta (all of trunk_ftheta's barriers are behind us); the chain stores this quotient and reloads it
                 const float *F = lds + L::OFF_H1 + tid * L::LDH;
                 float gr[9], dv[9];
+                if constexpr (SOLVER == SOLVER_DPM2M) {
+                    const bool has_d = (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) && sc[5] != 0.f;
 #pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    gr[j] = F[j] / (sigma_prev + 1e-7f);
-                    dv[j] = kind == HEUN_CORRECT || kind == HEUN_CORRECT_LAST ? mine[(9 + j) * P] : 0.f;
+                    for (int j = 0; j < 9; ++j) {
+                        gr[j] = F[j] / (sigma_prev + 1e-7f);
+                        dv[j] = has_d ? mine[(9 + j) * P] : 0.f;
+                    }
+                    dpm2m_update_row(kind, ev, dv, gr, c, h, sc[4], sc[5]);
+                    if (kind == DPM2M_STEP) {  // parks D_{l-1} for the next index
+#pragma unroll
+                        for (int j = 0; j < 9; ++j) mine[(9 + j) * P] = dv[j];
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) {
+                        gr[j] = F[j] / (sigma_prev + 1e-7f);
+                        dv[j] = kind == HEUN_CORRECT || kind == HEUN_CORRECT_LAST ? mine[(9 + j) * P] : 0.f;
+                    }
+                    heun_update_row(kind, ev, dv, gr, c, h);
                 }
-                heun_update_row(kind, ev, dv, gr, c, h);
-                if (kind == HEUN_PREDICT) {  // keeps x_i (the chain never stores the Euler point) and parks d_i
+                if (SOLVER == SOLVER_HEUN && kind == HEUN_PREDICT) {  // keeps x_i (the chain never stores the Euler point) and parks d_i
 #pragma unroll
                     for (int j = 0; j < 9; ++j) mine[(9 + j) * P] = dv[j];
                 } else {
@@ -76,7 +93,7 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a,
                         const float cen[3] = {mine[18 * P], mine[19 * P], mine[20 * P]};
                         HeunArgs al = a;
                         al.step = l, al.d = nullptr;
-                        heun_store_row(al, kind, r, ev, dv, cen);
+                        heun_store_row<SOLVER>(al, kind, r, ev, dv, cen);
                     }
                 }
             }
@@ -94,6 +111,15 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a,
     }
 }
 
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a, const gp_scorenet net0) {
+    heun_solve<P, SOLVER_HEUN>(a, net0);
+}
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_solve_kernel(HeunArgs a, const gp_scorenet net0) {
+    heun_solve<P, SOLVER_DPM2M>(a, net0);
+}
+
 // the trunk's block and 21 floats per row behind it
 template <int P>
 constexpr size_t solve_lds_bytes() {
@@ -108,6 +134,17 @@ int launch_solve(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t
         attr_done = true;
     }
     hipLaunchKernelGGL((heun_solve_kernel<P>), dim3(nwg), dim3(TrunkCfg<P>::NT), solve_lds_bytes<P>(), st, a, *net);
+    return gp_launch_status();
+}
+
+template <int P>
+int launch_dpm2m_solve(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(dpm2m_solve_kernel<P>, solve_lds_bytes<P>())) return GP_ELAUNCH;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((dpm2m_solve_kernel<P>), dim3(nwg), dim3(TrunkCfg<P>::NT), solve_lds_bytes<P>(), st, a, *net);
     return gp_launch_status();
 }
 
@@ -131,4 +168,24 @@ extern "C" int gp_heun_solve_tile(int tile, int ngroups, int nclouds_per_group, 
     if (P == 16) return launch_solve<16>(a, net, nwg, st);
     if (P == 32) return launch_solve<32>(a, net, nwg, st);
     return launch_solve<64>(a, net, nwg, st);
+}
+
+extern "C" int gp_dpm2m_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                                   const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                                   gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
+        return GP_EINVAL;
+    const long long rg = (long long)nclouds_per_group * k, R = ngroups * rg;
+    if (R > 0x7fffffffLL / 9) return GP_EINVAL;  // row and element indices are ints up to R * 9
+    if (R == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
+    if (rc != GP_OK) return rc;
+    if (P != 16 && P != 32 && P != 64) return GP_EINVAL;  // the chain form keeps its per-launch kernels
+    const HeunArgs a = heun_args((int)R, k, 0, gp_dpm2m_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    hipStream_t st = (hipStream_t)s;
+    const int nwg = ngroups * (int)((rg + P - 1) / P);
+    if (P == 16) return launch_dpm2m_solve<16>(a, net, nwg, st);
+    if (P == 32) return launch_dpm2m_solve<32>(a, net, nwg, st);
+    return launch_dpm2m_solve<64>(a, net, nwg, st);
 }

@@ -77,14 +77,38 @@ static inline HeunArgs heun_args(int nrows, int k, int launch, int last_launch, 
     a.x = x, a.d = d, a.score = score, a.out = out, a.traj = traj;
     return a;
 }
-// the row of tvec_all a launch evaluates at
-template <bool HEUN>
-__device__ __forceinline__ int pc_time_row(int step) {
-    return HEUN ? (step + 1) >> 1 : step;
+// The DPM-Solver++(2M) fixed-step solver (dpm2m_update_row, score_trunk.h) runs on the same launch shape, arguments and buffers: SOLVER
+// below is a template value of the kernels' shared code, HeunArgs serve both.  With N steps there are N + 1 launches (+ 1 with denoise):
+// launch 0 evaluates score(x_0, t_0); launch i = 1 .. N forms x_i from the stored score, x_{i-1} and D_{i-2}, stores x_i, D_{i-1} (in `d`,
+// whose role between launches that is) and traj[i-1] and evaluates at (x_i, t_i) - unless it is the last; with denoise launch N's
+// evaluation at (x_N, eps) is the denoising one and launch N + 1 applies it.  The time row a launch evaluates is its own index.  Its
+// schedule is a table of its own, one row of DPM2M_SCHED floats per launch:
+//     [0] sigma of the launch's evaluation (the score's divisor)   [3] kind (DPM2M_*)
+//     [1] sigma_{i-1}^2             (DPM2M_DENOISE: g(eps))           [4] the weight of D_{i-1} times -expm1(-h_{i-1})
+//     [2] sigma_i / sigma_{i-1}     (DPM2M_DENOISE: the step)         [5] the weight of D_{i-2} times -expm1(-h_{i-1}); 0: there is none
+// (launch i's update is step i-1 of the method).  A zero in [5] marks the first step: D_{i-2} does not exist and `d` is not read.
+enum { SOLVER_PC = 0, SOLVER_HEUN = 1, SOLVER_DPM2M = 2 };
+constexpr int DPM2M_SCHED = 8;
+template <int SOLVER>
+constexpr int fixed_sched_row() {
+    static_assert(SOLVER == SOLVER_HEUN || SOLVER == SOLVER_DPM2M, "the fixed-step solvers");
+    return SOLVER == SOLVER_DPM2M ? DPM2M_SCHED : 4;
 }
-// what a Heun launch stores for a live row after heun_update_row (one thread per row)
+// the row of tvec_all a launch evaluates at (a bool reads as SOLVER_PC / SOLVER_HEUN)
+template <int SOLVER>
+__device__ __forceinline__ int pc_time_row(int step) {
+    return SOLVER == SOLVER_HEUN ? (step + 1) >> 1 : step;
+}
+// what a Heun launch stores for a live row after heun_update_row (one thread per row); SOLVER_DPM2M: after dpm2m_update_row - D_{i-1} for
+// the next launch (the one-launch solve keeps it on chip: d null), the trajectory row of its own index
+template <int SOLVER = SOLVER_HEUN>
 __device__ __forceinline__ void heun_store_row(const HeunArgs &a, int kind, int r, const float (&xv)[9], const float (&dv)[9], const float (&cen)[3]) {
-    if (kind == HEUN_PREDICT) {
+    if constexpr (SOLVER == SOLVER_DPM2M) {
+        if (kind == DPM2M_STEP && a.d) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) a.d[(size_t)r * 9 + j] = dv[j];
+        }
+    } else if (kind == HEUN_PREDICT) {
 #pragma unroll
         for (int j = 0; j < 9; ++j) a.d[(size_t)r * 9 + j] = dv[j];
         return;
@@ -99,7 +123,7 @@ __device__ __forceinline__ void heun_store_row(const HeunArgs &a, int kind, int 
 #pragma unroll
         for (int j = 0; j < 9; ++j) a.x[(size_t)r * 9 + j] = xv[j];
         if (a.traj) {
-            float *tr = a.traj + ((size_t)((a.step - 2) >> 1) * a.nrows + r) * 9;
+            float *tr = a.traj + ((size_t)(SOLVER == SOLVER_DPM2M ? a.step - 1 : (a.step - 2) >> 1) * a.nrows + r) * 9;
 #pragma unroll
             for (int j = 0; j < 9; ++j) tr[j] = o[j];
         }
@@ -117,19 +141,21 @@ __device__ __forceinline__ void heun_store_row(const HeunArgs &a, int kind, int 
 // it, finish_previous() then runs the update while the weights are still on their way.
 // SEEDED: the two 9-vectors of noise are not loaded but drawn (gp_philox::draw9: seed state behind a.z_lang, global row = its row base
 // + the row of the launch) right before the update - the same values gp_pc_noise_fill writes, the same update expression after them.
-// HEUN: the Heun solver's launches (HeunArgs) - the overloads of request / finish_previous below; zz1 carries d_i, gdiff the slope factor,
-// dt the step.
+// SOLVER_HEUN: the Heun solver's launches (HeunArgs) - the overloads of request / finish_previous below; zz1 carries d_i, gdiff the slope
+// factor, dt the step.  SOLVER_DPM2M: the DPM-Solver++(2M) launches through the same overloads; zz1 carries D_{i-2}, gdiff / dt / sqdt / gn
+// the schedule row's [1] / [2] / [4] / [5].
 struct PcNoSeed {};
-template <int PT, bool SEEDED = false, bool HEUN = false>
+template <int PT, bool SEEDED = false, int SOLVER = SOLVER_PC>
 struct PcRows {
-    static_assert(!(SEEDED && HEUN), "the Heun update draws no noise");
+    static constexpr bool HEUN = SOLVER != SOLVER_PC;
+    static_assert(!(SEEDED && HEUN), "the fixed-step updates draw no noise");
     int row[PT];
     float xv[PT][9], gr[PT][9], zz1[PT][9], zz2[PT][9], cen[PT][3];
     typename std::conditional<SEEDED, gp_philox::Seed, PcNoSeed>::type seed;
     float gdiff, dt, sqdt, gn, sigma;
     float psum[4];    // the batch's first 256 partial sums, one per lane and quarter
     const float *pp;  // the batch's partial sums of step i-1
-    int kind;         // HEUN: the launch's kind (HEUN_*)
+    int kind;         // HEUN: the launch's kind (HEUN_* / DPM2M_*)
 
     // (1) the rows' operands, then the schedule and the batch's partial sums (or the statistic from outside), then sigma(t_i)
     template <int NW>
@@ -233,7 +259,7 @@ struct PcRows {
     __device__ __forceinline__ void request(const HeunArgs &a, int wave, int lane) {
         static_assert(HEUN, "HeunArgs drive the HEUN instantiations");
         const int i = a.step, pt = lane & 15, wg_row0 = blockIdx.x * (16 * PT * NW);
-        const float *sc = a.sched + (size_t)i * 4;
+        const float *sc = a.sched + (size_t)i * fixed_sched_row<SOLVER>();
         const int kind_ = (int)sc[3];
 #pragma unroll
         for (int p = 0; p < PT; ++p) row[p] = wg_row0 + (wave * PT + p) * 16 + pt;
@@ -246,12 +272,18 @@ struct PcRows {
 #pragma unroll
                 for (int j = 0; j < 9; ++j) gr[p][j] = a.score[(size_t)r * 9 + j];
 #pragma unroll
-                for (int j = 0; j < 9; ++j) zz1[p][j] = kind_ == HEUN_CORRECT || kind_ == HEUN_CORRECT_LAST ? a.d[(size_t)r * 9 + j] : 0.f;
+                for (int j = 0; j < 9; ++j) {
+                    if constexpr (SOLVER == SOLVER_DPM2M)  // D_{i-2}, unless this is the first step (no such denoiser: weight 0)
+                        zz1[p][j] = (kind_ == DPM2M_STEP || kind_ == DPM2M_STEP_LAST) && sc[5] != 0.f ? a.d[(size_t)r * 9 + j] : 0.f;
+                    else
+                        zz1[p][j] = kind_ == HEUN_CORRECT || kind_ == HEUN_CORRECT_LAST ? a.d[(size_t)r * 9 + j] : 0.f;
+                }
                 const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
                 cen[p][0] = cp[0], cen[p][1] = cp[1], cen[p][2] = cp[2];
             }
         }
         sigma = sc[0], gdiff = sc[1], dt = sc[2], kind = kind_;
+        if constexpr (SOLVER == SOLVER_DPM2M) sqdt = sc[4], gn = sc[5];
     }
 
     // HEUN (3): the update and the stores.  True when the launch is the finish-only one: the caller returns.
@@ -260,8 +292,11 @@ struct PcRows {
         if (a.step == 0) return false;
 #pragma unroll
         for (int p = 0; p < PT; ++p) {
-            heun_update_row(kind, xv[p], zz1[p], gr[p], gdiff, dt);
-            if (row[p] < a.nrows && (lane >> 4) == 0) heun_store_row(a, kind, row[p], xv[p], zz1[p], cen[p]);
+            if constexpr (SOLVER == SOLVER_DPM2M)
+                dpm2m_update_row(kind, xv[p], zz1[p], gr[p], gdiff, dt, sqdt, gn);
+            else
+                heun_update_row(kind, xv[p], zz1[p], gr[p], gdiff, dt);
+            if (row[p] < a.nrows && (lane >> 4) == 0) heun_store_row<SOLVER>(a, kind, row[p], xv[p], zz1[p], cen[p]);
         }
         return a.step == a.nsteps;
     }

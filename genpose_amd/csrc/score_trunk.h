@@ -488,4 +488,29 @@ __device__ __forceinline__ void heun_update_row(int kind, float (&xv)[9], float 
     }
 }
 
+// One launch's row update of the DPM-Solver++(2M) fixed-step solver of the same ODE: the second-order multistep exponential integrator in
+// lambda = -ln sigma on the denoiser D = x + sigma^2 score, ONE evaluation per step, the previous step's denoiser carried along.  With
+// h_i = lambda_{i+1} - lambda_i and r_i = (lambda_i - lambda_{i-1}) / h_i:
+//     D_i = x_i + sigma_i^2 score(x_i, t_i);   D~_i = D_0 (i = 0), (1 + 1/(2 r_i)) D_i - (1/(2 r_i)) D_{i-1} (i >= 1)
+//     x_{i+1} = (sigma_{i+1} / sigma_i) x_i - expm1(-h_i) D~_i
+// Row-local like heun_update_row; the operation order is written here once (tests/dpm2m_reference.py restates it in float64).  sc: the
+// score the previous launch stored; every coefficient comes from the device schedule (host float64, rounded once); no renormalisation
+// between steps.  The kinds share Heun's numbers where heun_store_row's effects are the same.
+//   DPM2M_STEP[_LAST]   s2 = sigma_i^2, ratio = sigma_{i+1} / sigma_i, wc / wp = the weights of D_i / D_{i-1} times -expm1(-h_i) (wp = 0 and
+//                       dv = 0 at i = 0): xv <- x_{i+1} = ratio x_i + (wc D_i + wp dv);  dv <- D_i (the caller stores it)
+//   DPM2M_DENOISE       heun_update_row's HEUN_DENOISE with c = s2, h = ratio
+enum { DPM2M_EVAL = HEUN_EVAL, DPM2M_STEP = HEUN_CORRECT, DPM2M_STEP_LAST = HEUN_CORRECT_LAST, DPM2M_DENOISE = HEUN_DENOISE };
+__device__ __forceinline__ void dpm2m_update_row(int kind, float (&xv)[9], float (&dv)[9], const float (&sc)[9], float s2, float ratio, float wc, float wp) {
+    if (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const float D = xv[j] + s2 * sc[j];
+            xv[j] = ratio * xv[j] + (wc * D + wp * dv[j]);
+            dv[j] = D;
+        }
+    } else if (kind == DPM2M_DENOISE) {
+        heun_update_row(HEUN_DENOISE, xv, dv, sc, s2, ratio);
+    }
+}
+
 }  // namespace gp_trunk

@@ -345,37 +345,53 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_seeded_kernel(PcArgs 
 // model; HeunArgs, pc_rows.h) in the tile form: pc_step_tile's shape - row work on tid < P, the evaluation point handed to the trunk
 // through LDS - with the row-local heun_update_row in place of the PC update: no noise, no gradient norm, no partial sums, so no barrier
 // before the update and nothing after the score stores.  Score model, whole tiles.
-template <int P>
+// SOLVER_DPM2M (dpm2m_step_kernel): a launch of the DPM-Solver++(2M) solver (pc_rows.h) - its schedule row, dpm2m_update_row, `d` holds
+// D_{i-2}; everything else is the same text.
+template <int P, int SOLVER = SOLVER_HEUN>
 __device__ __forceinline__ void heun_step_tile(const HeunArgs &a, const gp_scorenet &net) {
     using L = TrunkLds<P>;
+    constexpr int SROW = fixed_sched_row<SOLVER>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int row0 = blockIdx.x * P, tid = threadIdx.x, i = a.step;
-    const float *tvec = a.tvec_all + (size_t)pc_time_row<true>(i) * HEADS;
+    const float *tvec = a.tvec_all + (size_t)pc_time_row<SOLVER>(i) * HEADS;
     TrunkPre<P> pre;
     float sigma = 1.f;
     if (i < a.nsteps) {
         trunk_begin<P>(net, pre, a.cvec, tvec, row0, a.nrows, a.kcand);
-        sigma = a.sched[(size_t)i * 4 + 0];  // requested now, used after the trunk
+        sigma = a.sched[(size_t)i * SROW + 0];  // requested now, used after the trunk
         gp_pin(sigma);
     }
     if (i > 0) {
         if (tid < P) {
             const bool live = row0 + tid < a.nrows;
             const int r = live ? row0 + tid : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
-            const float *sc = a.sched + (size_t)i * 4;
+            const float *sc = a.sched + (size_t)i * SROW;
             const int kind = (int)sc[3];
             const float c = sc[1], h = sc[2];
             float xv[9], gr[9], dv[9], cen[3];
+            if constexpr (SOLVER == SOLVER_DPM2M) {
+                const bool has_d = (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) && sc[5] != 0.f;
 #pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                xv[j] = a.x[(size_t)r * 9 + j];
-                gr[j] = a.score[(size_t)r * 9 + j];
-                dv[j] = kind == HEUN_CORRECT || kind == HEUN_CORRECT_LAST ? a.d[(size_t)r * 9 + j] : 0.f;
+                for (int j = 0; j < 9; ++j) {
+                    xv[j] = a.x[(size_t)r * 9 + j];
+                    gr[j] = a.score[(size_t)r * 9 + j];
+                    dv[j] = has_d ? a.d[(size_t)r * 9 + j] : 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    xv[j] = a.x[(size_t)r * 9 + j];
+                    gr[j] = a.score[(size_t)r * 9 + j];
+                    dv[j] = kind == HEUN_CORRECT || kind == HEUN_CORRECT_LAST ? a.d[(size_t)r * 9 + j] : 0.f;
+                }
             }
             const float *cp = a.centre + (size_t)(r / a.kcand) * 3;
             cen[0] = cp[0], cen[1] = cp[1], cen[2] = cp[2];
-            heun_update_row(kind, xv, dv, gr, c, h);
-            if (live) heun_store_row(a, kind, r, xv, dv, cen);
+            if constexpr (SOLVER == SOLVER_DPM2M)
+                dpm2m_update_row(kind, xv, dv, gr, c, h, sc[4], sc[5]);
+            else
+                heun_update_row(kind, xv, dv, gr, c, h);
+            if (live) heun_store_row<SOLVER>(a, kind, r, xv, dv, cen);
             // hand the evaluation point to the trunk through LDS (no global round trip)
             float *xr = lds + tid * L::LD0;
 #pragma unroll
@@ -399,6 +415,10 @@ template <int P>
 __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_step_kernel(HeunArgs a, gp_scorenet net) {
     heun_step_tile<P>(a, net);
 }
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_step_kernel(HeunArgs a, gp_scorenet net) {
+    heun_step_tile<P, SOLVER_DPM2M>(a, net);
+}
 
 // The same launch in the chain form (trunk_chain.h).  A wave owns 16 * PT rows from the sampler update to the score: every lane
 // of a row's four lane groups carries the row's 9-vector (the update is ~150 VALU instructions per wave, computed redundantly by
@@ -409,9 +429,11 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_step_kernel(HeunArgs a, 
 // per 16-row tile through LDS.
 // SEEDED (pc_step_chain_seeded_kernel): PcRows draws the noise (pc_rows.h).
 // HEUN (heun_step_chain_kernel; Args = HeunArgs): a launch of the fixed-step Heun solver (samplers.py:230-290) - PcRows runs the row-local
-// update, the score is stored, and there is no partial sum.
-template <int PT, int MODEL, bool SEEDED, bool HEUN = false, class Args = PcArgs>
+// update, the score is stored, and there is no partial sum.  SOLVER_DPM2M (dpm2m_step_chain_kernel): the DPM-Solver++(2M) launch, the
+// same through PcRows' other update; the time row is the launch's own index.
+template <int PT, int MODEL, bool SEEDED, int SOLVER = SOLVER_PC, class Args = PcArgs>
 __device__ __forceinline__ void pc_step_chain(const Args &a, const gp_scorenet &net) {
+    constexpr bool HEUN = SOLVER != SOLVER_PC;
     static_assert(HEUN == std::is_same<Args, HeunArgs>::value && (!HEUN || (MODEL == 0 && !SEEDED)), "HeunArgs drive the HEUN instantiations: score model");
     using C = gp_chain::Cfg<PT>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -419,9 +441,9 @@ __device__ __forceinline__ void pc_step_chain(const Args &a, const gp_scorenet &
     const int wg_row0 = blockIdx.x * C::ROWS;
     gp_chain::State<PT> st;
     const int trow = i < a.nsteps ? i : 0;
-    const float *tvec = a.tvec_all + (size_t)(HEUN ? (trow + 1) >> 1 : trow) * HEADS;  // HEUN: one row per evaluated time (HeunArgs)
+    const float *tvec = a.tvec_all + (size_t)(SOLVER == SOLVER_HEUN ? (trow + 1) >> 1 : trow) * HEADS;  // HEUN: one row per evaluated time (HeunArgs)
     // ---- the rows' operands are requested first, the ring prologue behind them: one memory round trip covers both (PcRows, pc_rows.h)
-    PcRows<PT, SEEDED, HEUN> rs;
+    PcRows<PT, SEEDED, SOLVER> rs;
     rs.template request<gp_chain::NW>(a, wave, lane);
     auto &xv = rs.xv;
     const float sigma = rs.sigma;
@@ -486,7 +508,11 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_seeded_kernel(P
 }
 template <int PT>
 __global__ __launch_bounds__(gp_chain::NT, 1) void heun_step_chain_kernel(HeunArgs a, gp_scorenet net) {
-    pc_step_chain<PT, 0, false, true>(a, net);
+    pc_step_chain<PT, 0, false, SOLVER_HEUN>(a, net);
+}
+template <int PT>
+__global__ __launch_bounds__(gp_chain::NT, 1) void dpm2m_step_chain_kernel(HeunArgs a, gp_scorenet net) {
+    pc_step_chain<PT, 0, false, SOLVER_DPM2M>(a, net);
 }
 
 }  // namespace
@@ -538,6 +564,18 @@ static int launch_heun_chain(const HeunArgs &a, const gp_scorenet *net, int nwg,
         attr_done = true;
     }
     hipLaunchKernelGGL((heun_step_chain_kernel<PT>), dim3(nwg), dim3(gp_chain::NT), lds, st, a, *net);
+    return gp_launch_status();
+}
+
+template <int PT>
+static int launch_dpm2m_chain(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
+    const size_t lds = gp_chain::Cfg<PT>::LDS_BYTES;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(dpm2m_step_chain_kernel<PT>, lds)) return GP_ELAUNCH;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((dpm2m_step_chain_kernel<PT>), dim3(nwg), dim3(gp_chain::NT), lds, st, a, *net);
     return gp_launch_status();
 }
 
@@ -774,6 +812,39 @@ int gp_heun_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int l
         hipLaunchKernelGGL((heun_step_kernel<64>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
     else
         hipLaunchKernelGGL((heun_step_kernel<32>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
+    return gp_launch_status();
+}
+
+int gp_dpm2m_launches(int nsteps, int denoise) { return nsteps < 1 ? GP_EINVAL : nsteps + 1 + (denoise ? 1 : 0); }
+
+int gp_dpm2m_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                       const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                       gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_dpm2m_launches(nsteps, denoise) || !net || !cvec ||
+        !tvec_all || !sched || !centre || !x || !d || !score || !out)
+        return GP_EINVAL;
+    const int rg = nclouds_per_group * k, R = ngroups * rg;
+    if (R == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
+    if (rc != GP_OK) return rc;
+    const HeunArgs a = heun_args(R, k, launch, gp_dpm2m_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    hipStream_t st = (hipStream_t)s;
+    const int nwg = ngroups * ((rg + P - 1) / P);
+    if (P == 128) return launch_dpm2m_chain<2>(a, net, nwg, st);
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(dpm2m_step_kernel<16>, trunk_lds_bytes<16>()) || set_lds(dpm2m_step_kernel<32>, trunk_lds_bytes<32>()) ||
+            set_lds(dpm2m_step_kernel<64>, trunk_lds_bytes<64>()))
+            return GP_ELAUNCH;
+        attr_done = true;
+    }
+    if (P == 16)
+        hipLaunchKernelGGL((dpm2m_step_kernel<16>), dim3(nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
+    else if (P == 64)
+        hipLaunchKernelGGL((dpm2m_step_kernel<64>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
+    else
+        hipLaunchKernelGGL((dpm2m_step_kernel<32>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
     return gp_launch_status();
 }
 

@@ -44,16 +44,18 @@ using namespace gp_x9trunk;
 // SEEDED (pc_step_chain_seeded_kernel_bf16x9): PcRows draws the noise (pc_rows.h); the rest is the same text.
 // HEUN (heun_step_chain_kernel_bf16x9; Args = HeunArgs): a launch of the fixed-step Heun solver of the probability-flow ODE
 // (cond_edm_sampler's method, samplers.py:230-290) - PcRows runs the row-local update, the score is stored, there is no partial sum.
-template <bool SEEDED, bool HEUN = false, class Args = PcArgs>
+// SOLVER_DPM2M (dpm2m_step_chain_kernel_bf16x9): a launch of the DPM-Solver++(2M) solver (pc_rows.h), the same through PcRows' other update.
+template <bool SEEDED, int SOLVER = SOLVER_PC, class Args = PcArgs>
 __device__ __forceinline__ void pc_step_chain_bf16x9(const Args &a, const SplitNet &w) {
+    constexpr bool HEUN = SOLVER != SOLVER_PC;
     static_assert(HEUN == std::is_same<Args, HeunArgs>::value && !(HEUN && SEEDED), "HeunArgs drive the HEUN instantiation");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), i = a.step;
     const int wg_row0 = blockIdx.x * X9_ROWS;
     // ---- the rows' operands first, the ring prologue behind them (memory returns in order)
-    PcRows<X9_RT, SEEDED, HEUN> rs;
+    PcRows<X9_RT, SEEDED, SOLVER> rs;
     rs.template request<X9_NW>(a, wave, lane);
-    const float *tvec = a.tvec_all + (size_t)pc_time_row<HEUN>(i) * HEADS;
+    const float *tvec = a.tvec_all + (size_t)pc_time_row<SOLVER>(i) * HEADS;
     X9Staged sg;
     bf16x8 first[X9_PER_T], hold[X9_PER_T];
     if (i < a.nsteps) {
@@ -74,7 +76,8 @@ __device__ __forceinline__ void pc_step_chain_bf16x9(const Args &a, const SplitN
 
 __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<false>(a, w); }
 __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_seeded_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<true>(a, w); }
-__global__ __launch_bounds__(X9_NT, 1) void heun_step_chain_kernel_bf16x9(HeunArgs a, SplitNet w) { pc_step_chain_bf16x9<false, true>(a, w); }
+__global__ __launch_bounds__(X9_NT, 1) void heun_step_chain_kernel_bf16x9(HeunArgs a, SplitNet w) { pc_step_chain_bf16x9<false, SOLVER_HEUN>(a, w); }
+__global__ __launch_bounds__(X9_NT, 1) void dpm2m_step_chain_kernel_bf16x9(HeunArgs a, SplitNet w) { pc_step_chain_bf16x9<false, SOLVER_DPM2M>(a, w); }
 
 // stage_request reads the staged fp32 operands with 16-byte loads
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -155,6 +158,29 @@ int gp_heun_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, i
         attr_done = true;
     }
     hipLaunchKernelGGL(heun_step_chain_kernel_bf16x9, dim3(ngroups * ((rg + X9_ROWS - 1) / X9_ROWS)), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
+    return gp_launch_status();
+}
+
+int gp_dpm2m_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                         const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                         const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_dpm2m_launches(nsteps, denoise) || !net || !cvec ||
+        !tvec_all || !sched || !centre || !x || !d || !score || !out || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9 || !staged_aligned(net, cvec, tvec_all))
+        return GP_EINVAL;
+    const int rg = nclouds_per_group * k;
+    if (ngroups * rg == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(X9_ROWS, ngroups, nclouds_per_group, k, &P);  // the chain plan's rules
+    if (rc != GP_OK) return rc;
+    const HeunArgs a = heun_args(ngroups * rg, k, launch, gp_dpm2m_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
+                        reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (set_lds(dpm2m_step_chain_kernel_bf16x9, X9Lds::BYTES)) return GP_ELAUNCH;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(dpm2m_step_chain_kernel_bf16x9, dim3(ngroups * ((rg + X9_ROWS - 1) / X9_ROWS)), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
     return gp_launch_status();
 }
 

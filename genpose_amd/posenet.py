@@ -5,6 +5,7 @@ networks/posenet.py:18-179, inference modes only:
     net(data, mode='score' | 'energy')                 -> [R,9] | [R,2]     (posenet.py:159-164)
     net(data, mode='pc_sample' | 'ode_sample', init_x=, T0=) -> (in_process [R,S,9], res [R,9])  (posenet.py:94-130)
     net(data, mode='heun_sample', init_x=, T0=)        -> the same pair from the fixed-step Heun solver (ours; samplers.HeunSampler)
+    net(data, mode='dpm2m_sample', init_x=, T0=)       -> the same pair from the fixed-step DPM-Solver++(2M) solver (ours; samplers.Dpm2mSampler)
 
 `data` is the reference's dict of device tensors ('pts', 'pts_feat', 'sampled_pose', 't', 'pts_center').
 Extra (not in the reference): data may carry '_repeat' = K, meaning 'pts_feat'/'pts_center' hold one row per CLOUD
@@ -17,7 +18,7 @@ from .config import encoder_precision_of
 from .encoder import Pointnet2EncoderHIP
 from .lru import ShapeCache
 from .pointnet_encoder import ACT_RELU, PointNetEncoderHIP, dense_rows
-from .samplers import HEUN_GRIDS, HeunSampler, ODESampler, PCSampler
+from .samplers import HEUN_GRIDS, Dpm2mSampler, HeunSampler, ODESampler, PCSampler
 from .scorenet import ScoreNetHIP
 from .sde import SIGMA_MAX, SIGMA_MIN
 
@@ -159,6 +160,14 @@ class GFObjectPose:
         return "bf16x3" if groups == 1 or ((B // groups) * K) % 128 == 0 else "f32"
 
     def sample(self, data, sampler, init_x=None, T0=None, noise=None, return_process=True):
+        if sampler == "dpm2m":
+            # (ours) the fixed-step DPM-Solver++(2M) solve of the same ODE (samplers.Dpm2mSampler): the 'heun' branch's rules
+            if self.cfg.posenet_mode == "energy":
+                raise NotImplementedError("sampler 'dpm2m' with posenet_mode='energy': the DPM-Solver++(2M) solver has no energy-model kernel (use 'ode' or 'pc')")
+            if self.cfg.sampling_steps is None:
+                raise ValueError("the dpm2m sampler needs cfg.sampling_steps")
+            if getattr(self.cfg, "heun_grid", "geometric") not in HEUN_GRIDS:
+                raise ValueError(f"heun_grid {self.cfg.heun_grid!r}: one of {HEUN_GRIDS}")
         if sampler == "heun":
             # (ours) cond_edm_sampler's fixed-step Heun method on the score model's probability-flow ODE: what it cannot serve is said
             # before anything is computed
@@ -207,17 +216,18 @@ class GFObjectPose:
                 smp = self._samplers[key] = ODESampler(self.pose_score_net, B, K, self.device, coupling_group=coupling, trunk=trunk)
             self.last_sampler = smp
             return smp.run(cvec, centre, x0, T0, num_steps=self.cfg.sampling_steps, eps=self.sampling_eps, return_process=return_process)
-        if sampler == "heun":
+        if sampler in ("heun", "dpm2m"):
             # prior and warm start exactly as the 'ode' branch: a draw at T0, init_x + draw when given.  Row-local, so a sharded batch
-            # needs no coupling: self.coupling_group is ignored
+            # needs no coupling: self.coupling_group is ignored.  'dpm2m': the same draws, samplers.Dpm2mSampler's solve
             T0 = self.T if T0 is None else T0
             pr = self._prior_to_device((R, 9), T=T0)
             x0 = pr if init_x is None else init_x.float() + pr
             n, grid = int(self.cfg.sampling_steps), getattr(self.cfg, "heun_grid", "geometric")
-            key = ("heun", B, K, n, grid, return_process)
+            key = (sampler, B, K, n, grid, return_process)
             smp = self._samplers.get(key)
             if smp is None:
-                smp = self._samplers[key] = HeunSampler(self.pose_score_net, B, K, n, self.device, grid=grid, record_traj=return_process)
+                cls = HeunSampler if sampler == "heun" else Dpm2mSampler
+                smp = self._samplers[key] = cls(self.pose_score_net, B, K, n, self.device, grid=grid, record_traj=return_process)
             self.last_sampler = smp
             xs, res = smp.run(cvec, centre, x0, T0=T0, eps=self.sampling_eps)
             return (xs.clone() if xs is not None else None), res.clone()
@@ -342,6 +352,8 @@ class GFObjectPose:
             return self.sample(data, "ode", init_x=init_x, T0=T0)
         if mode == "heun_sample":
             return self.sample(data, "heun", init_x=init_x, T0=T0)
+        if mode == "dpm2m_sample":
+            return self.sample(data, "dpm2m", init_x=init_x, T0=T0)
         raise NotImplementedError(mode)
 
     __call__ = forward

@@ -263,9 +263,9 @@ class TrackingRunner:
         self.buffer = {"model_name": [], "pred_sRT": None}
         self.use_graphs = use_graphs
         if use_graphs:  # the frame graphs drive the PointNet++ encoder's stages themselves: refused here, not at the first frame
-            if score_agent.cfg.sampler_mode[0] == "heun":
+            if score_agent.cfg.sampler_mode[0] in ("heun", "dpm2m"):
                 raise NotImplementedError("TrackingRunner(use_graphs=True) builds its frame graphs around the adaptive ODE solve and does not serve "
-                                          "sampler_mode ['heun']: use use_graphs=False (the agent's pred_func)")
+                                          f"sampler_mode ['{score_agent.cfg.sampler_mode[0]}']: use use_graphs=False (the agent's pred_func)")
             for a in (score_agent, energy_agent):
                 a.net.pointnet2_encoder("TrackingRunner(use_graphs=True)")
         self._graphs = None
@@ -504,9 +504,12 @@ class FixedStepTracker:
     ranker: 'energy' - the energy agent's two energies at T = 1e-5; 'likelihood' - the score agent's own exact-divergence log-likelihood by
     samplers.HeunLikelihood (cfg.likelihood_steps, else the tracker's steps; cfg.likelihood_grid) in both columns, cast to float32 as
     SingleFrameRunner does: tracking from a score checkpoint alone.
-    launches: 'single' / 'chain' force the solve's form; None takes 'single' below SINGLE_MAX_ROWS rows where the plan is a tile plan."""
+    launches: 'single' / 'chain' force the solve's form; None takes 'single' below SINGLE_MAX_ROWS rows where the plan is a tile plan.
+    solver: 'heun' (default) or 'dpm2m' - the same frame with samplers.Dpm2mSampler's solve (steps + 1 evaluations instead of 2 steps + 1)
+    in HeunSampler's place; everything around the solve is unchanged."""
 
     RANKERS = ("energy", "likelihood")
+    SOLVERS = ("heun", "dpm2m")
     LAUNCHES = (None, "single", "chain")
     # rows below which launches=None takes the one-launch solve.  profiles/fixed_step_tracking.txt: its median lay below the chain's minimum
     # at 250, 800 and 3 200 rows (16-row tiles, 1.09x) and above it at 12 800 rows (64-row tiles, 0.97x); nothing was measured in between
@@ -515,8 +518,10 @@ class FixedStepTracker:
     RING = 4  # pinned blocks in rotation: the host rewrites one only after the copy issued four steps earlier has completed
 
     def __init__(self, score_agent, energy_agent=None, steps=8, repeat_num=50, T0=0.15, ratio=0.6, ranker="energy", seed=0, launches=None,
-                 grid="geometric", max_objects_per_frame=8):
+                 grid="geometric", max_objects_per_frame=8, solver="heun"):
         from .samplers import HEUN_GRIDS
+        if solver not in self.SOLVERS:
+            raise ValueError(f"FixedStepTracker(solver={solver!r}): one of {self.SOLVERS}")
         if score_agent.cfg.posenet_mode != "score":
             raise ValueError(f"FixedStepTracker: the score agent's posenet_mode is {score_agent.cfg.posenet_mode!r}, the Heun solver needs 'score'")
         if ranker not in self.RANKERS:
@@ -539,7 +544,7 @@ class FixedStepTracker:
         self.score_agent, self.energy_agent = score_agent, energy_agent if ranker == "energy" else None
         self.steps, self.repeat_num, self.T0, self.ratio = int(steps), int(repeat_num), float(T0), ratio
         self.ranker, self.seed, self.launches, self.grid = ranker, int(seed) % (1 << 64), launches, grid
-        self.max_objects = int(max_objects_per_frame)
+        self.max_objects, self.solver = int(max_objects_per_frame), solver
         self.buffers, self.frame_index = [], []
         self._embed = self._prev = None
         self._b = ShapeCache(self.MAX_SHAPES)
@@ -620,13 +625,14 @@ class FixedStepTracker:
         return init_x, pred, energy, r["sorted_RTs"], r["avg_RT"]
 
     def _capture(self, key, a_outs, pts):
-        from .samplers import HeunLikelihood, HeunSampler
+        from .samplers import Dpm2mSampler, HeunLikelihood, HeunSampler
         net = self.score_agent.net
         K = self.repeat_num
         n, dev = sum(c for _, c in key), pts.device
-        probe = HeunSampler(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False)
+        Solver = Dpm2mSampler if self.solver == "dpm2m" else HeunSampler
+        probe = Solver(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False)
         form = self._solve_form(n * K, probe.plan)
-        smp = probe if form == "chain" else HeunSampler(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False, launches=form)
+        smp = probe if form == "chain" else Solver(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False, launches=form)
         smp.cvec = a_outs[1]  # graph A's static output: nothing is copied
         ent = {"key": key, "smp": smp, "a_outs": a_outs, "sel": max(1, int(self.ratio * K)),
                "src": torch.full((n,), -1, dtype=torch.int32, device=dev), "fallback": torch.zeros(n, 4, 4, device=dev),

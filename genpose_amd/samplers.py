@@ -367,6 +367,18 @@ class HeunSampler:
     NFE and the schedule are those of the chain either way."""
 
     LAUNCHES = ("chain", "single")
+    # what a solver on the same launch shape, plans and buffers replaces (Dpm2mSampler): the floats per schedule row, the entry points
+    # (chain plan on bf16x9, any plan, one launch) and the kernels' names
+    SCHED_ROW = 4
+    ENTRY = ("gp_heun_step_bf16x9", "gp_heun_step_plan", "gp_heun_solve_tile")
+    KERNELS = ("heun_step_chain_kernel", "heun_step_kernel", "heun_solve_kernel")
+
+    @staticmethod
+    def _launches(nsteps, denoise):
+        return heun_launches(nsteps, denoise)
+
+    def _schedule(self, T0, eps):
+        return heun_schedule(self.n, T0, eps, self.grid, self.rho, self.denoise)
 
     def __init__(self, net, B, K, nsteps, device, groups=1, grid="geometric", rho=7.0, trunk=None, tile=None, record_traj=False, denoise=True,
                  use_graph=True, launches="chain"):
@@ -383,7 +395,7 @@ class HeunSampler:
             raise ValueError(f"launches {launches!r}: one of {self.LAUNCHES}")
         self.net, self.B, self.K, self.n, self.groups = net, B, K, int(nsteps), groups
         self.grid, self.rho, self.denoise = grid, float(rho), bool(denoise)
-        self.nlaunch = heun_launches(self.n, self.denoise)
+        self.nlaunch = self._launches(self.n, self.denoise)
         self.dev = torch.device(device)
         R = self.R = B * K
         t_out = ctypes.c_int(0)
@@ -400,14 +412,15 @@ class HeunSampler:
             self.trunk = trunk or "bf16x9"
             if self.trunk == "bf16x9":
                 self._x9 = net.w.bf16x9_packs()
-        self.kernel_name = ("heun_step_chain_kernel<bf16x9>" if self.trunk == "bf16x9" else "heun_step_chain_kernel<2>" if self.tile == 128
-                            else f"heun_solve_kernel<{self.tile}>" if launches == "single" else f"heun_step_kernel<{self.tile}>")
+        kc, kt, ks = self.KERNELS
+        self.kernel_name = (f"{kc}<bf16x9>" if self.trunk == "bf16x9" else f"{kc}<2>" if self.tile == 128
+                            else f"{ks}<{self.tile}>" if launches == "single" else f"{kt}<{self.tile}>")
         f = lambda *s: torch.empty(*s, device=self.dev)
         self.x, self.d, self.score, self.out = f(R, 9), f(R, 9), f(R, 9), f(R, 9)
         self.cvec, self.centre = f(B, 768), f(B, 3)
         self.traj = f(self.n, R, 9) if record_traj else None
-        # run-time schedule: [launches][4] + the N + 1 times, one pinned block -> one device block -> the time-embedding table
-        self._sched_len = self.nlaunch * 4
+        # run-time schedule: [launches][SCHED_ROW] + the N + 1 times, one pinned block -> one device block -> the time-embedding table
+        self._sched_len = self.nlaunch * self.SCHED_ROW
         self._table = torch.zeros(self._sched_len + self.n + 1, device=self.dev)
         self._table_host = torch.zeros(self._sched_len + self.n + 1).pin_memory()
         self._table_ev = None
@@ -423,7 +436,7 @@ class HeunSampler:
     def _write_schedule(self, T0, eps):
         key = (float(T0), float(eps))
         if key != self._table_key:
-            t, sched = heun_schedule(self.n, T0, eps, self.grid, self.rho, self.denoise)
+            t, sched = self._schedule(T0, eps)
             if self._table_ev is not None:
                 self._table_ev.synchronize()  # the previous copy out of the pinned block has completed
             else:
@@ -442,13 +455,13 @@ class HeunSampler:
         bufs = (ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
                 ptr(self.traj))
         if self.trunk == "bf16x9":
-            _lib.call("gp_heun_step_bf16x9", *shape, self.net.w.ref(), *bufs, *(ptr(w) for w in self._x9), stream_ptr())
+            _lib.call(self.ENTRY[0], *shape, self.net.w.ref(), *bufs, *(ptr(w) for w in self._x9), stream_ptr())
         else:
-            _lib.call("gp_heun_step_plan", self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
+            _lib.call(self.ENTRY[1], self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
 
     def _launch_all(self):
         if self.launches == "single":
-            _lib.call("gp_heun_solve_tile", self.plan, self.groups, self.B // self.groups, self.K, self.n, int(self.denoise), self.net.w.ref(),
+            _lib.call(self.ENTRY[2], self.plan, self.groups, self.B // self.groups, self.K, self.n, int(self.denoise), self.net.w.ref(),
                       ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
                       ptr(self.traj), stream_ptr())
             return
@@ -477,11 +490,78 @@ class HeunSampler:
                     self._launch_all()
                 self.captures += 1
             self.graph.replay()
-        self.last_stats = {"nfev": self.nlaunch - 1, "plan": self.plan, "launches": self.nlaunch, "kernel": self.kernel_name}
+        self.last_stats = {"nfev": self.nlaunch - 1, "plan": self.plan, "launches": self.nlaunch, "kernel": self.kernel_name,
+                           "nlaunch": self.nlaunch, "kernel_name": self.kernel_name}
         if self.launches == "single":
             self.last_stats["device_launches"] = 1
         xs = self.traj.permute(1, 0, 2) if self.traj is not None else None
         return xs, self.out
+
+
+# ---------------------------------------------------------------------------------------------- PF-ODE (fixed-step DPM-Solver++(2M))
+DPM2M_SCHED_ROW = 8
+
+
+def dpm2m_launches(nsteps, denoise=True):
+    """Launches of a DPM-Solver++(2M) chain (gp_dpm2m_launches): N + 1, one more with denoise.  NFE = launches - 1."""
+    if int(nsteps) < 1:
+        raise ValueError(f"nsteps {nsteps}: at least one step")
+    return int(nsteps) + 1 + (1 if denoise else 0)
+
+
+def dpm2m_coefficients(sig):
+    """Per step i = 0 .. N-1 of DPM-Solver++(2M) on the sigma grid `sig` [N+1] (float64): sigma_i^2, sigma_{i+1} / sigma_i and the weights
+    of D_i and D_{i-1} times -expm1(-h_i), with lambda = -ln sigma, h_i = lambda_{i+1} - lambda_i, r_i = (lambda_i - lambda_{i-1}) / h_i:
+    wc = -expm1(-h_i) (1 + 1/(2 r_i)), wp = -expm1(-h_i) (-1/(2 r_i)); step 0 is first order (wc = -expm1(-h_0), wp = 0).  float64."""
+    sig = np.asarray(sig, dtype=np.float64)
+    lam = -np.log(sig)
+    h = lam[1:] - lam[:-1]
+    em = -np.expm1(-h)
+    wc, wp = em.copy(), np.zeros_like(em)
+    for i in range(1, len(h)):
+        r = (lam[i] - lam[i - 1]) / h[i]
+        wc[i] = em[i] * (1.0 + 1.0 / (2.0 * r))
+        wp[i] = em[i] * (-(1.0 / (2.0 * r)))
+    return sig[:-1] * sig[:-1], sig[1:] / sig[:-1], wc, wp
+
+
+def dpm2m_schedule(nsteps, T0=1.0, eps=EPS, grid="geometric", rho=7.0, denoise=True):
+    """Host schedule of a DPM-Solver++(2M) chain on heun_schedule's grid: (t [N+1] f64, sched [launches,8] f32) - per launch the sigma of
+    its evaluation (the score's divisor), sigma_{i-1}^2, sigma_i / sigma_{i-1}, the launch kind, the two denoiser weights already multiplied
+    by -expm1(-h) and two zeros (include/genpose_hip.h: gp_dpm2m_step_plan), computed in float64 and rounded once.  Launch l evaluates at
+    t_l; the denoising launch carries g(eps) and the predictor's step where the steps carry sigma^2 and the ratio."""
+    N = int(nsteps)
+    t, sig = heun_grid(N, T0, eps, grid, rho)
+    s2, ratio, wc, wp = dpm2m_coefficients(sig)
+    sched = np.zeros((dpm2m_launches(N, denoise), DPM2M_SCHED_ROW), dtype=np.float64)
+    sched[0, 0] = sig[0]
+    for i in range(N):
+        sched[i + 1, :6] = (sig[i + 1], s2[i], ratio[i], 3.0 if i == N - 1 else 2.0, wc[i], wp[i])
+    if denoise:
+        # the reverse-diffusion predictor at eps (samplers.py:209-218) with cond_ode_sampler's divisor rule for num_steps = N, as heun_schedule
+        g = np.float32(sig[N]) * _HEUN_G_FACTOR
+        sched[N + 1, :4] = (sig[N], g, (1.0 - float(eps)) / N, 4.0)
+    return t, sched.astype(np.float32)
+
+
+class Dpm2mSampler(HeunSampler):
+    """Fixed-step DPM-Solver++(2M) solver of the probability-flow ODE (ours; opt-in): the second-order multistep exponential integrator in
+    lambda = -ln sigma on the denoiser D = x + sigma^2 score - ONE evaluation per step, the previous step's denoiser carried along, the
+    linear part of the VE flow integrated exactly; state in fp32.  NFE = N (+ 1 with denoise) in N + 1 (+ 1) launches against HeunSampler's
+    2 N (+ 1) on the same grid.  Everything else is HeunSampler's: constructor, plans, trunk, buffers (d holds the previous denoiser),
+    run-time T0 / eps with one capture per geometry, launches 'chain' | 'single' (gp_dpm2m_solve_tile), row locality, the finish (denoise,
+    normalize_rotation, cloud centre) and the trajectory's layout."""
+
+    SCHED_ROW = DPM2M_SCHED_ROW
+    ENTRY = ("gp_dpm2m_step_bf16x9", "gp_dpm2m_step_plan", "gp_dpm2m_solve_tile")
+    KERNELS = ("dpm2m_step_chain_kernel", "dpm2m_step_kernel", "dpm2m_solve_kernel")
+
+    @staticmethod
+    def _launches(nsteps, denoise):
+        return dpm2m_launches(nsteps, denoise)
+
+    def _schedule(self, T0, eps):
+        return dpm2m_schedule(self.n, T0, eps, self.grid, self.rho, self.denoise)
 
 
 # ---------------------------------------------------------------------------------------------- likelihood ODE (fixed-step Heun)

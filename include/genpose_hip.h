@@ -463,6 +463,43 @@ int gp_heun_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int 
                        const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                        gp_stream_t s);
 
+/* DPM-SOLVER++(2M) FIXED-STEP SOLVER of the same probability-flow ODE (opt-in; ours - the reference has no multistep sampler).  The
+ * second-order multistep exponential integrator in lambda = -ln sigma on the denoiser D = x + sigma^2 score: ONE evaluation per step, the
+ * previous step's denoiser carried along, the linear part of the VE flow integrated exactly.  On gp_heun_launches' grid t_0 .. t_nsteps,
+ * with h_i = lambda_{i+1} - lambda_i > 0 and r_i = (lambda_i - lambda_{i-1}) / h_i:
+ *     D_i = x_i + sigma_i^2 score(x_i, t_i);   D~_i = D_0 (i = 0),  (1 + 1/(2 r_i)) D_i - (1/(2 r_i)) D_{i-1} (i >= 1)
+ *     x_{i+1} = (sigma_{i+1} / sigma_i) x_i - expm1(-h_i) D~_i
+ * fp32 state, no rotation renormalisation between steps; after step nsteps exactly what the Heun solver does (the reverse-diffusion
+ * predictor at eps with denoise, normalize_rotation, the cloud centre).  Deterministic and ROW-LOCAL.  A solve of nsteps steps is a chain
+ * of gp_dpm2m_launches(nsteps, denoise) = nsteps + 1 (+ 1 with denoise) launches, NFE = launches - 1:
+ *     launch 0            evaluates score(x_0, t_0)
+ *     launch i = 1 .. nsteps  D_{i-1} from the stored score and x_{i-1}; x_i = ratio x_{i-1} + (wc D_{i-1} + wp D_{i-2}) -> x, D_{i-1} -> d,
+ *                         traj[i-1] (rotation normalised, centre added); evaluates score(x_i, t_i)                      (kind 2)
+ *     launch nsteps       the same update -> out as well; evaluates at (x_nsteps, eps) only with denoise                  (kind 3)
+ *     launch nsteps + 1   with denoise: out = normalise(x + (0 - c^2 score) h) + centre                                   (kind 4)
+ * The kernels know nothing about the grid.  sched [launches][8] (device, f32; host float64 rounded once): [0] the sigma of the launch's
+ * evaluation (the score's divisor), [1] sigma_{i-1}^2 (kind 4: c = g(eps)), [2] ratio = sigma_i / sigma_{i-1} (kind 4: the step h), [3] the
+ * kind as above (0 for launch 0), [4] wc and [5] wp: the weights of D_{i-1} and D_{i-2} times -expm1(-h_{i-1}) - wp = 0 marks the first step,
+ * whose launch does not read d - [6], [7] zero.  tvec_all [nsteps + 1][768]: gp_time_embed of t_0 .. t_nsteps (launch l evaluates at row l).
+ * Buffers, plans (gp_heun_layout) and refusals as gp_heun_step_plan's; d holds the previous denoiser between launches. */
+int gp_dpm2m_launches(int nsteps, int denoise);
+/* One launch of the DPM-Solver++(2M) chain on plan `tile`; the chain plan (128) runs the fp32 MFMA chain kernel. */
+int gp_dpm2m_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                       const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                       gp_stream_t s);
+/* The chain plan's DPM-Solver++(2M) launch with the trunk as exact-product split bf16 (as gp_heun_step_bf16x9 is to gp_heun_step_plan):
+ * the same buffers, w_*_x9 as there. */
+int gp_dpm2m_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                         const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                         const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s);
+/* The WHOLE DPM-Solver++(2M) solve in one launch, tile plans (csrc/heun_solve.hip), as gp_heun_solve_tile is to gp_heun_step_plan: x, out
+ * and traj hold afterwards, BIT FOR BIT, what the chain of gp_dpm2m_step_plan calls on the same plan leaves there; x_i, D_{i-1} and the
+ * centre stay on chip, `d` and `score` are not written.  GP_EINVAL with nothing written for the 128-row chain form, the head-split plan,
+ * nsteps < 1, null buffers or a plan that does not fit; zero rows: GP_OK.  Stateless, capturable. */
+int gp_dpm2m_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                        const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                        gp_stream_t s);
+
 /* FIXED-STEP HEUN SOLVE OF THE EXACT-LIKELIHOOD ODE (opt-in; csrc/heun_likelihood.hip).  cond_ode_likelihood's system (samplers.py:22-99)
  * d[x; logp]/dt = -g^2/2 [score; div_x score] with the exact divergence of gp_score_div_exact, integrated in sigma from sigma(eps) UP to
  * sigma(T) by Heun's method on a fixed grid (-g^2/2 dt = -sigma dsigma: slope d = -sigma [score; div]).  x and the slopes are fp32, the
