@@ -15,6 +15,7 @@ P = c_void_p
 PLAN_SHARED = 0x200     # GP_PLAN_SHARED: the RK45 driver's shared-chunk plan (16 | or 48 |), see include/genpose_hip.h
 PLAN_FLAGS = 0x300
 RK45_MODEL_LIKELIHOOD_EXACT = 4  # GP_RK45_MODEL_LIKELIHOOD_EXACT: the likelihood ODE with the exact divergence (3 stays an unknown model)
+CONSENSUS_MAX_K = 512   # GP_CONSENSUS_MAX_K: the largest candidate count the consensus ranker's LDS layout serves
 PLAN_HEADSPLIT = 0x100  # GP_PLAN_HEADSPLIT (include/genpose_hip.h): OR-ed onto a 16-row tile plan = three workgroups per tile, one head each
 
 
@@ -118,6 +119,8 @@ SIGNATURES = {
     "gp_rank_aggregate_rt": [c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P],
     "gp_pose9_to_rt": [c_int, c_int, P, P, P],
     "gp_quat_trans_to_rt": [c_int, P, P, P],
+    "gp_consensus_energy": [c_int, c_int, c_int, P, P, P, P],
+    "gp_consensus_rank_aggregate_rt": [c_int, c_int, c_int, c_int] + [P] * 9 + [P],
 }
 OPTIONAL = set()
 

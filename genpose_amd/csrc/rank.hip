@@ -114,23 +114,15 @@ __device__ __forceinline__ void quat_trans_to_rt(const float *q, float *o) {
     o[12] = o[13] = o[14] = 0.f, o[15] = 1.f;
 }
 
-// One wave per cloud: ranking, sorted copies, aggregation - and (optional) the 4x4 forms the runners hand on: sorted_rt [k][4][4] f64 =
-// gp_pose9_to_rt of the sorted poses, avg_rt [4][4] f32 = gp_quat_trans_to_rt of avg_pose (same arithmetic, same bits), so that the ranking
-// step of a tracking frame is this ONE launch.
+// Ranking, sorted copies and aggregation of one cloud by one wave, from the energies already in LDS: e [k][2], ord [k][2] (candidate index
+// at each rank) and quat [sel][4] are the caller's LDS, `poses` the cloud's own [k][9].  The callers put a barrier between the last write
+// of e and this.  Optional outputs (any may be NULL): sorted_rt [k][4][4] f64 = gp_pose9_to_rt of the sorted poses, avg_rt [4][4] f32 =
+// gp_quat_trans_to_rt of avg_pose (same arithmetic, same bits).
 template <typename T>
-__global__ __launch_bounds__(64) void rank_aggregate_kernel(int k, int sel, const T *__restrict__ poses, const float *__restrict__ energy,
-                                                            T *__restrict__ sorted_poses, float *__restrict__ sorted_energy,
-                                                            int32_t *__restrict__ order, float *__restrict__ avg_pose,
-                                                            double *__restrict__ sorted_rt, float *__restrict__ avg_rt) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *e = reinterpret_cast<float *>(smem);                   // [k][2]
-    int *ord = reinterpret_cast<int *>(e + 2 * k);                // [k][2]: candidate index at each rank
-    double *quat = reinterpret_cast<double *>(ord + 2 * k);  // [sel][4] (offset 16k bytes: 8-byte aligned)
-    const int b = blockIdx.x, tid = threadIdx.x;
-    poses += (size_t)b * k * 9;
-    energy += (size_t)b * k * 2;
-    for (int i = tid; i < 2 * k; i += 64) e[i] = energy[i];
-    __syncthreads();
+__device__ __forceinline__ void rank_aggregate_cloud(int b, int k, int sel, const T *__restrict__ poses, const float *e, int *ord, double *quat,
+                                                     T *__restrict__ sorted_poses, float *__restrict__ sorted_energy, int32_t *__restrict__ order,
+                                                     float *__restrict__ avg_pose, double *__restrict__ sorted_rt, float *__restrict__ avg_rt) {
+    const int tid = threadIdx.x;
     // stable descending rank by counting (torch.sort(descending=True, stable=True); ties keep candidate order).  The order is
     // torch's: every NaN ranks above +inf and NaNs tie with each other, -0.0 ties with +0.0.  With the plain `>` / `==` a NaN
     // compares false both ways, two candidates share a rank and some ord slots stay unwritten (read below as pose indices).
@@ -227,6 +219,139 @@ __global__ __launch_bounds__(64) void rank_aggregate_kernel(int k, int sel, cons
     }
 }
 
+// One wave per cloud: ranking, sorted copies, aggregation - and (optional) the 4x4 forms the runners hand on, so that the ranking step of a
+// tracking frame is this ONE launch.
+template <typename T>
+__global__ __launch_bounds__(64) void rank_aggregate_kernel(int k, int sel, const T *__restrict__ poses, const float *__restrict__ energy,
+                                                            T *__restrict__ sorted_poses, float *__restrict__ sorted_energy,
+                                                            int32_t *__restrict__ order, float *__restrict__ avg_pose,
+                                                            double *__restrict__ sorted_rt, float *__restrict__ avg_rt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *e = reinterpret_cast<float *>(smem);                   // [k][2]
+    int *ord = reinterpret_cast<int *>(e + 2 * k);                // [k][2]: candidate index at each rank
+    double *quat = reinterpret_cast<double *>(ord + 2 * k);  // [sel][4] (offset 16k bytes: 8-byte aligned)
+    const int b = blockIdx.x, tid = threadIdx.x;
+    poses += (size_t)b * k * 9;
+    energy += (size_t)b * k * 2;
+    for (int i = tid; i < 2 * k; i += 64) e[i] = energy[i];
+    __syncthreads();
+    rank_aggregate_cloud<T>(b, k, sel, poses, e, ord, quat, sorted_poses, sorted_energy, order, avg_pose, sorted_rt, avg_rt);
+}
+
+// ---------------------------------------------------------------------------------------------- consensus score
+// Ranks a cloud's candidates by their mutual agreement (ours; no network): the score of candidate i is minus the mean distance to the
+// cloud's other finite candidates, column 0 by rotation, column 1 by translation (include/genpose_hip.h, section D).  LDS per candidate:
+// its Gram-Schmidt matrix (row-major) and translation, 12 f64, written once, and a finiteness flag.
+constexpr int CONS_F64 = 12;
+constexpr size_t CONS_LDS_PER_K = CONS_F64 * sizeof(double) + sizeof(int);
+
+template <typename T>
+__device__ __forceinline__ void consensus_stage(int k, const T *__restrict__ poses, double *rt, int *fin) {
+    for (int i = threadIdx.x; i < k; i += 64) {
+        T p[9];
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            p[j] = poses[(size_t)i * 9 + j];
+            ok = ok && isfinite((double)p[j]);
+        }
+        double R[3][3];
+        rot6_to_matrix<T>(p, R);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rt[CONS_F64 * i + 3 * r + c] = R[r][c];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) rt[CONS_F64 * i + 9 + r] = (double)p[6 + r];
+        fin[i] = ok;
+    }
+}
+
+// Lanes stride over i; the loop over j is serial and ascending in every lane, which fixes the order of the sums and so the bits.  d_ij is
+// bitwise symmetric: the element differences (exact negatives of each other for (i, j) and (j, i)) are squared and summed in one order.
+// Writes the float32 scores to e_lds [k][2] and / or e_out [k][2] (either may be NULL).
+template <bool SYM>
+__device__ __forceinline__ void consensus_score(int k, const double *rt, const int *fin, float *e_lds, float *__restrict__ e_out) {
+    for (int i = threadIdx.x; i < k; i += 64) {
+        float s0 = -__builtin_inff(), s1 = -__builtin_inff();
+        if (fin[i]) {
+            double a[CONS_F64];
+#pragma unroll
+            for (int c = 0; c < CONS_F64; ++c) a[c] = rt[CONS_F64 * i + c];
+            double sr = 0.0, st = 0.0;
+            int cnt = 0;
+            for (int j = 0; j < k; ++j) {
+                if (j == i || !fin[j]) continue;
+                const double *q = rt + CONS_F64 * j;
+                double x;
+                if (SYM) {  // the object's y axis: the second column
+                    const double d0 = a[1] - q[1], d1 = a[4] - q[4], d2 = a[7] - q[7];
+                    x = sqrt((d0 * d0 + d1 * d1) + d2 * d2) / 2.0;
+                } else {
+                    double ss = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) {
+                        const double d = a[c] - q[c];
+                        ss += d * d;
+                    }
+                    x = sqrt(ss) / 2.8284271247461903;  // 2 sqrt 2
+                }
+                sr += 2.0 * asin(x < 1.0 ? x : 1.0);
+                const double t0 = a[9] - q[9], t1 = a[10] - q[10], t2 = a[11] - q[11];
+                st += sqrt((t0 * t0 + t1 * t1) + t2 * t2);
+                ++cnt;
+            }
+            const double den = (double)(cnt > 1 ? cnt : 1);
+            s0 = (float)(-(sr / den));
+            s1 = (float)(-(st / den));
+        }
+        if (e_lds) e_lds[2 * i + 0] = s0, e_lds[2 * i + 1] = s1;
+        if (e_out) e_out[2 * i + 0] = s0, e_out[2 * i + 1] = s1;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void consensus_energy_kernel(int k, const T *__restrict__ poses, const int8_t *__restrict__ sym,
+                                                              float *__restrict__ energy_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *rt = reinterpret_cast<double *>(smem);       // [k][12]
+    int *fin = reinterpret_cast<int *>(rt + CONS_F64 * k);  // [k]
+    const int b = blockIdx.x;
+    consensus_stage<T>(k, poses + (size_t)b * k * 9, rt, fin);
+    __syncthreads();
+    if (sym && sym[b])
+        consensus_score<true>(k, rt, fin, nullptr, energy_out + (size_t)b * k * 2);
+    else
+        consensus_score<false>(k, rt, fin, nullptr, energy_out + (size_t)b * k * 2);
+}
+
+// The score and everything rank_aggregate_kernel does, one launch.  LDS: e [k][2] f32, then the candidates' matrices; once every lane has
+// its scores the matrices are dead and ord / quat take their place (8 k + 32 sel <= 40 k bytes of the 100 k).
+template <typename T>
+__global__ __launch_bounds__(64) void consensus_rank_aggregate_kernel(int k, int sel, const T *__restrict__ poses, const int8_t *__restrict__ sym,
+                                                                      float *__restrict__ energy_out, T *__restrict__ sorted_poses,
+                                                                      float *__restrict__ sorted_energy, int32_t *__restrict__ order,
+                                                                      float *__restrict__ avg_pose, double *__restrict__ sorted_rt,
+                                                                      float *__restrict__ avg_rt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *e = reinterpret_cast<float *>(smem);                   // [k][2]
+    double *rt = reinterpret_cast<double *>(e + 2 * k);          // [k][12] (offset 8k bytes)
+    int *fin = reinterpret_cast<int *>(rt + CONS_F64 * k);        // [k]
+    int *ord = reinterpret_cast<int *>(e + 2 * k);                // [k][2], over rt
+    double *quat = reinterpret_cast<double *>(ord + 2 * k);  // [sel][4], over rt
+    const int b = blockIdx.x;
+    poses += (size_t)b * k * 9;
+    consensus_stage<T>(k, poses, rt, fin);
+    __syncthreads();
+    float *eo = energy_out ? energy_out + (size_t)b * k * 2 : nullptr;
+    if (sym && sym[b])
+        consensus_score<true>(k, rt, fin, e, eo);
+    else
+        consensus_score<false>(k, rt, fin, e, eo);
+    __syncthreads();  // every score is in e, and no lane reads rt / fin any more
+    rank_aggregate_cloud<T>(b, k, sel, poses, e, ord, quat, sorted_poses, sorted_energy, order, avg_pose, sorted_rt, avg_rt);
+}
+
 }  // namespace
 
 // [n][9] poses (two rotation columns + translation) -> [n][4][4] f64 homogeneous matrices (evaluation_single.py:325-332: get_rot_matrix
@@ -290,6 +415,33 @@ int gp_rank_aggregate_rt(int b, int k, int sel, int is_f64, const void *poses, c
 int gp_rank_aggregate(int b, int k, int sel, int is_f64, const void *poses, const float *energy, void *sorted_poses, float *sorted_energy,
                       int32_t *order, float *avg_pose, gp_stream_t s) {
     return gp_rank_aggregate_rt(b, k, sel, is_f64, poses, energy, sorted_poses, sorted_energy, order, avg_pose, nullptr, nullptr, s);
+}
+
+int gp_consensus_energy(int b, int k, int is_f64, const void *poses, const int8_t *sym, float *energy_out, gp_stream_t s) {
+    if (b < 0 || k <= 0 || k > GP_CONSENSUS_MAX_K || !poses || !energy_out) return GP_EINVAL;
+    if (b == 0) return GP_OK;
+    const size_t lds = (size_t)k * CONS_LDS_PER_K;
+    if (is_f64)
+        hipLaunchKernelGGL(consensus_energy_kernel<double>, dim3(b), dim3(64), lds, (hipStream_t)s, k, (const double *)poses, sym, energy_out);
+    else
+        hipLaunchKernelGGL(consensus_energy_kernel<float>, dim3(b), dim3(64), lds, (hipStream_t)s, k, (const float *)poses, sym, energy_out);
+    return gp_launch_status();
+}
+
+int gp_consensus_rank_aggregate_rt(int b, int k, int sel, int is_f64, const void *poses, const int8_t *sym, float *energy_out, void *sorted_poses,
+                                   float *sorted_energy, int32_t *order, float *avg_pose, double *sorted_rt, float *avg_rt, gp_stream_t s) {
+    if (b < 0 || k <= 0 || k > GP_CONSENSUS_MAX_K || !poses) return GP_EINVAL;
+    if (avg_pose && (sel <= 0 || sel > k)) return GP_EINVAL;
+    if (avg_rt && !avg_pose) return GP_EINVAL;
+    if (b == 0) return GP_OK;
+    const size_t lds = (size_t)k * (8 + CONS_LDS_PER_K);  // at most 108 * GP_CONSENSUS_MAX_K = 55 296 bytes: below the 64 KB default
+    if (is_f64)
+        hipLaunchKernelGGL(consensus_rank_aggregate_kernel<double>, dim3(b), dim3(64), lds, (hipStream_t)s, k, sel, (const double *)poses, sym,
+                           energy_out, (double *)sorted_poses, sorted_energy, order, avg_pose, sorted_rt, avg_rt);
+    else
+        hipLaunchKernelGGL(consensus_rank_aggregate_kernel<float>, dim3(b), dim3(64), lds, (hipStream_t)s, k, sel, (const float *)poses, sym,
+                           energy_out, (float *)sorted_poses, sorted_energy, order, avg_pose, sorted_rt, avg_rt);
+    return gp_launch_status();
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ Same inputs, same outputs and the same matching / AP rules as the reference:
   compute_ap_and_acc           utils/sgpa_utils.py:627-650
   sort_sRT, sort_sRT_by_energy utils/sgpa_utils.py:24-51, 897-954  (energy ranker; rotation and translation ranked independently)
   compute_mAP                  utils/sgpa_utils.py:957-1183  (use_matches_for_pose=True, 2-D IoU matching as evaluate() calls it)
+  consensus_energy             ours: ranker 'consensus_ranker', the host statement of gp_consensus_energy (include/genpose_hip.h, section D)
 
 Pinned by tests/golden/g10_map.npz, produced by the imported reference (oracle/gen_golden.py).
 """
@@ -24,6 +25,7 @@ from . import rotation
 
 SYNSET_NAMES = ["BG", "bottle", "bowl", "camera", "can", "laptop", "mug"]
 _Y_SYMMETRIC = ("bottle", "can", "bowl")
+_CONSENSUS_PAIRS = 1 << 22  # candidate pairs consensus_energy holds at once (it works through larger inputs in slices of instances)
 
 
 # ---------------------------------------------------------------------------------------------- containers
@@ -77,10 +79,10 @@ class DetectionResults:
 
 
 # ---------------------------------------------------------------------------------------------- ranking / aggregation
-def sort_sRT(poses, energy):
+def sort_sRT(poses, energy, stable=False):
     """poses [n,K,4,4], energy [n,K,2] -> hypotheses ranked from highest to lowest energy, rotation (and the rest of the
-    matrix) by energy[...,0], the translation column by energy[...,1]."""
-    order = np.argsort(-energy, axis=1)
+    matrix) by energy[...,0], the translation column by energy[...,1].  stable: ties keep candidate order (the device ranking's rule)."""
+    order = np.argsort(-energy, axis=1, kind="stable" if stable else None)
     sorted_energy = -np.sort(-energy, axis=1)
     rows = np.arange(poses.shape[0])[:, None]
     out = poses[rows, order[:, :, 0]].copy()
@@ -103,7 +105,35 @@ def average_sRT(selected):
     return out
 
 
-def sort_sRT_by_energy(sRT, energy=None, RT_overlaps=None, ranker="energy_ranker", ratio=1.0, error_mode="average"):
+def consensus_energy(sRT, sym=None):
+    """sRT [n,K,4,4] hypotheses -> [n,K,2] float64 consensus scores, the definition gp_consensus_energy computes on the device: minus the
+    mean distance of a hypothesis to the instance's other finite hypotheses - column 0 the geodesic angle in chordal form,
+    2 asin(min(1, |R_i - R_j|_F / (2 sqrt 2))), or for sym[n] != 0 (symmetric about the y axis) 2 asin(min(1, |y_i - y_j| / 2)) of the
+    second columns; column 1 |t_i - t_j|.  A hypothesis with a non-finite entry scores -inf and enters no other sum.  The 3x3 blocks are
+    taken as rotations as they stand (what pose9_to_RT hands on)."""
+    sRT = np.asarray(sRT, dtype=np.float64)
+    n, K = sRT.shape[:2]
+    chunk = max(1, _CONSENSUS_PAIRS // max(1, K * K))  # the pairwise differences are [n,K,K,3,3] float64: ~0.3 GB per temporary at most
+    if n > chunk:
+        symv = None if sym is None else np.broadcast_to(np.asarray(sym), (n,))
+        return np.concatenate([consensus_energy(sRT[s:s + chunk], None if symv is None else symv[s:s + chunk]) for s in range(0, n, chunk)], axis=0)
+    R, t = sRT[:, :, :3, :3], sRT[:, :, :3, 3]
+    fin = np.isfinite(sRT[:, :, :3, :]).all(axis=(2, 3))
+    symv = np.zeros(n, dtype=bool) if sym is None else np.broadcast_to(np.asarray(sym).astype(bool), (n,))
+    with np.errstate(invalid="ignore", over="ignore"):
+        dF = np.sqrt(np.sum((R[:, :, None] - R[:, None, :]) ** 2, axis=(-2, -1)))
+        dy = np.sqrt(np.sum((R[:, :, None, :, 1] - R[:, None, :, :, 1]) ** 2, axis=-1))
+        x = np.where(symv[:, None, None], dy / 2.0, dF / (2.0 * np.sqrt(2.0)))
+        d = np.stack([2.0 * np.arcsin(np.minimum(1.0, x)), np.sqrt(np.sum((t[:, :, None] - t[:, None, :]) ** 2, axis=-1))], axis=-1)
+    pair = fin[:, :, None] & fin[:, None, :] & ~np.eye(K, dtype=bool)[None]
+    sums = np.where(pair[..., None], d, 0.0).sum(axis=2)
+    score = -(sums / np.maximum(1, fin.sum(axis=1) - 1)[:, None, None])
+    score[~fin] = -np.inf
+    return score
+
+
+def sort_sRT_by_energy(sRT, energy=None, RT_overlaps=None, ranker="energy_ranker", ratio=1.0, error_mode="average", sym=None):
+    """sym (ranker 'consensus_ranker' only): per-instance flags, symmetric about the y axis."""
     n, K = sRT.shape[:2]
     m = max(1, int(K * ratio))
     if n == 0:
@@ -114,9 +144,11 @@ def sort_sRT_by_energy(sRT, energy=None, RT_overlaps=None, ranker="energy_ranker
         e = -np.min(RT_overlaps, axis=1)
     elif ranker == "random":
         e = np.random.rand(n, K, 2)  # sgpa_utils.py:926-927: numpy's global generator (seed it for a repeatable ablation)
+    elif ranker == "consensus_ranker":  # (ours) the hypotheses' mutual agreement; `energy` is ignored
+        e = consensus_energy(sRT, sym)
     else:
         raise NotImplementedError(ranker)
-    s, se = sort_sRT(sRT, e)
+    s, se = sort_sRT(sRT, e, stable=ranker == "consensus_ranker")
     s, se = s[:, :m], se[:, :m]
     if error_mode == "average":
         return s, average_sRT(s), se
@@ -331,15 +363,16 @@ def compute_mAP(pred_results, out_dir=None, degree_thresholds=(180,), shift_thre
                 c_gt_hv = c_gt_hv[keep_g] if len(keep_g) else np.zeros(0)
 
             hyp_overlaps = None
+            c_sym = np.full(len(c_hyp), synset_names[c] in _Y_SYMMETRIC) if ranker == "consensus_ranker" else None
             if ranker == "gt_ranker":
                 per_h = [compute_RT_overlaps(c_gt_ids, c_gt_sRT, c_gt_hv, c_pred_ids, c_hyp[:, i], synset_names) for i in range(c_hyp.shape[1])]
                 hyp_overlaps = np.array(per_h).transpose(1, 2, 0, 3)
             if pooling_mode == "nearest":
-                s_hyp, _, _ = sort_sRT_by_energy(c_hyp, c_energy, hyp_overlaps, ranker, ratio, "nearest")
+                s_hyp, _, _ = sort_sRT_by_energy(c_hyp, c_energy, hyp_overlaps, ranker, ratio, "nearest", sym=c_sym)
                 per_h = [compute_RT_overlaps(c_gt_ids, c_gt_sRT, c_gt_hv, c_pred_ids, s_hyp[:, i], synset_names) for i in range(s_hyp.shape[1])]
                 RT_overlaps = np.min(np.array(per_h), axis=0)
             elif pooling_mode == "average":
-                _, avg, _ = sort_sRT_by_energy(c_hyp, c_energy, hyp_overlaps, ranker, ratio, "average")
+                _, avg, _ = sort_sRT_by_energy(c_hyp, c_energy, hyp_overlaps, ranker, ratio, "average", sym=c_sym)
                 RT_overlaps = compute_RT_overlaps(c_gt_ids, c_gt_sRT, c_gt_hv, c_pred_ids, avg, synset_names)
             else:
                 raise NotImplementedError(pooling_mode)

@@ -40,9 +40,11 @@ class SingleFrameRunner:
 
     ranker: 'energy' (default: the energy agent's two energies rank the hypotheses, as the reference) or 'likelihood' (ours: the SCORE
     agent's own exact-divergence log-likelihood, PoseNet.get_likelihood under the agent's cfg.likelihood_solver / likelihood_steps, fills
-    both columns of the [n,K,2] array, cast to float32, and goes through the same ranking - no energy agent needed)."""
+    both columns of the [n,K,2] array, cast to float32, and goes through the same ranking - no energy agent needed) or 'consensus' (ours: no
+    network at all - reward.consensus_rank_aggregate scores every candidate by its mean distance to the cloud's other candidates, rotation
+    and translation independently, and ranks and aggregates in the same launch; the stored 'energy' is that array)."""
 
-    RANKERS = ("energy", "likelihood")
+    RANKERS = ("energy", "likelihood", "consensus")
 
     def __init__(self, score_agent, energy_agent=None, repeat_num=50, T0=0.55, batch_size=256, ratio=0.6, ranker="energy"):
         if ranker not in self.RANKERS:
@@ -50,16 +52,28 @@ class SingleFrameRunner:
         self.score_agent, self.energy_agent, self.ranker = score_agent, energy_agent, ranker
         self.repeat_num, self.T0, self.batch_size, self.ratio = repeat_num, T0, batch_size, ratio
 
-    def infer_tensors(self, clouds):
-        """clouds: device tensor [n,1024,3] -> dict of device tensors with leading dim n (usable under ShardedInference)."""
+    def infer_tensors(self, clouds, sym=None):
+        """clouds: device tensor [n,1024,3] -> dict of device tensors with leading dim n (usable under ShardedInference).
+        sym [n] (ranker 'consensus' only): clouds of objects symmetric about their y axis, compared by that axis alone."""
         n = clouds.shape[0]
+        if sym is not None:
+            if self.ranker != "consensus":
+                raise ValueError(f"sym is the consensus ranker's argument (ranker={self.ranker!r})")
+            sym = torch.as_tensor(sym)
+            if sym.shape != (n,):
+                raise ValueError(f"sym must hold one flag per cloud ([{n}]), got {tuple(sym.shape)}")
         out = {"pred_pose": [], "multi_hypothesis_pred_RTs": [], "energy": [], "sorted_RTs": [], "average_sRT": []}
         for s in range(0, n, self.batch_size):  # evaluation_single.py:380-382 batch slicing
             sample = make_batch_sample(clouds[s:s + self.batch_size])
             pred = self.score_agent.pred_func(data=sample, repeat_num=self.repeat_num, save_path=None, T0=self.T0)
             out["pred_pose"].append(pred)
             out["multi_hypothesis_pred_RTs"].append(rotation.pose9_to_RT(pred))
-            if self.ranker == "likelihood" or self.energy_agent is not None:
+            if self.ranker == "consensus":
+                r = reward.consensus_rank_aggregate(pred, None if sym is None else sym[s:s + self.batch_size], ratio=self.ratio)
+                out["energy"].append(r["energy"])
+                out["sorted_RTs"].append(rotation.pose9_to_RT(r["sorted_poses"]))
+                out["average_sRT"].append(rotation.quat_trans_to_RT(r["avg_pose"].double()))
+            elif self.ranker == "likelihood" or self.energy_agent is not None:
                 if self.ranker == "likelihood":
                     # (pred_func left the clouds' features in the dict) higher = more likely = first, in both columns
                     ll32 = self.score_agent.get_likelihood(sample, pred, extract_pts_feature=False).float()
@@ -72,10 +86,10 @@ class SingleFrameRunner:
                 out["average_sRT"].append(rotation.quat_trans_to_RT(r["avg_pose"].double()))
         return {k: torch.cat(v, dim=0) for k, v in out.items() if v}
 
-    def infer(self, clouds, device="cuda"):
+    def infer(self, clouds, device="cuda", sym=None):
         """clouds: array-like [n,1024,3].  Returns dict of numpy arrays (+ 'pred_pose' [n,K,9])."""
         clouds = torch.as_tensor(np.asarray(clouds), dtype=torch.float32).to(device)
-        return {k: v.cpu().numpy() for k, v in self.infer_tensors(clouds).items()}
+        return {k: v.cpu().numpy() for k, v in (self.infer_tensors(clouds) if sym is None else self.infer_tensors(clouds, sym)).items()}
 
 
     def evaluate(self, detect_result, out_dir=None, degree_thresholds=tuple(range(0, 46)), shift_thresholds=tuple(i / 2 for i in range(21)),
@@ -88,12 +102,15 @@ class SingleFrameRunner:
         if self.ranker == "likelihood":
             if ranker == "energy_ranker":
                 ranker = "likelihood_ranker"  # the array stored as 'energy' holds the log-likelihoods: ranked as it stands
+        elif self.ranker == "consensus":
+            if ranker == "energy_ranker":
+                ranker = "consensus_ranker"  # compute_mAP scores the stored hypotheses itself, the symmetric categories by their y axis
         elif self.energy_agent is None:
             raise ValueError("evaluation needs the energy agent (hypotheses are ranked by energy)")
         store = evaluation.DetectionResults(detect_result, self.repeat_num)
         for cat in store.by_category:
             for sl, pts in store.batches(cat, self.batch_size):
-                res = self.infer(pts)
+                res = self.infer(pts, sym=np.full(len(pts), cat in evaluation._Y_SYMMETRIC)) if self.ranker == "consensus" else self.infer(pts)
                 sorted_energy = -np.sort(-res["energy"], axis=1)  # sort_poses_by_energy's second output (reward.py:146-147)
                 store.write(cat, sl, res["sorted_RTs"], sorted_energy)
         maps = evaluation.compute_mAP(store.results(), out_dir, list(degree_thresholds), list(shift_thresholds), list(iou_thresholds),
@@ -503,12 +520,16 @@ class FixedStepTracker:
 
     ranker: 'energy' - the energy agent's two energies at T = 1e-5; 'likelihood' - the score agent's own exact-divergence log-likelihood by
     samplers.HeunLikelihood (cfg.likelihood_steps, else the tracker's steps; cfg.likelihood_grid) in both columns, cast to float32 as
-    SingleFrameRunner does: tracking from a score checkpoint alone.
+    SingleFrameRunner does: tracking from a score checkpoint alone; 'consensus' - no ranking network either: the candidates' mutual
+    agreement, scored, ranked and aggregated by ONE launch (gp_consensus_rank_aggregate_rt) in place of the likelihood solve and
+    gp_rank_aggregate_rt - the score agent's embed graph and the frame's graph, last_stats['replays'] == 2.
+    symmetric (ranker 'consensus'): callable model_name -> bool, True for objects symmetric about their y axis (their candidates are compared
+    by that axis alone); None: no object is.  The flags are uploaded only in a step whose names differ from the previous step's.
     launches: 'single' / 'chain' force the solve's form; None takes 'single' below SINGLE_MAX_ROWS rows where the plan is a tile plan.
     solver: 'heun' (default) or 'dpm2m' - the same frame with samplers.Dpm2mSampler's solve (steps + 1 evaluations instead of 2 steps + 1)
     in HeunSampler's place; everything around the solve is unchanged."""
 
-    RANKERS = ("energy", "likelihood")
+    RANKERS = ("energy", "likelihood", "consensus")
     SOLVERS = ("heun", "dpm2m")
     LAUNCHES = (None, "single", "chain")
     # rows below which launches=None takes the one-launch solve.  profiles/fixed_step_tracking.txt: its median lay below the chain's minimum
@@ -518,7 +539,7 @@ class FixedStepTracker:
     RING = 4  # pinned blocks in rotation: the host rewrites one only after the copy issued four steps earlier has completed
 
     def __init__(self, score_agent, energy_agent=None, steps=8, repeat_num=50, T0=0.15, ratio=0.6, ranker="energy", seed=0, launches=None,
-                 grid="geometric", max_objects_per_frame=8, solver="heun"):
+                 grid="geometric", max_objects_per_frame=8, solver="heun", symmetric=None):
         from .samplers import HEUN_GRIDS
         if solver not in self.SOLVERS:
             raise ValueError(f"FixedStepTracker(solver={solver!r}): one of {self.SOLVERS}")
@@ -528,6 +549,8 @@ class FixedStepTracker:
             raise ValueError(f"FixedStepTracker(ranker={ranker!r}): one of {self.RANKERS}")
         if ranker == "energy" and energy_agent is None:
             raise ValueError("FixedStepTracker(ranker='energy') needs energy_agent (ranker='likelihood' tracks from the score agent alone)")
+        if symmetric is not None and (ranker != "consensus" or not callable(symmetric)):
+            raise ValueError("FixedStepTracker(symmetric=...): a callable model_name -> bool, for ranker='consensus'")
         if launches not in self.LAUNCHES:
             raise ValueError(f"FixedStepTracker(launches={launches!r}): one of {self.LAUNCHES}")
         if grid not in HEUN_GRIDS:
@@ -544,7 +567,7 @@ class FixedStepTracker:
         self.score_agent, self.energy_agent = score_agent, energy_agent if ranker == "energy" else None
         self.steps, self.repeat_num, self.T0, self.ratio = int(steps), int(repeat_num), float(T0), ratio
         self.ranker, self.seed, self.launches, self.grid = ranker, int(seed) % (1 << 64), launches, grid
-        self.max_objects, self.solver = int(max_objects_per_frame), solver
+        self.max_objects, self.solver, self.symmetric = int(max_objects_per_frame), solver, symmetric
         self.buffers, self.frame_index = [], []
         self._embed = self._prev = None
         self._b = ShapeCache(self.MAX_SHAPES)
@@ -608,6 +631,10 @@ class FixedStepTracker:
             lo += c
         smp._launch_all()
         pred = smp.out.view(n, K, 9)
+        if self.ranker == "consensus":  # score, ranking, aggregation and both 4x4 forms: one launch
+            r = reward.consensus_rank_aggregate(pred, ent["sym"], selected_num=ent["sel"], with_rt=True)
+            self._prev.index_copy_(0, ent["dst"], r["avg_RT"])
+            return init_x, pred, r["energy"], r["sorted_RTs"], r["avg_RT"]
         pose = pred.clone()
         pose[:, :, 6:] -= centre.unsqueeze(1)  # posenet_agent.py:516: translations relative to the cloud centre
         if self.ranker == "energy":
@@ -644,6 +671,11 @@ class FixedStepTracker:
                "pin_fb": [torch.zeros(n, 4, 4).pin_memory() for _ in range(self.RING)],
                "ev": [None] * self.RING}
         smp._write_schedule(self.T0, net.sampling_eps)
+        if self.ranker == "consensus":  # the symmetry flags: static, read by the captured launch; NULL (no object symmetric) without `symmetric`
+            ent["sym"] = ent["sym_host"] = None
+            if self.symmetric is not None:
+                ent["sym"], ent["sym_host"] = torch.zeros(n, dtype=torch.int8, device=dev), [0] * n
+                ent["pin_sym"] = [torch.zeros(n, dtype=torch.int8).pin_memory() for _ in range(self.RING)]
         if self.ranker == "likelihood":
             lsteps = getattr(net.cfg, "likelihood_steps", None) or self.steps
             lk = ent["lik"] = HeunLikelihood(net.pose_score_net, n, K, dev, int(lsteps), grid=getattr(net.cfg, "likelihood_grid", "geometric"), use_graph=False)
@@ -708,6 +740,12 @@ class FixedStepTracker:
                 ent["pin_src"][slot].copy_(torch.tensor(src, dtype=torch.int32))
                 ent["src"].copy_(ent["pin_src"][slot], non_blocking=True)
                 ent["src_host"] = src
+            if self.symmetric is not None:
+                sym = [int(bool(self.symmetric(name))) for i in live for name in frames[i][1]]
+                if sym != ent["sym_host"]:
+                    ent["pin_sym"][slot].copy_(torch.tensor(sym, dtype=torch.int8))
+                    ent["sym"].copy_(ent["pin_sym"][slot], non_blocking=True)
+                    ent["sym_host"] = sym
             words = np.zeros((len(live), 8), dtype=np.uint32)
             for q, i in enumerate(live):
                 base = i * self.max_objects * K

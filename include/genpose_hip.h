@@ -656,6 +656,29 @@ int gp_rank_aggregate_rt(int b, int k, int sel, int is_f64, const void *poses, c
 int gp_pose9_to_rt(int n, int is_f64, const void *pose, double *out, gp_stream_t s);
 int gp_quat_trans_to_rt(int n, const float *quat_trans, float *out, gp_stream_t s);
 
+/* Consensus ranker (ours): an "energy" array [b,k,2] f32 for gp_rank_aggregate(_rt) that needs no network - a candidate's score is minus
+ * its mean distance to the cloud's other candidates (higher = closer to the rest = first), rotation (column 0) and translation (column 1)
+ * independently.  In float64, for cloud b with candidates i = 0..k-1:
+ *   R_i   the Gram-Schmidt matrix of pose[0:6] (gp_pose9_to_rt's, same 1e-12 floors), t_i = pose[6:9];
+ *   candidate i is finite when all nine inputs are; m = the cloud's finite candidates;
+ *   dR_ij = 2 asin(min(1, |R_i - R_j|_F / (2 sqrt 2)))   the geodesic angle in chordal form (sym[b] == 0), or
+ *           2 asin(min(1, |y_i - y_j| / 2))              y = the second column of R (sym[b] != 0: symmetric about the y axis);
+ *   dT_ij = |t_i - t_j|_2;
+ *   s_i[c] = -(sum over finite j != i, ascending j, of d_ij) / max(1, m - 1), stored as float32.
+ * A non-finite candidate scores -inf in both columns and enters no other sum.  d_ij is bitwise symmetric (element differences squared and
+ * summed in one fixed order), so duplicates and k = 2 tie exactly and the stable ranking keeps candidate order.  No tunable.
+ * One wave per cloud; every candidate's R and t sit in LDS in float64 (100 bytes each, + 8 for the ranking), which serves
+ * k <= GP_CONSENSUS_MAX_K within the default 64 KB; a larger k returns GP_EINVAL.  sym: int8 [b] or NULL (no cloud symmetric).
+ * Cost: k (k - 1) float64 distances per cloud on ONE wave - measured (profiles/consensus_ranker.txt) 29 us at k = 50 and 2.2 ms at the cap,
+ * whatever b up to the device's wave slots; it is meant for tens of candidates. */
+#define GP_CONSENSUS_MAX_K 512
+int gp_consensus_energy(int b, int k, int is_f64, const void *poses, const int8_t *sym, float *energy_out, gp_stream_t s);
+/* The score followed by everything gp_rank_aggregate_rt does, in ONE launch: bit for bit gp_consensus_energy + gp_rank_aggregate_rt.
+ * energy_out [b,k,2] is optional like every output; argument rules as gp_rank_aggregate_rt.  It saves a launch and the round trip of the
+ * array (1.2 - 1.5 us of 51 - 54 at k = 50); at k = 512 it was measured SLOWER than the two launches (2.62 against 2.54 ms). */
+int gp_consensus_rank_aggregate_rt(int b, int k, int sel, int is_f64, const void *poses, const int8_t *sym, float *energy_out, void *sorted_poses,
+                                   float *sorted_energy, int32_t *order, float *avg_pose, double *sorted_rt, float *avg_rt, gp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
