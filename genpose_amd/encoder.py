@@ -8,7 +8,9 @@ forward(pts [B,N,3] f32 on the GPU) -> [B,1024].  Launch sequence per call (all 
                         the hidden-layer layout the weights were packed for, weights.SAScale); grouping level 2 (128-196-256) by default
                         through gp_sa_pre_mlp_max_bf16x9: the same job with layers 2-3 as exact-product split bf16
   1 + 2 x the same pair  GroupAll level: whole rounds of 256 clouds on the ring kernel (one cloud per workgroup), the rest on 32-row tiles
-                        (the tiles of a cloud combine by integer atomic max into a zeroed buffer)
+                        (the tiles of a cloud combine by integer atomic max into a zeroed buffer); under level3 = 'bf16x9', from
+                        LEVEL3_BF16X9_MIN_CLOUDS clouds up, ONE gp_sa_groupall_bf16x9 instead: all three layers of both scales as
+                        exact-product split bf16 from the level-2 features (no hoisted GEMM, no zeroing)
 Intermediate features stay point-major [B, n, C]; the reference's grouped [B,C+3,np,ns] tensors never exist.
 
 Points per cloud.  Any N >= the first level's npoint (512 in every shipped configuration) is served; fewer points than level 0 selects
@@ -50,7 +52,7 @@ def _unpin_entry(key, ent):
 
 
 class Pointnet2EncoderHIP:
-    def __init__(self, state_dict, device="cuda", params="light", prefix="pts_encoder.", arith=None, precision="f32"):
+    def __init__(self, state_dict, device="cuda", params="light", prefix="pts_encoder.", arith=None, precision="f32", level3=None):
         """arith: contraction convention of the squared distances in furthest point sampling and the ball queries ('A' | 'B' | 'C',
         config.DEFAULT_DIST_ARITH when None; include/genpose_hip.h GP_ARITH_*).
         precision: 'f32' (default of this class): every dense layer on the fp32 matrix pipe.
@@ -59,10 +61,18 @@ class Pointnet2EncoderHIP:
         accumulation - the fp32 kernels' error class), every other dense layer on the fp32 matrix pipe; a scale whose folded weights do
         not split exactly keeps the fp32 kernel (`sa_kernels` says which kernel serves each scale).
         'bf16x3' (OPT-IN, exploratory, round 5): grouping levels 1 and 2 (64-64/96-128, 128-196-256) as three-term split products with
-        fp32 accumulation (csrc/sa_bf16x3.hip; ~2^-17 relative per product).  Centres and neighbourhoods are unaffected by any of them."""
+        fp32 accumulation (csrc/sa_bf16x3.hip; ~2^-17 relative per product).  Centres and neighbourhoods are unaffected by any of them.
+        level3: the GroupAll level.  None / 'f32mfma' (default of this class): gp_point_linear + the fp32 ring / tile kernels.  'bf16x9'
+        (what an agent of the PC sampler asks for by default, config.encoder_level3_of): all three layers of both scales as exact-product
+        split bf16 in one launch (csrc/sa_groupall_bf16x9.hip) for batches of LEVEL3_BF16X9_MIN_CLOUDS clouds or more; where one of the
+        level's six folded matrices does not split exactly, or the level is not the light encoder's, it keeps the fp32 kernels
+        (`level3_kernel` says which serves it)."""
         if precision not in ("f32", "bf16x3", "bf16x9"):
             raise ValueError(f"encoder precision {precision!r}: 'f32', 'bf16x9' or 'bf16x3'")
+        if level3 not in (None, "f32mfma", "bf16x9"):
+            raise ValueError(f"encoder level3 {level3!r}: 'f32mfma' or 'bf16x9'")
         self.precision = precision
+        self.level3 = level3 or "f32mfma"
         self.device = torch.device(device)
         self.arith = dist_arith_code(arith)
         self.w = EncoderWeights(state_dict, self.device, params, prefix)
@@ -75,6 +85,7 @@ class Pointnet2EncoderHIP:
         self._seen_once = ShapeCache(4 * self.MAX_PASS_GRAPHS)
         # which kernel serves each (level, scale) of the grouping levels: 'f32mfma' | 'bf16x9' | 'bf16x3' (bf16x3 also needs whole 32-row
         # units of the batch at hand, see forward)
+        self.level3_kernel = "bf16x9" if self.level3 == "bf16x9" and self.w.groupall_bf16x9_packs() is not None else "f32mfma"
         self.sa_kernels = {}
         for k, npnt in enumerate(self.cfg["npoints"]):
             if npnt is None:
@@ -89,6 +100,9 @@ class Pointnet2EncoderHIP:
                 self.sa_kernels[(k, i)] = name
 
     MAX_WORKSPACES = 12
+    # batches from this many clouds up take the split-bf16 GroupAll kernel under level3 = 'bf16x9' (one 128-row item per CU and scale:
+    # below, the fp32 tile kernels split finer; measured crossover, profiles/sa_groupall_bf16x9.txt)
+    LEVEL3_BF16X9_MIN_CLOUDS = 128
     # (layer widths, neighbourhood size) the exact-product split-bf16 kernel is instantiated for: grouping level 2 (csrc/sa_bf16x9.hip)
     BF16X9_SHAPES = {((128, 196, 256), 16), ((128, 196, 256), 32)}
     # (layer widths, neighbourhood size) the opt-in split-bf16 kernel is instantiated for: grouping levels 1 and 2 (csrc/sa_bf16x3.hip)
@@ -353,6 +367,17 @@ class Pointnet2EncoderHIP:
             if npnt is None:
                 # GroupAll: same hoisted form - layer 1's feature half is one GEMM over all B*n points (both scales), the
                 # tiles of a cloud combine through an integer atomic max into the zeroed output
+                if self.level3_kernel == "bf16x9" and B >= self.LEVEL3_BF16X9_MIN_CLOUDS:
+                    # all three layers of both scales as exact-product split bf16, straight from the level-2 features: one launch, every
+                    # output column written whole (no hoisted rows, no zeroing)
+                    wx9, offs = self.w.groupall_bf16x9_packs()
+                    sargs = []
+                    for i, sc in enumerate(scales):
+                        (_, b1), (_, b2), (_, b3) = sc.layers
+                        sargs += [sc.couts[1], ptr(wx9[offs[i]:]), ptr(sc.wxyz), ptr(b1), ptr(b2), ptr(b3), i * sc.couts[2]]
+                    _lib.call("gp_sa_groupall_bf16x9", B, n, cin, scales[0].couts[0], scales[0].couts[2], ptr(xyz), ptr(feats), *sargs, ptr(out), cout_total, st)
+                    feats, n, cin = out, 1, cout_total
+                    break
                 out.zero_()
                 z = ws["z"][k]
                 zstride = sum(sc.couts[0] for sc in scales)

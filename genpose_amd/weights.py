@@ -225,8 +225,31 @@ def pack_sa_bf16x9(W2, W3):
     return torch.cat([w2, w3], dim=0).contiguous()
 
 
+def pack_groupall_bf16x9(W1, W2, W3):
+    """One scale of the GroupAll level - layer 1's feature half [256, 512], layer 2 [C2, 256] and layer 3 [512, C2], C2 = 256 | 384 - ->
+    int16 [80 | 104 slices][8 chunks][3][64][8]: the stream of csrc/sa_groupall_bf16x9.hip's ring in the order it is consumed.  For half
+    h = 0, 1: layer 1's output chunks 8 h .. 8 h + 7 over its 16 k-blocks (16 slices), then layer 2's k-blocks 4 h .. 4 h + 3, each as C2 / 128
+    slices of 8 output chunks (8 | 12 slices); then layer 3 as (group q of 8 output chunks, k-block) = 4 x C2 / 32 slices.  Fragments, k
+    order and the exactness check are pack_bf16x9's."""
+    c2 = W2.shape[0]
+    if tuple(W1.shape) != (256, 512) or c2 not in (256, 384) or W2.shape[1] != 256 or tuple(W3.shape) != (512, c2):
+        raise ValueError(f"GroupAll shapes [256, 512], [256 | 384, 256], [512, C2] expected, got {tuple(W1.shape)}, {tuple(W2.shape)}, {tuple(W3.shape)}")
+    nh2, kb3 = c2 // 128, c2 // 32
+    w1 = pack_bf16x9(W1, 16, 16)                                             # [kb 16][chunk 16][3][64][8]
+    w2 = pack_bf16x9(W2, 8 * nh2, 8).reshape(8, nh2, 8, 3, 64, 8)            # [kb 8][chunk third / half][8]
+    w3 = pack_bf16x9(W3, 32, kb3)                                            # [kb][chunk 32]
+    parts = []
+    for h in range(2):
+        parts.append(w1[:, 8 * h:8 * h + 8])                                 # 16 slices
+        parts.append(w2[4 * h:4 * h + 4].reshape(4 * nh2, 8, 3, 64, 8))
+    parts += [w3[:, 8 * q:8 * q + 8] for q in range(4)]
+    return torch.cat(parts, dim=0).contiguous()
+
+
 class EncoderWeights:
     def __init__(self, sd, device, params="light", prefix="pts_encoder."):
+        self._device = device
+        self._groupall_x9 = None
         if params not in ENCODER_CFGS:
             raise NotImplementedError(params)
         self.cfg = ENCODER_CFGS[params]
@@ -243,6 +266,26 @@ class EncoderWeights:
             self.z_weights.append(pack_weight(torch.cat([sc.w1_feat for sc in scales], dim=0)).to(device) if cin > 0 else None)
             cin = sum(s.couts[-1] for s in scales)
         self.out_dim = cin
+
+    def groupall_bf16x9_packs(self):
+        """Operands of the exact-product split-bf16 GroupAll kernel (csrc/sa_groupall_bf16x9.hip): -> (w, slice offset of every scale) - the
+        six matrices of the level's two scales as ONE int16 device tensor [80 + 104 slices][8][3][64][8] in the order the ring consumes them
+        (pack_groupall_bf16x9 per scale) - or None where the level is not the light encoder's (128 points x 512 -> (256, 256 | 384, 512), two
+        scales) or ANY of the six does not split exactly into three normal bf16 terms (split_bf16x9): the whole level then keeps the fp32
+        kernels."""
+        if self._groupall_x9 is None:
+            self._groupall_x9 = False
+            k = len(self.levels) - 1
+            scales = self.levels[k]
+            if self.cfg["npoints"][k] is None and k >= 1 and self.cfg["npoints"][k - 1] == 128 and len(scales) == 2:
+                try:
+                    packs = [pack_groupall_bf16x9(sc.w1_feat, sc._folded_plain[1][0], sc._folded_plain[2][0]) for sc in scales]
+                except ValueError:
+                    packs = None
+                if packs is not None:
+                    offs = [0, packs[0].shape[0]]
+                    self._groupall_x9 = (torch.cat(packs, dim=0).contiguous().to(self._device), offs)
+        return self._groupall_x9 or None
 
 
 class PointNetWeights:

@@ -195,6 +195,20 @@ int gp_sa_pre_mlp_max_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c
                              const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w23_x9, const float *bias2,
                              const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s);
 
+/* The GroupAll level of the light encoder (n = 128 points, cin = 512 features, c1 = 256, c3 = 512, c2 = 256 | 384 per scale) in ONE launch
+ * with all three dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (csrc/sa_groupall_bf16x9.hip; the arithmetic of
+ * gp_sa_pre_mlp_max_bf16x9): the job of gp_point_linear (hoisted feature half of layer 1) + gp_sa_pre_mlp_max_layout per scale, from
+ * feat [b, 128, 512] directly - no hoisted rows in memory, no zeroed output, no atomics; out[b, cout_off : cout_off + 512] of every scale
+ * is written whole, and a cloud's values do not depend on b or on its position.  xyz [b, 128, 3] absolute coordinates.  Per scale (_a, and
+ * _b unless c2_b = 0 = one scale): w = the three matrices as hi / mid / lo bf16 triples in the kernel's streaming order
+ * (genpose_amd/weights.py: pack_groupall_bf16x9 - [80 | 104 slices][8 chunks][3][64][8] bf16), wxyz [256][4] rows (wx, wy, wz, 0), biases
+ * [256], [c2], [512], channel order as trained.  GP_EINVAL for any other shape, a misaligned pointer (16 bytes: feat, w, wxyz; 4 the rest),
+ * overlapping or out-of-range output columns; b = 0 returns GP_OK. */
+int gp_sa_groupall_bf16x9(int b, int n, int cin, int c1, int c3, const float *xyz, const float *feat, int c2_a, const void *w_a, const float *wxyz_a,
+                          const float *bias1_a, const float *bias2_a, const float *bias3_a, int cout_off_a, int c2_b, const void *w_b,
+                          const float *wxyz_b, const float *bias1_b, const float *bias2_b, const float *bias3_b, int cout_off_b, float *out,
+                          int cout_total, gp_stream_t s);
+
 /* Vanilla PointNet encoder, PointNetfeat(num_points, out_dim=1024) without BatchNorm (networks/pts_encoder/pointnets.py:83-123; the agent's
  * cfg.pts_encoder = 'pointnet' | 'pointnet_and_pointnet2', networks/posenet.py:36-46, 79-90).  csrc/pointnet.hip: per-point MLP chains on
  * fp32 MFMA over 48-point tiles, bias after the product, ReLU where the reference has it; the [b, n, 1024] and [b, n, 512] activations of
