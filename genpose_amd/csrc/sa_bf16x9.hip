@@ -9,15 +9,21 @@
 // 16: every weight fragment read from LDS feeds two B tiles), activations register-resident from the gather to the pooled output, layer 1
 // on the fp32 VALU with the fp32 kernel's arithmetic, layer 3 transposed (activations as the A operand, lane = channel) in halves of eight
 // output chunks, max over the points before bias + ReLU - except that three terms per weight do not leave layer 2 LDS-resident
-// (128 x 208 x 3 x 2 B = 160 KB), so BOTH layers stream through a 2-slot LDS ring in 22 slices of 24 KB = (one 32-wide k-block) x (8
+// (128 x 208 x 3 x 2 B = 160 KB), so BOTH layers stream through a 2-slot LDS ring in slices of 24 KB = (one 32-wide k-block) x (8
 // output chunks) x (hi, mid, lo): layer 2 as (k-block, chunk half) = 8 slices (13 chunks padded to 16 with zero weights; the MFMAs of the
-// padding chunks are skipped), layer 3 as (half, k-block) = 14.  Slice s + 1 (held in registers since step s - 1) is written into the other
+// padding chunks are skipped), layer 3 as (half, k-block) = 12.  Slice s + 1 (held in registers since step s - 1) is written into the other
 // slot while slot s is multiplied, slice s + 2 is requested, one barrier per slice; the slice in flight stays in flight across the barrier.
 // Hidden activations stay in fp32 registers and are split one k-block at a time as the next layer consumes them.
-// The 196-wide layer is padded to 208 outputs (zero weights, zero bias: ReLU(0) = 0) and 224 layer-3 inputs (chunk 13 is a literal zero).
-// Budget per workgroup iteration (256 rows; MI355X: v_mfma_f32_16x16x32_bf16 16 cycles, LDS 128 B/clk/CU):
-//   MFMA                (4 x 13 + 7 x 16) chunks x 9 products x 2 tiles = 2 952 per wave x 16 cycles x 2 waves per SIMD = 94 k cycles
-//   LDS fragment reads  (52 + 112) KB x 3 terms x 8 waves = 3.9 MB -> 31 k cycles;  ring writes 528 KB
+// The 196-wide layer is padded to 208 outputs (zero weights, zero bias: ReLU(0) = 0).  Layer 3's K = 196 = 6 x 32 + 4: six k-blocks go
+// through the ring, and the K TAIL OF FOUR (hidden channels 192-195 = chunk 12, lane group 0) is ONE v_mfma_f32_16x16x4_f32 per (output
+// chunk, tile) on fp32 weights rebuilt exactly, (hi + mid) + lo, from the stream in the prologue (4 KB of LDS) - an exact-product fmaf chain,
+// the fp32 kernels' arithmetic; it OPENS each layer-3 accumulator, before the first ring step, for every row alike.  The packed stream keeps
+// its 22 slices (weights.py: pack_sa_bf16x9); the ring consumes 20: of slices 14 and 21 (layer 3's seventh k-block of either half) only the
+// tail's 256 x 4 x 3 terms are read, once - nothing of layer-3 columns >= 196.
+// Budget per workgroup iteration (256 rows; MI355X: v_mfma_f32_16x16x32_bf16 16 cycles, v_mfma_f32_16x16x4_f32 32, LDS 128 B/clk/CU):
+//   MFMA                (4 x 13 + 6 x 16) chunks x 9 products x 2 tiles = 2 664 per wave x 16 cycles + 16 chunks x 2 tiles x 32 cycles
+//                       = 43.6 k cycles per wave (47.2 k with the tail as a seventh k-block) x 2 waves per SIMD = 87 k cycles
+//   LDS fragment reads  (52 + 96) KB x 3 terms x 8 waves = 3.5 MB -> 28 k cycles;  ring writes 480 KB
 // so the matrix pipe bounds it.
 #include "bf16x9.h"
 #include "sa_rows.h"
@@ -31,7 +37,7 @@ struct SAX9Args {
     const float *xyz, *new_xyz, *z;
     const int32_t *idx;
     const float *wxyz, *b1;  // layer 1 stays on the fp32 VALU (three FMAs per channel on top of the hoisted feature half)
-    const bf16x8 *w;         // [22 slices][8 chunks][3 = hi, mid, lo][64 lanes] (weights.py: pack_sa_bf16x9)
+    const bf16x8 *w;         // [22 slices][8 chunks][3 = hi, mid, lo][64 lanes] (weights.py: pack_sa_bf16x9); slices 14, 21: the K tail only
     const float *b2;         // [224] (zero padded)
     const float *b3;         // [256]
     float *out;
@@ -43,9 +49,14 @@ constexpr int SX_KB1 = SX_C1 / 32, SX_NC2 = (SX_C2 + 15) / 16, SX_KB2 = (SX_NC2 
 constexpr int SX_NWV = 8, SX_NTH = 64 * SX_NWV;
 constexpr int SX_SLICE = SX_NCS * 3 * 64;  // bf16x8 (16 B) per slice = 24 KB
 constexpr int SX_PER_T = SX_SLICE / SX_NTH;
-constexpr int SX_NSL = 2 * SX_KB1 + SX_NHALF * SX_KB2;  // slices per iteration: 8 + 14
-constexpr size_t SX_LDS = (size_t)(2 * SX_SLICE + SX_C1) * 16 + (size_t)(32 * SX_KB2 + SX_C3) * sizeof(float);
+constexpr int SX_KB3 = SX_C2 / 32, SX_KT = SX_C2 - 32 * SX_KB3;  // layer 3's K: whole k-blocks through the ring + the tail (fp32 MFMA)
+constexpr int SX_NSL = 2 * SX_KB1 + SX_NHALF * SX_KB2;            // slices of the packed stream: 8 + 14
+constexpr int SX_NRING = 2 * SX_KB1 + SX_NHALF * SX_KB3;          // slices the ring consumes per iteration: 8 + 12
+constexpr int SX_TAIL0 = 2 * SX_KB1 + SX_KB3;                     // the tail's slice of half h: SX_TAIL0 + h SX_KB2 (14, 21) - never in the ring
+constexpr size_t SX_LDS = (size_t)(2 * SX_SLICE + SX_C1) * 16 + (size_t)(32 * SX_KB2 + SX_C3 + SX_KT * SX_C3) * sizeof(float);
 static_assert(SX_NC2 > SX_NCS && SX_NC2 <= 2 * SX_NCS && SX_NC2 - SX_NCS >= SX_PER_T && SX_PER_T * SX_NTH == SX_SLICE, "slice geometry");
+static_assert(SX_KT == 4 && SX_NC2 == 2 * SX_KB3 + 1 && SX_KB2 == SX_KB3 + 1 && SX_NHALF == 2, "layer 3: six k-blocks + a K tail of four = chunk 12, lane group 0");
+static_assert(SX_NSL == 22 && SX_NRING == 20 && SX_TAIL0 + SX_KB2 == SX_NSL - 1, "the stream has 22 slices; the ring skips 14 and 21");
 static_assert(SX_LDS <= 160 * 1024, "LDS");
 
 // Keeps a value's uses behind this point (no instruction: the optimiser may not move what is computed from it further up).
@@ -57,8 +68,15 @@ struct SXRing {
     int par, snext;  // slot of the slice being multiplied; slice to request next
 };
 
+// The slice the ring consumes after slice s: the stream's next, past a tail slice (13 -> 15), wrapping to the next iteration's first
+// (20 -> 0).  Prologue (0 in the slot, 1 held, 2 to request), steady state and wrap all walk this one sequence of SX_NRING slices.
+__device__ __forceinline__ int sx_next_slice(int s) {
+    const int n = s + 1 + (s + 1 == SX_TAIL0 || s + 1 == SX_TAIL0 + SX_KB2);
+    return n >= SX_NSL ? 0 : n;
+}
+
 // One step of the ring (bf16x9.h: ring_step) over the current slot, chunks [N0, N0 + NCH) of acc; the weight stream wraps over the
-// iteration's SX_NSL contiguous slices.
+// iteration's SX_NRING slices (sx_next_slice).
 template <bool TRANSPOSED, int N0, int NCH, int NA>
 __device__ __forceinline__ void sx_step(SXRing &r, bf16x8 (&hold)[SX_PER_T], const Split8 (&xs)[2], f32x4 (&acc)[2][NA], int tid, int lane) {
     static_assert(NCH <= SX_NCS, "chunks of one slice");
@@ -66,7 +84,7 @@ __device__ __forceinline__ void sx_step(SXRing &r, bf16x8 (&hold)[SX_PER_T], con
     bf16x8 *dst = r.ring + (r.par ^ 1) * SX_SLICE;
     const bf16x8 *src = r.w + (size_t)r.snext * SX_SLICE;
     r.par ^= 1;
-    r.snext = r.snext + 1 == SX_NSL ? 0 : r.snext + 1;
+    r.snext = sx_next_slice(r.snext);
     ring_step<SX_NTH, SX_PER_T, TRANSPOSED, N0, NCH>(slot, dst, src, hold, xs, acc, tid, lane);
 }
 
@@ -79,8 +97,24 @@ __global__ __launch_bounds__(SX_NTH) void sa_chain_bf16x9_kernel(SAX9Args a, int
     f32x4 *w1l = reinterpret_cast<f32x4 *>(ring + 2 * SX_SLICE);    // [C1] rows (wx, wy, wz, b1)
     float *b2l = reinterpret_cast<float *>(w1l + C1);               // [32 KB2]
     float *b3l = b2l + 32 * KB2;                                    // [C3]
+    float *wtl = b3l + C3;                                          // [KT][C3]: layer 3's K tail W3[c][32 KB3 + e] in fp32
     const int tid = threadIdx.x, lane = tid & 63, pt = lane & 15, g = lane >> 4;
     gp_sa_rows::stage_operands<C1, 32 * KB2, C3, NTH>(a, w1l, b2l, b3l, tid);
+    // layer 3's K tail from the stream: output channel c = 16 (8 h + n) + l sits in slice (h, k-block KB3), chunk n, lane l < 16 (lane group
+    // 0: k = 32 KB3 + e for elements e < 4).  Only those 8 bytes of each term are read; (hi + mid) + lo gives the fp32 weight back exactly.
+    for (int c = tid; c < C3; c += NTH) {
+        const bf16x8 *src = a.w + (size_t)(SX_TAIL0 + (c >> 7) * KB2) * SX_SLICE + ((c >> 4) & (NCS - 1)) * 3 * 64 + (c & 15);
+        uint2 t[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[k] = *reinterpret_cast<const uint2 *>(src + k * 64);
+#pragma unroll
+        for (int e = 0; e < SX_KT; ++e) {
+            float v[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = __uint_as_float(((e < 2 ? t[k].x : t[k].y) >> (16 * (e & 1))) << 16);
+            wtl[e * C3 + c] = (v[0] + v[1]) + v[2];
+        }
+    }
     // ring prologue: slice 0 into slot 0; slice 1 held in registers (written during step 0)
     bf16x8 hold[SX_PER_T];
 #pragma unroll
@@ -146,23 +180,40 @@ __global__ __launch_bounds__(SX_NTH) void sa_chain_bf16x9_kernel(SAX9Args a, int
 #pragma unroll
             for (int s = 0; s < 2; ++s) acc2[s][n] = relu4(acc2[s][n] + bv);
         }
+        // ---- layer 3's K tail as the A operand of v_mfma_f32_16x16x4_f32: lane (pt, g) holds h2[pt][32 KB3 + g] = register g of chunk
+        // NC2 - 1 in lane pt (lane group 0); once per iteration, kept across the two halves
+        float atail[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f32x4 v = acc2[s][NC2 - 1];
+            const int from = (lo_ & 15) * 4;
+            const float t0 = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(v.x)));
+            const float t1 = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(v.y)));
+            const float t2 = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(v.z)));
+            const float t3 = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(v.w)));
+            atail[s] = g4 == 0 ? t0 : g4 == 4 ? t1 : g4 == 8 ? t2 : t3;
+        }
         // ---- layer 3 (transposed: lane = channel, registers x lane groups = the 16 points of a sub-chunk), eight output chunks at a time
 #pragma unroll 1
         for (int half = 0; half < NHALF; ++half) {
             f32x4 acc3[2][NCS];
+            // the tail opens the accumulators (a literal-zero C operand: no zero fill): B = Wtail[g][channel 16 chunk + pt].  (After the last
+            // ring step instead it measured the same: 3 119 / 3 179 against 3 122 / 3 175 us for both scales at 640 clouds.)
 #pragma unroll
-            for (int s = 0; s < 2; ++s)
+            for (int n = 0; n < NCS; ++n) {
+                const float bt = wtl[(g4 >> 2) * C3 + 16 * (half * NCS + n) + (lo_ & 15)];
 #pragma unroll
-                for (int n = 0; n < NCS; ++n) acc3[s][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int s = 0; s < 2; ++s) acc3[s][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(atail[s], bt, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            }
 #pragma unroll
-            for (int kb = 0; kb < KB2; ++kb) {
+            for (int kb = 0; kb < SX_KB3; ++kb) {
                 Split8 xs[2];
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    // (pinned: the split does not depend on `half`, and hoisted out of that loop all 14 of them would live in registers)
+                    // (pinned: the split does not depend on `half`, and hoisted out of that loop all 12 of them would live in registers)
                     sx_pin(acc2[s][2 * kb]);
-                    if (2 * kb + 1 < NC2) sx_pin(acc2[s][2 * kb + 1]);
-                    xs[s] = split8(acc2[s][2 * kb], 2 * kb + 1 < NC2 ? acc2[s][2 * kb + 1] : f32x4{0.f, 0.f, 0.f, 0.f});  // (chunk 13: the zero k-padding)
+                    sx_pin(acc2[s][2 * kb + 1]);
+                    xs[s] = split8(acc2[s][2 * kb], acc2[s][2 * kb + 1]);
                 }
                 sx_step<true, 0, NCS>(rg, hold, xs, acc3, tid, lo_);
             }

@@ -189,7 +189,8 @@ int gp_sa_pre_mlp_max_bf16x3(int b, int n, int np, int ns, int c1, int c2, int c
  * v_mfma_f32_16x16x32_bf16, fp32 accumulation - the error class of the fp32 MFMA kernel, as gp_pc_step_bf16x9 is to gp_pc_step_plan).  Layer 1,
  * the pooling, the inputs and the [b, np, c3] output columns are gp_sa_pre_mlp_max's.  w23_x9: both layers' weights as hi / mid / lo bf16
  * triples in the kernel's streaming order (genpose_amd/weights.py: pack_sa_bf16x9 - [22 slices][8 chunks][3][64][8] bf16: layer 2 as
- * (k-block, chunk half), layer 3 as (half, k-block)); bias2 [224] zero padded, bias3 [256], channel order as trained.  b * np * ns must be
+ * (k-block, chunk half), layer 3 as (half, k-block)); bias2 [224] zero padded, bias3 [256], channel order as trained.  Layer-3 columns >= 196
+ * and, of slices 14 / 21 (layer 3's seventh k-block), everything beyond k = 195 are not read.  b * np * ns must be
  * a multiple of 32.  What an agent of the PC sampler runs for this level by default (genpose_amd/config.py: encoder_level2); the fp32 entry points above stay selectable. */
 int gp_sa_pre_mlp_max_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c3, const float *xyz, const float *new_xyz, const int32_t *idx,
                              const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w23_x9, const float *bias2,
