@@ -21,6 +21,11 @@ struct SplitNet {
                        // (head, chunk pair, chunk of the pair, k-block) - the order trunk_bf16x9.h consumes (weights.pack_heads_bf16x9)
     const float *b0, *b2, *w_out, *b_out;  // fp32: biases [256], [256]; output layers [9][256], [9]
 };
+// from an entry point's arguments: the three packs as they arrive over the C ABI, the fp32 operands from the network
+static inline SplitNet split_net(const gp_scorenet *net, const void *w_pose0, const void *w_pose2, const void *w_headx) {
+    return {reinterpret_cast<const bf16x8 *>(w_pose0), reinterpret_cast<const bf16x8 *>(w_pose2), reinterpret_cast<const bf16x8 *>(w_headx),
+            net->b_pose0, net->b_pose2, net->w_out, net->b_out};
+}
 
 constexpr int NSLICES = 33;  // pose_encoder.0 (1), pose_encoder.2 (8), three heads (8 each)
 constexpr int NCL = 4;       // clouds a workgroup's 128 rows may span (gp_pc_layout)

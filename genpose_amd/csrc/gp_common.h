@@ -3,14 +3,52 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/genpose_hip.h"
 
 static inline int gp_launch_status() { return hipGetLastError() == hipSuccess ? GP_OK : GP_ELAUNCH; }
 
-// Lets a kernel use `bytes` of dynamic LDS (above the 64 KB default); callers do it once per kernel.
+// Lets a kernel use `bytes` of dynamic LDS (above the 64 KB default).  gp_prepare_lds / gp_launch below do it once per kernel; only a
+// launch whose LDS size varies from call to call (sa_mlp.hip: launch_tiles) calls it directly.
 template <typename K>
 static inline int set_lds(K kern, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? GP_OK : GP_ELAUNCH;
+}
+
+// set_lds on every kernel of the pack that has not had it yet; GP_ELAUNCH on failure (a kernel that failed is tried again by the next
+// call).  The flag is the template's, one per kernel and PROCESS: this project runs one process per device, and the launch path makes no
+// hipGetDevice call for it.  An entry point that picks one kernel of a family per call names the whole family here, so that its first
+// call - the samplers' warm-up, outside any stream capture - prepares every kernel a later call may launch.
+template <auto Kern>
+static inline int gp_prepare_lds_one(size_t bytes) {
+    static bool done = false;
+    if (!done) {
+        if (set_lds(Kern, bytes)) return GP_ELAUNCH;
+        done = true;
+    }
+    return GP_OK;
+}
+template <auto... Kern>
+static inline int gp_prepare_lds(size_t bytes) {
+    return (gp_prepare_lds_one<Kern>(bytes) || ...) ? GP_ELAUNCH : GP_OK;
+}
+
+// One launch: the kernel's LDS attribute (once), the launch, its status.
+template <auto Kern, class... A>
+static inline int gp_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
+    if (gp_prepare_lds<Kern>(lds)) return GP_ELAUNCH;
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+    return gp_launch_status();
+}
+
+// The tile plans' dispatch: f(std::integral_constant<int, P>{}) for P = 16 / 32 / 64 rows per workgroup, GP_EINVAL for any other P.
+template <class F>
+static inline int gp_with_tile(int P, F &&f) {
+    if (P == 16) return f(std::integral_constant<int, 16>{});
+    if (P == 32) return f(std::integral_constant<int, 32>{});
+    if (P == 64) return f(std::integral_constant<int, 64>{});
+    return GP_EINVAL;
 }
 
 // Compute units of the CURRENT device (MI355X: 256 in 8 XCDs), queried once per device ordinal: persistent grids are sized from it.

@@ -111,16 +111,9 @@ extern "C" int gp_heun_likelihood_step(int nclouds, int k, int launch, int nstep
     const long long R = (long long)nclouds * k;
     if (R == 0) return GP_OK;
     if (R > 0x7fffffffLL / LD_D) return GP_EINVAL;  // row and element indices are ints up to R * 10
-    const size_t lds = LDS_BYTES_EXACT;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(heun_likelihood_step_kernel, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
     HeunLikArgs a;
     a.nrows = (int)R, a.kcand = k, a.launch = launch, a.last = 2 * nsteps;
     a.cvec = cvec, a.tvec_all = tvec_all, a.sched = sched;
     a.x = x, a.d = d, a.score = score, a.div = div, a.logp = logp, a.z_out = z_out;
-    hipLaunchKernelGGL(heun_likelihood_step_kernel, dim3((unsigned)((R + DP - 1) / DP)), dim3(DNT), lds, (hipStream_t)s, a, *net);
-    return gp_launch_status();
+    return gp_launch<heun_likelihood_step_kernel>(dim3((unsigned)((R + DP - 1) / DP)), dim3(DNT), LDS_BYTES_EXACT, (hipStream_t)s, a, *net);
 }

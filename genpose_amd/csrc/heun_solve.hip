@@ -126,26 +126,29 @@ constexpr size_t solve_lds_bytes() {
     return trunk_lds_bytes<P>() + (size_t)21 * P * sizeof(float);
 }
 
+template <int SOLVER, int P>
+constexpr auto solve_kernel = heun_solve_kernel<P>;
 template <int P>
-int launch_solve(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(heun_solve_kernel<P>, solve_lds_bytes<P>())) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((heun_solve_kernel<P>), dim3(nwg), dim3(TrunkCfg<P>::NT), solve_lds_bytes<P>(), st, a, *net);
-    return gp_launch_status();
-}
+constexpr auto solve_kernel<SOLVER_DPM2M, P> = dpm2m_solve_kernel<P>;
 
-template <int P>
-int launch_dpm2m_solve(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(dpm2m_solve_kernel<P>, solve_lds_bytes<P>())) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((dpm2m_solve_kernel<P>), dim3(nwg), dim3(TrunkCfg<P>::NT), solve_lds_bytes<P>(), st, a, *net);
-    return gp_launch_status();
+// A whole solve as one launch (gp_heun_solve_tile, gp_dpm2m_solve_tile).
+template <int SOLVER>
+int solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec, const float *tvec_all,
+               const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj, hipStream_t st) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
+        return GP_EINVAL;
+    const long long rg = (long long)nclouds_per_group * k, R = ngroups * rg;
+    if (R > 0x7fffffffLL / 9) return GP_EINVAL;  // row and element indices are ints up to R * 9
+    if (R == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
+    if (rc != GP_OK) return rc;
+    const HeunArgs a = heun_args((int)R, k, 0, fixed_launches<SOLVER>(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    return gp_with_tile(P, [&](auto tile_rows) {  // (GP_EINVAL for plan 128: the chain form keeps its per-launch kernels)
+        constexpr int T = decltype(tile_rows)::value;
+        const int nwg = ngroups * (int)((rg + T - 1) / T);
+        return gp_launch<solve_kernel<SOLVER, T>>(dim3(nwg), dim3(TrunkCfg<T>::NT), solve_lds_bytes<T>(), st, a, *net);
+    });
 }
 
 }  // namespace
@@ -153,39 +156,11 @@ int launch_dpm2m_solve(const HeunArgs &a, const gp_scorenet *net, int nwg, hipSt
 extern "C" int gp_heun_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                                   const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                                   gp_stream_t s) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
-        return GP_EINVAL;
-    const long long rg = (long long)nclouds_per_group * k, R = ngroups * rg;
-    if (R > 0x7fffffffLL / 9) return GP_EINVAL;  // row and element indices are ints up to R * 9
-    if (R == 0) return GP_OK;
-    int P = 0;
-    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
-    if (rc != GP_OK) return rc;
-    if (P != 16 && P != 32 && P != 64) return GP_EINVAL;  // the chain form keeps its per-launch kernels
-    const HeunArgs a = heun_args((int)R, k, 0, gp_heun_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
-    hipStream_t st = (hipStream_t)s;
-    const int nwg = ngroups * (int)((rg + P - 1) / P);
-    if (P == 16) return launch_solve<16>(a, net, nwg, st);
-    if (P == 32) return launch_solve<32>(a, net, nwg, st);
-    return launch_solve<64>(a, net, nwg, st);
+    return solve_tile<SOLVER_HEUN>(tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj, (hipStream_t)s);
 }
 
 extern "C" int gp_dpm2m_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                                    const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                                    gp_stream_t s) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
-        return GP_EINVAL;
-    const long long rg = (long long)nclouds_per_group * k, R = ngroups * rg;
-    if (R > 0x7fffffffLL / 9) return GP_EINVAL;  // row and element indices are ints up to R * 9
-    if (R == 0) return GP_OK;
-    int P = 0;
-    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
-    if (rc != GP_OK) return rc;
-    if (P != 16 && P != 32 && P != 64) return GP_EINVAL;  // the chain form keeps its per-launch kernels
-    const HeunArgs a = heun_args((int)R, k, 0, gp_dpm2m_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
-    hipStream_t st = (hipStream_t)s;
-    const int nwg = ngroups * (int)((rg + P - 1) / P);
-    if (P == 16) return launch_dpm2m_solve<16>(a, net, nwg, st);
-    if (P == 32) return launch_dpm2m_solve<32>(a, net, nwg, st);
-    return launch_dpm2m_solve<64>(a, net, nwg, st);
+    return solve_tile<SOLVER_DPM2M>(tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj, (hipStream_t)s);
 }

@@ -94,6 +94,12 @@ constexpr int fixed_sched_row() {
     static_assert(SOLVER == SOLVER_HEUN || SOLVER == SOLVER_DPM2M, "the fixed-step solvers");
     return SOLVER == SOLVER_DPM2M ? DPM2M_SCHED : 4;
 }
+// launches of a solve (the host side of the two solvers is written once over SOLVER; each file names its kernels beside them)
+template <int SOLVER>
+static inline int fixed_launches(int nsteps, int denoise) {
+    static_assert(SOLVER == SOLVER_HEUN || SOLVER == SOLVER_DPM2M, "the fixed-step solvers");
+    return SOLVER == SOLVER_DPM2M ? gp_dpm2m_launches(nsteps, denoise) : gp_heun_launches(nsteps, denoise);
+}
 // the row of tvec_all a launch evaluates at (a bool reads as SOLVER_PC / SOLVER_HEUN)
 template <int SOLVER>
 __device__ __forceinline__ int pc_time_row(int step) {

@@ -137,13 +137,7 @@ int launch_pool(PNArgs a, int b, const float *bias_last, float *out, hipStream_t
     const long long blocks = (long long)b * a.ntiles;
     if (blocks > 0x7fffffffLL) return GP_EINVAL;
     constexpr size_t lds = lds_floats(TRUNK) * sizeof(float);
-    if (lds > 64 * 1024) {
-        static bool done = false;
-        if (!done) {
-            if (set_lds(pointnet_pool_kernel<TRUNK>, lds)) return GP_ELAUNCH;
-            done = true;
-        }
-    }
+    if (lds > 64 * 1024 && gp_prepare_lds<pointnet_pool_kernel<TRUNK>>(lds)) return GP_ELAUNCH;
     const size_t count = (size_t)b * PN_COUT;
     hipLaunchKernelGGL(pointnet_zero_keys_kernel, dim3((unsigned)((count / 4 + 255) / 256)), dim3(256), 0, st, a.keys, count / 4);
     hipLaunchKernelGGL(pointnet_pool_kernel<TRUNK>, dim3((unsigned)blocks), dim3(256), lds, st, a);

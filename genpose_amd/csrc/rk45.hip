@@ -919,6 +919,20 @@ __global__ void rk45_set_slot0_kernel(Rk45State *st, double t) {
     if (threadIdx.x == 0) set_stage(st + blockIdx.x, 0, t);
 }
 
+// gp_prepare_lds over the stage kernels S... of a plan (tile form, chain form, chain form with the split-bf16 trunk)
+template <int... S>
+struct Rk45Stages {
+    template <int P, int MODEL, bool SPLIT>
+    static int prepare_tile(size_t lds) {
+        return gp_prepare_lds<rk45_stage_kernel<P, S, MODEL, SPLIT>...>(lds);
+    }
+    template <int MODEL>
+    static int prepare_chain(size_t lds) {
+        return gp_prepare_lds<rk45_stage_chain_kernel<2, S, MODEL>...>(lds);
+    }
+    static int prepare_chain_bf16x9() { return gp_prepare_lds<rk45_stage_chain_kernel_bf16x9<S>...>(X9Lds::BYTES); }
+};
+
 }  // namespace
 
 // CHAIN: the stage kernels run in the chain form (a.bpg / a.nblocks count 128-row workgroups); the denoising evaluation of phase 5
@@ -931,40 +945,22 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
     const size_t chain_lds = MODEL == 0 ? gp_chain::Cfg<2>::LDS_BYTES : gp_chain::CfgV<2>::LDS_BYTES;
     const double *y = a.y;
     const size_t lds = MODEL == 0 ? trunk_lds_bytes<P>() : (MODEL == MODEL_EXACT ? gp_bwd::LDS_BYTES_EXACT : gp_bwd::LDS_BYTES);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if constexpr (CHAIN) {
-            if (set_lds(rk45_stage_chain_kernel<2, 0, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 1, MODEL>, chain_lds) ||
-                set_lds(rk45_stage_chain_kernel<2, 2, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 3, MODEL>, chain_lds) ||
-                set_lds(rk45_stage_chain_kernel<2, 4, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 5, MODEL>, chain_lds) ||
-                set_lds(rk45_stage_chain_kernel<2, 6, MODEL>, chain_lds) || set_lds(rk45_stage_chain_kernel<2, 7, MODEL>, chain_lds))
-                return GP_ELAUNCH;
-        }
-        if (set_lds(rk45_stage_kernel<P, 0, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 1, MODEL, SPLIT>, lds) ||
-            set_lds(rk45_stage_kernel<P, 2, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 3, MODEL, SPLIT>, lds) ||
-            set_lds(rk45_stage_kernel<P, 4, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 5, MODEL, SPLIT>, lds) ||
-            set_lds(rk45_stage_kernel<P, 6, MODEL, SPLIT>, lds) || set_lds(rk45_stage_kernel<P, 7, MODEL, SPLIT>, lds))
-            return GP_ELAUNCH;
-        if constexpr (OdeModel<MODEL>::NC == POSE) {
-            if (set_lds(rk45_finish_kernel<P, MODEL>, lds)) return GP_ELAUNCH;
-        }
-        if constexpr (!CHAIN && !SPLIT && P == 16) {
-            if (set_lds(rk45_attempt_kernel<P, MODEL>, lds)) return GP_ELAUNCH;
-        }
-        attr_done = true;
+    // every phase's first call prepares all the kernels any phase of this plan launches
+    using Stages = Rk45Stages<0, 1, 2, 3, 4, 5, 6, 7>;
+    if constexpr (CHAIN) {
+        if (Stages::template prepare_chain<MODEL>(chain_lds)) return GP_ELAUNCH;
+    }
+    if (Stages::template prepare_tile<P, MODEL, SPLIT>(lds)) return GP_ELAUNCH;
+    if constexpr (OdeModel<MODEL>::NC == POSE) {
+        if (gp_prepare_lds<rk45_finish_kernel<P, MODEL>>(lds)) return GP_ELAUNCH;
+    }
+    if constexpr (!CHAIN && !SPLIT && P == 16) {
+        if (gp_prepare_lds<rk45_attempt_kernel<P, MODEL>>(lds)) return GP_ELAUNCH;
     }
     // x9 (gp_rk45_phase_bf16x9; score model, chain form): the stage kernels with the split-bf16 trunk, everything else as it is
     if (x9 && !(CHAIN && MODEL == 0)) return GP_EINVAL;
     if constexpr (CHAIN && MODEL == 0) {
-        static bool x9_attr_done = false;
-        if (x9 && !x9_attr_done) {
-            if (set_lds(rk45_stage_chain_kernel_bf16x9<0>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<1>, X9Lds::BYTES) ||
-                set_lds(rk45_stage_chain_kernel_bf16x9<2>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<3>, X9Lds::BYTES) ||
-                set_lds(rk45_stage_chain_kernel_bf16x9<4>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<5>, X9Lds::BYTES) ||
-                set_lds(rk45_stage_chain_kernel_bf16x9<6>, X9Lds::BYTES) || set_lds(rk45_stage_chain_kernel_bf16x9<7>, X9Lds::BYTES))
-                return GP_ELAUNCH;
-            x9_attr_done = true;
-        }
+        if (x9 && Stages::prepare_chain_bf16x9()) return GP_ELAUNCH;
     }
     if ((a.hsplit == 3) != SPLIT) return GP_EINVAL;
     const dim3 grid(a.nblocks * (SPLIT ? 3 : 1)), blk(TrunkCfg<P>::NT), blk1(256);
@@ -1086,11 +1082,7 @@ static inline bool shared_plan(int nrows, int kcand, SharedPlan *sp) {
 template <int PW>
 static int rk45_attempt_shared(const OdeArgs &a0, const SharedPlan &sp, const gp_scorenet *net, double *traj, hipStream_t st) {
     const size_t lds = trunk_lds_bytes<PW>() > trunk_lds_bytes<16>() ? trunk_lds_bytes<PW>() : trunk_lds_bytes<16>();
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(rk45_attempt_shared_kernel<PW>, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
+    if (gp_prepare_lds<rk45_attempt_shared_kernel<PW>>(lds)) return GP_ELAUNCH;
     OdeArgs a = a0;
     a.hsplit = 1, a.bpg = 1 << 30, a.nblocks = sp.nwg + sp.nshared;  // one group: every tile belongs to group 0
     hipLaunchKernelGGL((rk45_attempt_shared_kernel<PW>), dim3(sp.nwg), dim3(TrunkCfg<PW>::NT), lds, st, a, *net, sp.nshared);
@@ -1255,8 +1247,7 @@ int gp_rk45_phase_bf16x9(int phase, int ngroups, int nclouds_per_group, int k, c
         return GP_EINVAL;
     if (ext_sums && ext_rows_per_group < a.rows_per_group) return GP_EINVAL;
     a.ext_sums = ext_sums, a.ext_rows = ext_rows_per_group;
-    const gp_split::SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
-                                  reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
+    const gp_split::SplitNet w = gp_split::split_net(net, w_pose0_x9, w_pose2_x9, w_headx_x9);
     return rk45_phase_impl<32, 0, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out, (hipStream_t)s,
                                         &w);
 }

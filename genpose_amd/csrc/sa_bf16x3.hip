@@ -211,18 +211,11 @@ int launch_bf16x3(const SABfArgs &a, int b, hipStream_t st) {
     constexpr int KB1 = C1 / 32, NC2 = (C2 + 15) / 16, KB2 = (NC2 + 1) / 2, NSL = (C3 / 128) * KB2;
     const size_t lds = ((size_t)KB1 * NC2 * 2 * 64 + (RING ? 3 : NSL) * 8 * 2 * 64 + C1) * 16 + (size_t)(32 * KB2 + C3) * sizeof(float);
     if (lds > 160 * 1024) return GP_EINVAL;
-    auto kern = sa_chain_bf16x3_kernel<C1, C2, C3, NS, RING>;
-    static bool done = false;
-    if (!done) {
-        if (set_lds(kern, lds)) return GP_ELAUNCH;
-        done = true;
-    }
     const int nunits = (int)(((size_t)b * a.np * NS) / 32);
     int blocks = (nunits + 7) / 8;
     const int per_cu = RING ? 1 : 2;  // persistent; the resident form (<= 90 KB of LDS, <= 128 registers for the 64-wide hidden layer) fits twice
     if (blocks > gp_num_cus() * per_cu) blocks = gp_num_cus() * per_cu;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, st, a, nunits);
-    return gp_launch_status();
+    return gp_launch<sa_chain_bf16x3_kernel<C1, C2, C3, NS, RING>>(dim3(blocks), dim3(512), lds, st, a, nunits);
 }
 
 }  // namespace

@@ -227,17 +227,10 @@ __global__ __launch_bounds__(SX_NTH) void sa_chain_bf16x9_kernel(SAX9Args a, int
 
 template <int NS>
 int launch_bf16x9(const SAX9Args &a, int b, hipStream_t st) {
-    auto kern = sa_chain_bf16x9_kernel<NS>;
-    static bool done = false;
-    if (!done) {
-        if (set_lds(kern, SX_LDS)) return GP_ELAUNCH;
-        done = true;
-    }
     const int nunits = (int)(((size_t)b * a.np * NS) / 32);
     int blocks = (nunits + SX_NWV - 1) / SX_NWV;
     if (blocks > gp_num_cus()) blocks = gp_num_cus();  // persistent: one 8-wave workgroup per CU
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(SX_NTH), SX_LDS, st, a, nunits);
-    return gp_launch_status();
+    return gp_launch<sa_chain_bf16x9_kernel<NS>>(dim3(blocks), dim3(SX_NTH), SX_LDS, st, a, nunits);
 }
 
 }  // namespace

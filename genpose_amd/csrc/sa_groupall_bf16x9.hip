@@ -300,15 +300,8 @@ int gp_sa_groupall_bf16x9(int b, int n, int cin, int c1, int c3, const float *xy
     a.xyz = xyz, a.feat = feat, a.out = out, a.cout_total = cout_total, a.nsc = nsc, a.nitems = b * nsc;
     a.sc0 = GAScale{reinterpret_cast<const bf16x8 *>(w_a), wxyz_a, bias1_a, bias2_a, bias3_a, c2_a, cout_off_a};
     a.sc1 = nsc == 2 ? GAScale{reinterpret_cast<const bf16x8 *>(w_b), wxyz_b, bias1_b, bias2_b, bias3_b, c2_b, cout_off_b} : a.sc0;
-    auto kern = sa_groupall_bf16x9_kernel;
-    static bool done = false;
-    if (!done) {
-        if (set_lds(kern, GA_LDS)) return GP_ELAUNCH;
-        done = true;
-    }
     const int blocks = a.nitems < gp_num_cus() ? a.nitems : gp_num_cus();  // persistent: one 4-wave workgroup per CU
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(GA_NTH), GA_LDS, (hipStream_t)s, a);
-    return gp_launch_status();
+    return gp_launch<sa_groupall_bf16x9_kernel>(dim3(blocks), dim3(GA_NTH), GA_LDS, (hipStream_t)s, a);
 }
 
 }  // extern "C"

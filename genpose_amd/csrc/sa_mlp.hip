@@ -324,19 +324,13 @@ template <int KB, int NCW, int PT, bool PF, int WGS>
 int launch_point_linear_ws(int rows, int n_out, const float *x, const float *wpack, float *z, hipStream_t st) {
     constexpr int K = 16 * KB, R = 16 * PT;
     constexpr size_t lds = (size_t)R * (K + GP_LD_PAD) * sizeof(float);
-    static bool done = false;
-    if (!done) {
-        if (set_lds(point_linear_ws_kernel<KB, NCW, PT, PF, WGS>, lds)) return GP_ELAUNCH;
-        done = true;
-    }
     const int ntiles = (rows + R - 1) / R, nsplit = n_out / (64 * NCW);
     // persistent: WGS workgroups per CU over all channel splits, so that the splits of a tile run side by side and share its rows in the
     // L2 (a multiple of 8 in x keeps them on one XCD: the linear workgroup index is dealt round-robin over the eight)
     int gx = gp_num_cus() * WGS / nsplit;
     gx = ntiles < gx ? ntiles : gx;
     if (gx >= 8) gx &= ~7;
-    hipLaunchKernelGGL((point_linear_ws_kernel<KB, NCW, PT, PF, WGS>), dim3(gx, nsplit), dim3(256), lds, st, rows, n_out, x, wpack, z, ntiles);
-    return gp_launch_status();
+    return gp_launch<point_linear_ws_kernel<KB, NCW, PT, PF, WGS>>(dim3(gx, nsplit), dim3(256), lds, st, rows, n_out, x, wpack, z, ntiles);
 }
 
 struct SAPreArgs {
@@ -676,20 +670,13 @@ int launch_chain_lds(const SAPreArgs &a, int b, hipStream_t st) {
     constexpr int Q1 = C1 / 16, Q2 = (C2 + 15) / 16, Q3 = C3 / 16;
     static_assert(Q3 % 4 == 0, "layer-3 width must be a multiple of 64");
     const size_t lds = ((size_t)(Q1 * Q2 + Q2 * Q3) * 64 + C1) * sizeof(f32x4);
-    auto kern = sa_chain_lds_kernel<C1, C2, C3, NS>;
-    static bool done = false;
-    if (!done) {
-        if (set_lds(kern, lds)) return GP_ELAUNCH;
-        done = true;
-    }
     const int ncentres = b * a.np;
     // persistent workgroups per CU: as many as the LDS holds, at most three (132-152 registers: three waves per SIMD; a third wave's VALU
     // work - layer 1, bias + ReLU, pooling - runs under the other two's MFMAs)
     const int fit = (int)((160 * 1024) / lds), per_cu = fit < 1 ? 1 : (fit > 3 ? 3 : fit);
     int blocks = (ncentres + 3) / 4;
     if (blocks > gp_num_cus() * per_cu) blocks = gp_num_cus() * per_cu;  // persistent: weights are staged once per workgroup
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, a, ncentres);
-    return gp_launch_status();
+    return gp_launch<sa_chain_lds_kernel<C1, C2, C3, NS>>(dim3(blocks), dim3(256), lds, st, a, ncentres);
 }
 
 // out[r][0 .. 4 w4) = 0 for the rows of a [rows][ld] tensor: the zeroed output the SPLITP form below combines into
@@ -1006,14 +993,7 @@ template <int C1, int C2, int C3>
 int launch_groupall_ring(const SAPreArgs &a, int b, hipStream_t st) {
     constexpr int Q2 = C2 / 16, SLOTF = Q2 > 16 ? Q2 : 16;
     const size_t lds = ((size_t)4 * SLOTF * 64 + C1) * sizeof(f32x4) + (size_t)(8 * C3 + C2) * sizeof(float);
-    auto kern = sa_groupall_ring_kernel<C1, C2, C3>;
-    static bool done = false;
-    if (!done) {
-        if (set_lds(kern, lds)) return GP_ELAUNCH;
-        done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(b < gp_num_cus() ? b : gp_num_cus()), dim3(512), lds, st, a, b);
-    return gp_launch_status();
+    return gp_launch<sa_groupall_ring_kernel<C1, C2, C3>>(dim3(b < gp_num_cus() ? b : gp_num_cus()), dim3(512), lds, st, a, b);
 }
 
 template <int C1, int C2, int C3, int NS, bool SPREAD>
@@ -1021,36 +1001,24 @@ int launch_chain_ring(const SAPreArgs &a, int b, hipStream_t st) {
     constexpr int Q1 = C1 / 16, Q2 = (C2 + 15) / 16, Q3 = C3 / 16;
     const size_t lds = ((size_t)(Q1 * Q2 + 3 * Q3) * 64 + C1) * sizeof(f32x4) + (size_t)(16 * Q2 + C3) * sizeof(float);
     if (lds > 160 * 1024) return GP_EINVAL;
-    auto kern = sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD>;
-    static bool done = false;
-    if (!done) {
-        if (set_lds(kern, lds)) return GP_ELAUNCH;
-        done = true;
-    }
+    if (gp_prepare_lds<sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD>>(lds)) return GP_ELAUNCH;
     const int ncentres = b * a.np;
     if constexpr (NS > 16) {
         // a small batch (a tracking frame: 5 clouds = 640 neighbourhoods = 80 workgroups): the chunks of a neighbourhood go to different
         // waves while that still fits one workgroup per CU - half the iterations (89 -> ~50 us at 5 clouds)
         constexpr int PT = NS / 16;
         if (ncentres * PT <= 8 * gp_num_cus()) {
-            auto kern_s = sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD, true>;
-            static bool done_s = false;
-            if (!done_s) {
-                if (set_lds(kern_s, lds)) return GP_ELAUNCH;
-                done_s = true;
-            }
+            if (gp_prepare_lds<sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD, true>>(lds)) return GP_ELAUNCH;
             // (a KERNEL, not hipMemset2DAsync: as a memset node of a graph captured on a side stream - the tracking runner's energy-model
             // graph - the zeroing was not ordered before the kernel on replay, and the atomic max then kept stale values)
             hipLaunchKernelGGL(zero_columns_kernel, dim3((ncentres * (C3 / 4) + 255) / 256), dim3(256), 0, st, a.out + a.cout_off, a.cout_total, C3 / 4,
                                ncentres * (C3 / 4));
-            hipLaunchKernelGGL(kern_s, dim3((ncentres * PT + 7) / 8), dim3(512), lds, st, a, ncentres);
-            return gp_launch_status();
+            return gp_launch<sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD, true>>(dim3((ncentres * PT + 7) / 8), dim3(512), lds, st, a, ncentres);
         }
     }
     int blocks = (ncentres + 7) / 8;
     if (blocks > gp_num_cus()) blocks = gp_num_cus();  // persistent, one 8-wave workgroup per CU (154 KB LDS)
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, st, a, ncentres);
-    return gp_launch_status();
+    return gp_launch<sa_chain_ring_kernel<C1, C2, C3, NS, SPREAD>>(dim3(blocks), dim3(512), lds, st, a, ncentres);
 }
 
 template <int C1, int C2, int C3, int NS>
@@ -1113,13 +1081,7 @@ int gp_point_linear(int rows, int k_in, int n_out, const float *x, const float *
     if (k_in == 512 && n_out == 512) return launch_point_linear_ws<32, 1, 2, false, 2>(rows, n_out, x, wpack, z, (hipStream_t)s);
     const size_t lds = (size_t)64 * (gp_round16(k_in) + GP_LD_PAD) * sizeof(float);
     if (lds > 160 * 1024) return GP_EINVAL;
-    if (lds > 64 * 1024) {
-        static bool done = false;
-        if (!done) {
-            if (set_lds(point_linear_kernel, 160 * 1024)) return GP_ELAUNCH;
-            done = true;
-        }
-    }
+    if (lds > 64 * 1024 && gp_prepare_lds<point_linear_kernel>(160 * 1024)) return GP_ELAUNCH;
     hipLaunchKernelGGL(point_linear_kernel, dim3((rows + 63) / 64), dim3(256), lds, (hipStream_t)s, rows, k_in, n_out, x, wpack, z);
     return gp_launch_status();
 }

@@ -59,14 +59,9 @@ extern "C" int gp_score_div(int nclouds, int k, const gp_scorenet *net, const fl
     if (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t) return GP_EINVAL;
     const int R = nclouds * k;
     if (R == 0) return GP_OK;
-    const size_t lds = LDS_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(score_div_kernel<SCORE_DIV>, lds) || set_lds(score_div_kernel<ENERGY>, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(score_div_kernel<SCORE_DIV>, dim3((R + DP - 1) / DP), dim3(DNT), lds, (hipStream_t)s, R, k, *net, cvec, tvec, x, eps, sigma_dev, score, div);
-    return gp_launch_status();
+    if (gp_prepare_lds<score_div_kernel<SCORE_DIV>, score_div_kernel<ENERGY>>(LDS_BYTES)) return GP_ELAUNCH;
+    return gp_launch<score_div_kernel<SCORE_DIV>>(dim3((R + DP - 1) / DP), dim3(DNT), LDS_BYTES, (hipStream_t)s, R, k, *net, cvec, tvec, x, eps, sigma_dev, score,
+                                                  div);
 }
 
 extern "C" int gp_energy_score(int nclouds, int k, const gp_scorenet *net, const float *cvec, const float *tvec, const float *x, const float *sigma_dev,
@@ -75,14 +70,8 @@ extern "C" int gp_energy_score(int nclouds, int k, const gp_scorenet *net, const
     if (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t) return GP_EINVAL;
     const int R = nclouds * k;
     if (R == 0) return GP_OK;
-    const size_t lds = LDS_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(score_div_kernel<ENERGY>, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(score_div_kernel<ENERGY>, dim3((R + DP - 1) / DP), dim3(DNT), lds, (hipStream_t)s, R, k, *net, cvec, tvec, x, x, sigma_dev, score, energy);
-    return gp_launch_status();
+    return gp_launch<score_div_kernel<ENERGY>>(dim3((R + DP - 1) / DP), dim3(DNT), LDS_BYTES, (hipStream_t)s, R, k, *net, cvec, tvec, x, x, sigma_dev, score,
+                                               energy);
 }
 
 extern "C" int gp_score_div_exact(int nclouds, int k, const gp_scorenet *net, const float *cvec, const float *tvec, const float *x, const float *sigma_dev,
@@ -91,12 +80,5 @@ extern "C" int gp_score_div_exact(int nclouds, int k, const gp_scorenet *net, co
     if (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t) return GP_EINVAL;
     const int R = nclouds * k;
     if (R == 0) return GP_OK;
-    const size_t lds = LDS_BYTES_EXACT;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(score_div_exact_kernel, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(score_div_exact_kernel, dim3((R + DP - 1) / DP), dim3(DNT), lds, (hipStream_t)s, R, k, *net, cvec, tvec, x, sigma_dev, score, div);
-    return gp_launch_status();
+    return gp_launch<score_div_exact_kernel>(dim3((R + DP - 1) / DP), dim3(DNT), LDS_BYTES_EXACT, (hipStream_t)s, R, k, *net, cvec, tvec, x, sigma_dev, score, div);
 }

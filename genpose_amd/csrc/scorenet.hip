@@ -515,68 +515,94 @@ __global__ __launch_bounds__(gp_chain::NT, 1) void dpm2m_step_chain_kernel(HeunA
     pc_step_chain<PT, 0, false, SOLVER_DPM2M>(a, net);
 }
 
+// The kernels of a host template's arguments.  PC: seeded or not, score model (the energy model has one tile kernel and no seeded one).
+template <bool SEEDED, int P, bool SPLIT = false>
+constexpr auto pc_tile_kernel = pc_step_kernel<P, 0, SPLIT>;
+template <int P, bool SPLIT>
+constexpr auto pc_tile_kernel<true, P, SPLIT> = pc_step_seeded_kernel<P, SPLIT>;
+// The fixed-step solvers (SOLVER_HEUN / SOLVER_DPM2M): tile and chain form.
+template <int SOLVER, int P>
+constexpr auto fixed_step_kernel = heun_step_kernel<P>;
+template <int P>
+constexpr auto fixed_step_kernel<SOLVER_DPM2M, P> = dpm2m_step_kernel<P>;
+template <int SOLVER, int PT>
+constexpr auto fixed_chain_kernel = heun_step_chain_kernel<PT>;
+template <int PT>
+constexpr auto fixed_chain_kernel<SOLVER_DPM2M, PT> = dpm2m_step_chain_kernel<PT>;
+
 }  // namespace
 
-template <int PT>
-static int launch_eval_chain(int R, int k, const gp_scorenet *net, const float *cvec, const float *tvec, const float *x, const float *sigma_dev, int mode,
-                             float *out, hipStream_t st) {
-    using C = gp_chain::Cfg<PT>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(score_eval_chain_kernel<PT>, C::LDS_BYTES)) return GP_ELAUNCH;
-        attr_done = true;
+// rows per partial sum of |score| for a plan
+static int pc_rows_per_partial(int P) { return P <= 64 ? P : P / gp_chain::NW; }  // tile form: per workgroup; chain form: per wave
+static int pc_rows_per_wg(int P) { return P; }
+
+// What gp_pc_step_plan and gp_pc_step_plan_seeded do behind their own argument checks: the layout, the head-split plan's rule, PcArgs
+// and the launch.  z_lang carries the Langevin noise or, SEEDED, the seed state (PcArgs; z_pred is null then, model 0).
+template <bool SEEDED>
+static int pc_step_launch(int model, int tile, int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
+                          const float *tvec_all, const float *sched, const float *z_lang, const float *z_pred, const float *centre, float *x, float *mean_x,
+                          float *score, float *partials, float *traj, const float *gn_ext, int gn_rows_total, hipStream_t st) {
+    const int rg = nclouds_per_group * k, R = ngroups * rg;
+    if (R == 0) return GP_OK;
+    int P = 0, nparts = 0;
+    const int rc = gp_pc_layout(model, tile, ngroups, nclouds_per_group, k, &P, &nparts);
+    if (rc != GP_OK) return rc;
+    if (model == 1 && (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t)) return GP_EINVAL;
+    const bool split = P == (16 | GP_PLAN_HEADSPLIT);
+    if (split) {
+        if (gn_ext) return GP_EINVAL;  // a sharded batch's callers sum whole-tile partials between the launches: tile plans only
+        P = 16;
     }
-    hipLaunchKernelGGL((score_eval_chain_kernel<PT>), dim3((R + C::ROWS - 1) / C::ROWS), dim3(gp_chain::NT), C::LDS_BYTES, st, R, k, *net, cvec, tvec, x,
-                       sigma_dev, mode, out);
-    return gp_launch_status();
+    const int wgpg = (rg + pc_rows_per_wg(P) - 1) / pc_rows_per_wg(P);
+    const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, wgpg, cvec, tvec_all, sched, z_lang, z_pred, centre, x, mean_x, score, partials, traj, gn_ext,
+                             gn_rows_total);
+    const int nwg = a.wgpg * ngroups;
+    const dim3 chain_blk(gp_chain::NT), blk16(TrunkCfg<16>::NT);
+    if (P == 128) {
+        if constexpr (SEEDED)
+            return gp_launch<pc_step_chain_seeded_kernel<2>>(dim3(nwg), chain_blk, gp_chain::Cfg<2>::LDS_BYTES, st, a, *net);
+        else if (model == 1)
+            return gp_launch<pc_step_chain_kernel<2, 1>>(dim3(nwg), chain_blk, gp_chain::CfgV<2>::LDS_BYTES, st, a, *net);
+        else
+            return gp_launch<pc_step_chain_kernel<2, 0>>(dim3(nwg), chain_blk, gp_chain::Cfg<2>::LDS_BYTES, st, a, *net);
+    }
+    if (gp_prepare_lds<pc_tile_kernel<SEEDED, 16>, pc_tile_kernel<SEEDED, 16, true>>(trunk_lds_bytes<16>()) ||
+        gp_prepare_lds<pc_tile_kernel<SEEDED, 32>>(trunk_lds_bytes<32>()) || gp_prepare_lds<pc_tile_kernel<SEEDED, 64>>(trunk_lds_bytes<64>()))
+        return GP_ELAUNCH;
+    if constexpr (!SEEDED) {
+        if (gp_prepare_lds<pc_step_kernel<16, 1>>(gp_bwd::LDS_BYTES)) return GP_ELAUNCH;
+        if (model == 1) return gp_launch<pc_step_kernel<16, 1>>(dim3(nwg), blk16, gp_bwd::LDS_BYTES, st, a, *net);
+    }
+    if (split) return gp_launch<pc_tile_kernel<SEEDED, 16, true>>(dim3(3 * nwg), blk16, trunk_lds_bytes<16>(), st, a, *net);
+    return gp_with_tile(P, [&](auto tile_rows) {
+        constexpr int T = decltype(tile_rows)::value;
+        return gp_launch<pc_tile_kernel<SEEDED, T>>(dim3(nwg), dim3(TrunkCfg<T>::NT), trunk_lds_bytes<T>(), st, a, *net);
+    });
 }
 
-template <int PT>
-static int launch_pc_chain_seeded(const PcArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
-    const size_t lds = gp_chain::Cfg<PT>::LDS_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(pc_step_chain_seeded_kernel<PT>, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((pc_step_chain_seeded_kernel<PT>), dim3(nwg), dim3(gp_chain::NT), lds, st, a, *net);
-    return gp_launch_status();
-}
-
-template <int PT, int MODEL>
-static int launch_pc_chain(const PcArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
-    const size_t lds = MODEL == 0 ? gp_chain::Cfg<PT>::LDS_BYTES : gp_chain::CfgV<PT>::LDS_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(pc_step_chain_kernel<PT, MODEL>, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((pc_step_chain_kernel<PT, MODEL>), dim3(nwg), dim3(gp_chain::NT), lds, st, a, *net);
-    return gp_launch_status();
-}
-
-template <int PT>
-static int launch_heun_chain(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
-    const size_t lds = gp_chain::Cfg<PT>::LDS_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(heun_step_chain_kernel<PT>, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((heun_step_chain_kernel<PT>), dim3(nwg), dim3(gp_chain::NT), lds, st, a, *net);
-    return gp_launch_status();
-}
-
-template <int PT>
-static int launch_dpm2m_chain(const HeunArgs &a, const gp_scorenet *net, int nwg, hipStream_t st) {
-    const size_t lds = gp_chain::Cfg<PT>::LDS_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(dpm2m_step_chain_kernel<PT>, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((dpm2m_step_chain_kernel<PT>), dim3(nwg), dim3(gp_chain::NT), lds, st, a, *net);
-    return gp_launch_status();
+// A launch of a fixed-step solver (gp_heun_step_plan, gp_dpm2m_step_plan).
+template <int SOLVER>
+static int fixed_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                           const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                           hipStream_t st) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= fixed_launches<SOLVER>(nsteps, denoise) || !net || !cvec ||
+        !tvec_all || !sched || !centre || !x || !d || !score || !out)
+        return GP_EINVAL;
+    const int rg = nclouds_per_group * k, R = ngroups * rg;
+    if (R == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
+    if (rc != GP_OK) return rc;
+    const HeunArgs a = heun_args(R, k, launch, fixed_launches<SOLVER>(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    const int nwg = ngroups * ((rg + P - 1) / P);
+    if (P == 128) return gp_launch<fixed_chain_kernel<SOLVER, 2>>(dim3(nwg), dim3(gp_chain::NT), gp_chain::Cfg<2>::LDS_BYTES, st, a, *net);
+    if (gp_prepare_lds<fixed_step_kernel<SOLVER, 16>>(trunk_lds_bytes<16>()) || gp_prepare_lds<fixed_step_kernel<SOLVER, 32>>(trunk_lds_bytes<32>()) ||
+        gp_prepare_lds<fixed_step_kernel<SOLVER, 64>>(trunk_lds_bytes<64>()))
+        return GP_ELAUNCH;
+    return gp_with_tile(P, [&](auto tile_rows) {
+        constexpr int T = decltype(tile_rows)::value;
+        return gp_launch<fixed_step_kernel<SOLVER, T>>(dim3(nwg), dim3(TrunkCfg<T>::NT), trunk_lds_bytes<T>(), st, a, *net);
+    });
 }
 
 extern "C" {
@@ -587,14 +613,7 @@ int gp_cloud_embed(int b, const gp_scorenet *net, const float *pts_feat, float *
     if (b < 0 || !net || !pts_feat || !cvec) return GP_EINVAL;
     if (b == 0) return GP_OK;
     const size_t lds = (size_t)16 * (1024 + GP_LD_PAD) * sizeof(float);
-    auto kern = cloud_embed_kernel;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(kern, lds)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((b + 15) / 16, 3), dim3(256), lds, (hipStream_t)s, b, *net, pts_feat, cvec);
-    return gp_launch_status();
+    return gp_launch<cloud_embed_kernel>(dim3((b + 15) / 16, 3), dim3(256), lds, (hipStream_t)s, b, *net, pts_feat, cvec);
 }
 
 int gp_time_embed(int nt, const gp_scorenet *net, const float *t, float *tvec, gp_stream_t s) {
@@ -618,25 +637,21 @@ int gp_score_eval_plan(int tile, int nclouds, int k, const gp_scorenet *net, con
     if (R == 0) return GP_OK;
     const int P = tile == 0 ? score_plan_rows(R, 0, k) : tile;
     hipStream_t st = (hipStream_t)s;
-    if (P == 128) return gp_chain::Cfg<2>::fits(k) ? launch_eval_chain<2>(R, k, net, cvec, tvec, x, sigma_dev, mode, out, st) : GP_EINVAL;
-    if (P != 16 && P != 32 && P != 64) return GP_EINVAL;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(score_eval_kernel<16>, trunk_lds_bytes<16>()) || set_lds(score_eval_kernel<32>, trunk_lds_bytes<32>()) ||
-            set_lds(score_eval_kernel<64>, trunk_lds_bytes<64>()))
-            return GP_ELAUNCH;
-        attr_done = true;
+    if (P == 128) {
+        using C = gp_chain::Cfg<2>;
+        if (!C::fits(k)) return GP_EINVAL;
+        return gp_launch<score_eval_chain_kernel<2>>(dim3((R + C::ROWS - 1) / C::ROWS), dim3(gp_chain::NT), C::LDS_BYTES, st, R, k, *net, cvec, tvec, x,
+                                                     sigma_dev, mode, out);
     }
-    if (P == 64)
-        hipLaunchKernelGGL(score_eval_kernel<64>, dim3((R + 63) / 64), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, R, k, *net, cvec, tvec, x, sigma_dev,
-                           mode, out);
-    else if (P == 16)
-        hipLaunchKernelGGL(score_eval_kernel<16>, dim3((R + 15) / 16), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, R, k, *net, cvec, tvec, x, sigma_dev,
-                           mode, out);
-    else
-        hipLaunchKernelGGL(score_eval_kernel<32>, dim3((R + 31) / 32), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, R, k, *net, cvec, tvec, x, sigma_dev,
-                           mode, out);
-    return gp_launch_status();
+    if (P != 16 && P != 32 && P != 64) return GP_EINVAL;
+    if (gp_prepare_lds<score_eval_kernel<16>>(trunk_lds_bytes<16>()) || gp_prepare_lds<score_eval_kernel<32>>(trunk_lds_bytes<32>()) ||
+        gp_prepare_lds<score_eval_kernel<64>>(trunk_lds_bytes<64>()))
+        return GP_ELAUNCH;
+    return gp_with_tile(P, [&](auto tile) {
+        constexpr int T = decltype(tile)::value;
+        return gp_launch<score_eval_kernel<T>>(dim3((R + T - 1) / T), dim3(TrunkCfg<T>::NT), trunk_lds_bytes<T>(), st, R, k, *net, cvec, tvec, x, sigma_dev,
+                                               mode, out);
+    });
 }
 
 int gp_score_eval(int nclouds, int k, const gp_scorenet *net, const float *cvec, const float *tvec, const float *x, const float *sigma_dev, int mode,
@@ -652,10 +667,6 @@ int gp_pc_tile_rows(int ngroups, int nclouds_per_group, int k) {
     if (ngroups > 1 && rg % P != 0) return GP_EINVAL;
     return P;
 }
-
-// rows per partial sum of |score| for a plan
-static int pc_rows_per_partial(int P) { return P <= 64 ? P : P / gp_chain::NW; }  // tile form: per workgroup; chain form: per wave
-static int pc_rows_per_wg(int P) { return P; }
 
 int gp_pc_layout(int model, int tile, int ngroups, int nclouds_per_group, int k, int *tile_out, int *nparts_out) {
     if ((model != 0 && model != 1) || ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || !tile_out || !nparts_out) return GP_EINVAL;
@@ -687,43 +698,8 @@ int gp_pc_step_plan(int model, int tile, int ngroups, int nclouds_per_group, int
     if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || step < 0 || step > nsteps || !net || !cvec || !tvec_all || !sched || !z_langevin ||
         !z_predictor || !centre || !x || !mean_x || !score || !partials || gn_rows_total < 0)
         return GP_EINVAL;
-    const int rg = nclouds_per_group * k, R = ngroups * rg;
-    if (R == 0) return GP_OK;
-    int P = 0, nparts = 0;
-    const int rc = gp_pc_layout(model, tile, ngroups, nclouds_per_group, k, &P, &nparts);
-    if (rc != GP_OK) return rc;
-    if (model == 1 && (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t)) return GP_EINVAL;
-    const bool split = P == (16 | GP_PLAN_HEADSPLIT);
-    if (split) {
-        if (gn_ext) return GP_EINVAL;  // a sharded batch's callers sum whole-tile partials between the launches: tile plans only
-        P = 16;
-    }
-    const int wgpg = (rg + pc_rows_per_wg(P) - 1) / pc_rows_per_wg(P);
-    const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, wgpg, cvec, tvec_all, sched, z_langevin, z_predictor, centre, x, mean_x, score, partials,
-                             traj, gn_ext, gn_rows_total);
-    hipStream_t st = (hipStream_t)s;
-    const int nwg = a.wgpg * ngroups;
-    if (P == 128) return model == 1 ? launch_pc_chain<2, 1>(a, net, nwg, st) : launch_pc_chain<2, 0>(a, net, nwg, st);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(pc_step_kernel<16, 0>, trunk_lds_bytes<16>()) || set_lds(pc_step_kernel<16, 0, true>, trunk_lds_bytes<16>()) ||
-            set_lds(pc_step_kernel<32, 0>, trunk_lds_bytes<32>()) ||
-            set_lds(pc_step_kernel<64, 0>, trunk_lds_bytes<64>()) ||
-            set_lds(pc_step_kernel<16, 1>, gp_bwd::LDS_BYTES))
-            return GP_ELAUNCH;
-        attr_done = true;
-    }
-    if (model == 1)
-        hipLaunchKernelGGL((pc_step_kernel<16, 1>), dim3(nwg), dim3(TrunkCfg<16>::NT), gp_bwd::LDS_BYTES, st, a, *net);
-    else if (split)
-        hipLaunchKernelGGL((pc_step_kernel<16, 0, true>), dim3(3 * nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
-    else if (P == 16)
-        hipLaunchKernelGGL((pc_step_kernel<16, 0>), dim3(nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
-    else if (P == 64)
-        hipLaunchKernelGGL((pc_step_kernel<64, 0>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
-    else
-        hipLaunchKernelGGL((pc_step_kernel<32, 0>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
-    return gp_launch_status();
+    return pc_step_launch<false>(model, tile, ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched, z_langevin, z_predictor, centre, x, mean_x,
+                                score, partials, traj, gn_ext, gn_rows_total, (hipStream_t)s);
 }
 
 int gp_pc_step_plan_seeded(int tile, int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
@@ -732,39 +708,9 @@ int gp_pc_step_plan_seeded(int tile, int ngroups, int nclouds_per_group, int k, 
     if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || step < 0 || step > nsteps || (uint32_t)nsteps >= gp_philox::MAX_STEPS || !net || !cvec ||
         !tvec_all || !sched || !seed_state || !centre || !x || !mean_x || !score || !partials || gn_rows_total < 0)
         return GP_EINVAL;
-    const int rg = nclouds_per_group * k, R = ngroups * rg;
-    if (R == 0) return GP_OK;
-    int P = 0, nparts = 0;
-    const int rc = gp_pc_layout(0, tile, ngroups, nclouds_per_group, k, &P, &nparts);
-    if (rc != GP_OK) return rc;
-    const bool split = P == (16 | GP_PLAN_HEADSPLIT);
-    if (split) {
-        if (gn_ext) return GP_EINVAL;  // as gp_pc_step_plan
-        P = 16;
-    }
-    const int wgpg = (rg + pc_rows_per_wg(P) - 1) / pc_rows_per_wg(P);
     // (the seed state travels in the argument block's z_lang slot: PcArgs)
-    const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, wgpg, cvec, tvec_all, sched, reinterpret_cast<const float *>(seed_state), nullptr, centre, x,
-                             mean_x, score, partials, traj, gn_ext, gn_rows_total);
-    hipStream_t st = (hipStream_t)s;
-    const int nwg = a.wgpg * ngroups;
-    if (P == 128) return launch_pc_chain_seeded<2>(a, net, nwg, st);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(pc_step_seeded_kernel<16>, trunk_lds_bytes<16>()) || set_lds(pc_step_seeded_kernel<16, true>, trunk_lds_bytes<16>()) ||
-            set_lds(pc_step_seeded_kernel<32>, trunk_lds_bytes<32>()) || set_lds(pc_step_seeded_kernel<64>, trunk_lds_bytes<64>()))
-            return GP_ELAUNCH;
-        attr_done = true;
-    }
-    if (split)
-        hipLaunchKernelGGL((pc_step_seeded_kernel<16, true>), dim3(3 * nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
-    else if (P == 16)
-        hipLaunchKernelGGL((pc_step_seeded_kernel<16>), dim3(nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
-    else if (P == 64)
-        hipLaunchKernelGGL((pc_step_seeded_kernel<64>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
-    else
-        hipLaunchKernelGGL((pc_step_seeded_kernel<32>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
-    return gp_launch_status();
+    return pc_step_launch<true>(0, tile, ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched, reinterpret_cast<const float *>(seed_state),
+                               nullptr, centre, x, mean_x, score, partials, traj, gn_ext, gn_rows_total, (hipStream_t)s);
 }
 
 int gp_heun_launches(int nsteps, int denoise) { return nsteps < 1 ? GP_EINVAL : 2 * nsteps + 1 + (denoise ? 1 : 0); }
@@ -787,32 +733,8 @@ int gp_heun_layout(int tile, int ngroups, int nclouds_per_group, int k, int *til
 int gp_heun_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                       const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                       gp_stream_t s) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_heun_launches(nsteps, denoise) || !net || !cvec ||
-        !tvec_all || !sched || !centre || !x || !d || !score || !out)
-        return GP_EINVAL;
-    const int rg = nclouds_per_group * k, R = ngroups * rg;
-    if (R == 0) return GP_OK;
-    int P = 0;
-    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
-    if (rc != GP_OK) return rc;
-    const HeunArgs a = heun_args(R, k, launch, gp_heun_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
-    hipStream_t st = (hipStream_t)s;
-    const int nwg = ngroups * ((rg + P - 1) / P);
-    if (P == 128) return launch_heun_chain<2>(a, net, nwg, st);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(heun_step_kernel<16>, trunk_lds_bytes<16>()) || set_lds(heun_step_kernel<32>, trunk_lds_bytes<32>()) ||
-            set_lds(heun_step_kernel<64>, trunk_lds_bytes<64>()))
-            return GP_ELAUNCH;
-        attr_done = true;
-    }
-    if (P == 16)
-        hipLaunchKernelGGL((heun_step_kernel<16>), dim3(nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
-    else if (P == 64)
-        hipLaunchKernelGGL((heun_step_kernel<64>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
-    else
-        hipLaunchKernelGGL((heun_step_kernel<32>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
-    return gp_launch_status();
+    return fixed_step_plan<SOLVER_HEUN>(tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                        (hipStream_t)s);
 }
 
 int gp_dpm2m_launches(int nsteps, int denoise) { return nsteps < 1 ? GP_EINVAL : nsteps + 1 + (denoise ? 1 : 0); }
@@ -820,32 +742,8 @@ int gp_dpm2m_launches(int nsteps, int denoise) { return nsteps < 1 ? GP_EINVAL :
 int gp_dpm2m_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                        const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                        gp_stream_t s) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_dpm2m_launches(nsteps, denoise) || !net || !cvec ||
-        !tvec_all || !sched || !centre || !x || !d || !score || !out)
-        return GP_EINVAL;
-    const int rg = nclouds_per_group * k, R = ngroups * rg;
-    if (R == 0) return GP_OK;
-    int P = 0;
-    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
-    if (rc != GP_OK) return rc;
-    const HeunArgs a = heun_args(R, k, launch, gp_dpm2m_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
-    hipStream_t st = (hipStream_t)s;
-    const int nwg = ngroups * ((rg + P - 1) / P);
-    if (P == 128) return launch_dpm2m_chain<2>(a, net, nwg, st);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(dpm2m_step_kernel<16>, trunk_lds_bytes<16>()) || set_lds(dpm2m_step_kernel<32>, trunk_lds_bytes<32>()) ||
-            set_lds(dpm2m_step_kernel<64>, trunk_lds_bytes<64>()))
-            return GP_ELAUNCH;
-        attr_done = true;
-    }
-    if (P == 16)
-        hipLaunchKernelGGL((dpm2m_step_kernel<16>), dim3(nwg), dim3(TrunkCfg<16>::NT), trunk_lds_bytes<16>(), st, a, *net);
-    else if (P == 64)
-        hipLaunchKernelGGL((dpm2m_step_kernel<64>), dim3(nwg), dim3(TrunkCfg<64>::NT), trunk_lds_bytes<64>(), st, a, *net);
-    else
-        hipLaunchKernelGGL((dpm2m_step_kernel<32>), dim3(nwg), dim3(TrunkCfg<32>::NT), trunk_lds_bytes<32>(), st, a, *net);
-    return gp_launch_status();
+    return fixed_step_plan<SOLVER_DPM2M>(tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                         (hipStream_t)s);
 }
 
 int gp_pc_step_coupled(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,

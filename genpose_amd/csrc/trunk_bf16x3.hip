@@ -161,13 +161,7 @@ int gp_pc_step_bf16x3(int ngroups, int nclouds_per_group, int k, int step, int n
                              mean_x, score, partials, traj, nullptr, 0);
     const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_split), reinterpret_cast<const bf16x8 *>(w_pose2_split),
                         reinterpret_cast<const bf16x8 *>(w_headx_split), b_pose0, b_pose2, w_out, b_out};
-    static bool done = false;
-    if (!done) {
-        if (set_lds(pc_step_bf16x3_kernel, BfLds::BYTES)) return GP_ELAUNCH;
-        done = true;
-    }
-    hipLaunchKernelGGL(pc_step_bf16x3_kernel, dim3(a.wgpg * ngroups), dim3(BF_NT), BfLds::BYTES, (hipStream_t)s, a, w);
-    return gp_launch_status();
+    return gp_launch<pc_step_bf16x3_kernel>(dim3(a.wgpg * ngroups), dim3(BF_NT), BfLds::BYTES, (hipStream_t)s, a, w);
 }
 
 }  // extern "C"

@@ -85,13 +85,12 @@ inline bool staged_aligned(const gp_scorenet *net, const float *cvec, const floa
     return aligned16(net->b_pose0) && aligned16(net->b_pose2) && aligned16(net->w_out) && aligned16(cvec) && aligned16(tvec_all);
 }
 
-// What the two entry points share: the chain plan's rules, PcArgs / SplitNet, the once-per-kernel LDS attribute and the launch.
+// What the two PC entry points share: the chain plan's rules, PcArgs / SplitNet and the launch.
 // z_lang carries the Langevin noise or, for the seeded kernel, the seed state (PcArgs).
-template <class K>
-int launch_pc_bf16x9(K kern, bool &attr_done, int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
-                     const float *tvec_all, const float *sched, const float *z_lang, const float *z_pred, const float *centre, float *x, float *mean_x,
-                     float *score, float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
-                     const void *w_headx_x9, gp_stream_t s) {
+template <auto Kern>
+int launch_pc_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec, const float *tvec_all,
+                     const float *sched, const float *z_lang, const float *z_pred, const float *centre, float *x, float *mean_x, float *score, float *partials,
+                     float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
     if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || step < 0 || step > nsteps || !net || !cvec || !tvec_all || !sched || !z_lang || !centre || !x ||
         !mean_x || !score || !partials || gn_rows_total < 0 || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9 || !staged_aligned(net, cvec, tvec_all))
         return GP_EINVAL;
@@ -103,14 +102,26 @@ int launch_pc_bf16x9(K kern, bool &attr_done, int ngroups, int nclouds_per_group
     if (P != X9_ROWS || !gp_chain::Cfg<2>::fits(k)) return GP_EINVAL;
     const PcArgs a = pc_args(ngroups, rg, k, step, nsteps, nparts, (rg + X9_ROWS - 1) / X9_ROWS, cvec, tvec_all, sched, z_lang, z_pred, centre, x, mean_x, score,
                              partials, traj, gn_ext, gn_rows_total);
-    const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
-                        reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
-    if (!attr_done) {
-        if (set_lds(kern, X9Lds::BYTES)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.wgpg * ngroups), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
-    return gp_launch_status();
+    return gp_launch<Kern>(dim3(a.wgpg * ngroups), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, split_net(net, w_pose0_x9, w_pose2_x9, w_headx_x9));
+}
+
+// A launch of a fixed-step solver (gp_heun_step_bf16x9, gp_dpm2m_step_bf16x9).
+template <int SOLVER>
+int fixed_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+                      const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
+                      const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
+    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= fixed_launches<SOLVER>(nsteps, denoise) || !net || !cvec ||
+        !tvec_all || !sched || !centre || !x || !d || !score || !out || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9 || !staged_aligned(net, cvec, tvec_all))
+        return GP_EINVAL;
+    const int rg = nclouds_per_group * k;
+    if (ngroups * rg == 0) return GP_OK;
+    int P = 0;
+    const int rc = gp_heun_layout(X9_ROWS, ngroups, nclouds_per_group, k, &P);  // the chain plan's rules
+    if (rc != GP_OK) return rc;
+    const HeunArgs a = heun_args(ngroups * rg, k, launch, fixed_launches<SOLVER>(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    constexpr auto kern = SOLVER == SOLVER_DPM2M ? dpm2m_step_chain_kernel_bf16x9 : heun_step_chain_kernel_bf16x9;
+    return gp_launch<kern>(dim3(ngroups * ((rg + X9_ROWS - 1) / X9_ROWS)), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a,
+                           split_net(net, w_pose0_x9, w_pose2_x9, w_headx_x9));
 }
 
 }  // namespace
@@ -121,67 +132,33 @@ int gp_pc_step_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int n
                       const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score,
                       float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
                       const void *w_headx_x9, gp_stream_t s) {
-    static bool done = false;
     if (!z_predictor) return GP_EINVAL;
-    return launch_pc_bf16x9(pc_step_chain_kernel_bf16x9, done, ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched, z_langevin, z_predictor,
-                            centre, x, mean_x, score, partials, traj, gn_ext, gn_rows_total, w_pose0_x9, w_pose2_x9, w_headx_x9, s);
+    return launch_pc_bf16x9<pc_step_chain_kernel_bf16x9>(ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched, z_langevin, z_predictor, centre, x,
+                                                         mean_x, score, partials, traj, gn_ext, gn_rows_total, w_pose0_x9, w_pose2_x9, w_headx_x9, s);
 }
 
 int gp_pc_step_bf16x9_seeded(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
                              const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
                              float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
                              const void *w_headx_x9, gp_stream_t s) {
-    static bool done = false;
     if ((uint32_t)nsteps >= gp_philox::MAX_STEPS) return GP_EINVAL;
-    return launch_pc_bf16x9(pc_step_chain_seeded_kernel_bf16x9, done, ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched,
-                            reinterpret_cast<const float *>(seed_state), nullptr, centre, x, mean_x, score, partials, traj, gn_ext, gn_rows_total, w_pose0_x9,
-                            w_pose2_x9, w_headx_x9, s);
+    return launch_pc_bf16x9<pc_step_chain_seeded_kernel_bf16x9>(ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched,
+                                                                reinterpret_cast<const float *>(seed_state), nullptr, centre, x, mean_x, score, partials, traj,
+                                                                gn_ext, gn_rows_total, w_pose0_x9, w_pose2_x9, w_headx_x9, s);
 }
 
 int gp_heun_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                         const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                         const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_heun_launches(nsteps, denoise) || !net || !cvec ||
-        !tvec_all || !sched || !centre || !x || !d || !score || !out || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9 || !staged_aligned(net, cvec, tvec_all))
-        return GP_EINVAL;
-    const int rg = nclouds_per_group * k;
-    if (ngroups * rg == 0) return GP_OK;
-    int P = 0;
-    const int rc = gp_heun_layout(X9_ROWS, ngroups, nclouds_per_group, k, &P);  // the chain plan's rules
-    if (rc != GP_OK) return rc;
-    const HeunArgs a = heun_args(ngroups * rg, k, launch, gp_heun_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
-    const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
-                        reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(heun_step_chain_kernel_bf16x9, X9Lds::BYTES)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(heun_step_chain_kernel_bf16x9, dim3(ngroups * ((rg + X9_ROWS - 1) / X9_ROWS)), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
-    return gp_launch_status();
+    return fixed_step_bf16x9<SOLVER_HEUN>(ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                          w_pose0_x9, w_pose2_x9, w_headx_x9, s);
 }
 
 int gp_dpm2m_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                          const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                          const void *w_pose0_x9, const void *w_pose2_x9, const void *w_headx_x9, gp_stream_t s) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= gp_dpm2m_launches(nsteps, denoise) || !net || !cvec ||
-        !tvec_all || !sched || !centre || !x || !d || !score || !out || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9 || !staged_aligned(net, cvec, tvec_all))
-        return GP_EINVAL;
-    const int rg = nclouds_per_group * k;
-    if (ngroups * rg == 0) return GP_OK;
-    int P = 0;
-    const int rc = gp_heun_layout(X9_ROWS, ngroups, nclouds_per_group, k, &P);  // the chain plan's rules
-    if (rc != GP_OK) return rc;
-    const HeunArgs a = heun_args(ngroups * rg, k, launch, gp_dpm2m_launches(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
-    const SplitNet w = {reinterpret_cast<const bf16x8 *>(w_pose0_x9), reinterpret_cast<const bf16x8 *>(w_pose2_x9),
-                        reinterpret_cast<const bf16x8 *>(w_headx_x9), net->b_pose0, net->b_pose2, net->w_out, net->b_out};
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (set_lds(dpm2m_step_chain_kernel_bf16x9, X9Lds::BYTES)) return GP_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(dpm2m_step_chain_kernel_bf16x9, dim3(ngroups * ((rg + X9_ROWS - 1) / X9_ROWS)), dim3(X9_NT), X9Lds::BYTES, (hipStream_t)s, a, w);
-    return gp_launch_status();
+    return fixed_step_bf16x9<SOLVER_DPM2M>(ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                           w_pose0_x9, w_pose2_x9, w_headx_x9, s);
 }
 
 }  // extern "C"

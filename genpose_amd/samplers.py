@@ -137,6 +137,7 @@ class PCSampler:
             use_graph = use_graph and dist.get_backend(coupling_group) == "nccl"  # an RCCL all-reduce is graph-capturable, a gloo one is not
         self.use_graph = use_graph
         self.graph = None
+        self.captures = 0
         if self.seed is not None:
             # a shard of a batch draws the rows it holds of the unsharded batch
             rank = self._dist.get_rank(coupling_group) if coupling_group is not None else 0
@@ -226,22 +227,60 @@ class PCSampler:
         if not self.use_graph:
             self._launch_all()
         else:
-            if self.graph is None:
-                # warm-up launch outside capture (sets kernel attributes), then capture the whole T-step loop once
-                x0 = self.x.clone()
-                self._launch_all()
-                torch.cuda.synchronize()
-                self.x.copy_(x0)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self._launch_all()
-            if graph_events is not None:
-                graph_events[0].record(torch.cuda.current_stream())
-            self.graph.replay()
-            if graph_events is not None:
-                graph_events[1].record(torch.cuda.current_stream())
+            _replay_captured(self, self.x.clone() if self.graph is None else None, graph_events)
         xs = self.traj.permute(1, 0, 2) if self.traj is not None else None
         return xs, self.mean_x
+
+
+def _replay_captured(smp, restore, graph_events=None):
+    """The graph path of a sampler's run().  First run: a warm-up chain outside capture (it sets the kernels' attributes), smp.x put back
+    from `restore`, the whole chain captured once.  Every run: the replay, between graph_events' two events where given."""
+    if smp.graph is None:
+        smp._launch_all()
+        torch.cuda.synchronize()
+        smp.x.copy_(restore)
+        smp.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(smp.graph):
+            smp._launch_all()
+        smp.captures += 1
+    if graph_events is not None:
+        graph_events[0].record(torch.cuda.current_stream())
+    smp.graph.replay()
+    if graph_events is not None:
+        graph_events[1].record(torch.cuda.current_stream())
+
+
+class _ScheduleTable:
+    """A fixed-step solver's run-time schedule: [launches][row] floats + the N + 1 times, one pinned block -> one device block (sched,
+    t_dev) -> the time-embedding table (tvec_all), refilled in stream order when the key changes."""
+
+    def __init__(self, net, nlaunch, row, ntimes, device):
+        self.net, self.dev = net, device
+        self._sched_len = nlaunch * row
+        self._table = torch.zeros(self._sched_len + ntimes, device=device)
+        self._host = torch.zeros(self._sched_len + ntimes).pin_memory()
+        self._ev = None
+        self._key = None
+        self.sched = self._table[: self._sched_len]
+        self.t_dev = self._table[self._sched_len:]
+        self.tvec_all = torch.empty(ntimes, 768, device=device)
+
+    def write(self, key, schedule):
+        """schedule() -> (times [N + 1], sched [launches][row]); called only when `key` is not the one the buffers hold."""
+        if key == self._key:
+            return
+        t, sched = schedule()
+        if self._ev is not None:
+            self._ev.synchronize()  # the previous copy out of the pinned block has completed
+        else:
+            self._ev = torch.cuda.Event()
+        h = self._host.numpy()
+        h[: self._sched_len] = sched.reshape(-1)
+        h[self._sched_len:] = t.astype(np.float32)
+        self._table.copy_(self._host, non_blocking=True)
+        self._ev.record(torch.cuda.current_stream(self.dev))
+        self.net.time_embed(self.t_dev, out=self.tvec_all)
+        self._key = key
 
 
 def pc_noise_fill(seed, run_index, num_steps, nrows, device, row_base=0, step0=0, row0=0):
@@ -419,35 +458,15 @@ class HeunSampler:
         self.x, self.d, self.score, self.out = f(R, 9), f(R, 9), f(R, 9), f(R, 9)
         self.cvec, self.centre = f(B, 768), f(B, 3)
         self.traj = f(self.n, R, 9) if record_traj else None
-        # run-time schedule: [launches][SCHED_ROW] + the N + 1 times, one pinned block -> one device block -> the time-embedding table
-        self._sched_len = self.nlaunch * self.SCHED_ROW
-        self._table = torch.zeros(self._sched_len + self.n + 1, device=self.dev)
-        self._table_host = torch.zeros(self._sched_len + self.n + 1).pin_memory()
-        self._table_ev = None
-        self._table_key = None
-        self.sched = self._table[: self._sched_len]
-        self.t_dev = self._table[self._sched_len:]
-        self.tvec_all = f(self.n + 1, 768)
+        self._table = _ScheduleTable(net, self.nlaunch, self.SCHED_ROW, self.n + 1, self.dev)
+        self.sched, self.t_dev, self.tvec_all = self._table.sched, self._table.t_dev, self._table.tvec_all
         self.use_graph = use_graph
         self.graph = None
         self.captures = 0
         self.last_stats = {}
 
     def _write_schedule(self, T0, eps):
-        key = (float(T0), float(eps))
-        if key != self._table_key:
-            t, sched = self._schedule(T0, eps)
-            if self._table_ev is not None:
-                self._table_ev.synchronize()  # the previous copy out of the pinned block has completed
-            else:
-                self._table_ev = torch.cuda.Event()
-            h = self._table_host.numpy()
-            h[: self._sched_len] = sched.reshape(-1)
-            h[self._sched_len:] = t.astype(np.float32)
-            self._table.copy_(self._table_host, non_blocking=True)
-            self._table_ev.record(torch.cuda.current_stream(self.dev))
-            self.net.time_embed(self.t_dev, out=self.tvec_all)
-            self._table_key = key
+        self._table.write((float(T0), float(eps)), lambda: self._schedule(T0, eps))
 
     def launch_step(self, l):
         """Launch l of the chain (0 <= l < nlaunch) on the current stream."""
@@ -480,16 +499,7 @@ class HeunSampler:
         if not self.use_graph:
             self._launch_all()
         else:
-            if self.graph is None:
-                # warm-up launch outside capture (sets kernel attributes), then capture the chain once
-                self._launch_all()
-                torch.cuda.synchronize()
-                self.x.copy_(x0)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self._launch_all()
-                self.captures += 1
-            self.graph.replay()
+            _replay_captured(self, x0)
         self.last_stats = {"nfev": self.nlaunch - 1, "plan": self.plan, "launches": self.nlaunch, "kernel": self.kernel_name,
                            "nlaunch": self.nlaunch, "kernel_name": self.kernel_name}
         if self.launches == "single":
@@ -611,35 +621,15 @@ class HeunLikelihood:
         self.x, self.d, self.score, self.div, self.z = f(R, 9), f(R, 10), f(R, 9), f(R), f(R, 9)
         self.logp = torch.zeros(R, dtype=torch.float64, device=self.dev)
         self.cvec = f(B, 768)
-        # run-time schedule: [launches][4] + the N + 1 times, one pinned block -> one device block -> the time-embedding table
-        self._sched_len = self.nlaunch * 4
-        self._table = torch.zeros(self._sched_len + self.n + 1, device=self.dev)
-        self._table_host = torch.zeros(self._sched_len + self.n + 1).pin_memory()
-        self._table_ev = None
-        self._table_key = None
-        self.sched = self._table[: self._sched_len]
-        self.t_dev = self._table[self._sched_len:]
-        self.tvec_all = f(self.n + 1, 768)
+        self._table = _ScheduleTable(net, self.nlaunch, 4, self.n + 1, self.dev)
+        self.sched, self.t_dev, self.tvec_all = self._table.sched, self._table.t_dev, self._table.tvec_all
         self.use_graph = use_graph
         self.graph = None
         self.captures = 0
         self.last_stats = {}
 
     def _write_schedule(self, eps, T):
-        key = (float(eps), float(T))
-        if key != self._table_key:
-            t, sched = heun_likelihood_schedule(self.n, eps, T, self.grid, self.rho)
-            if self._table_ev is not None:
-                self._table_ev.synchronize()  # the previous copy out of the pinned block has completed
-            else:
-                self._table_ev = torch.cuda.Event()
-            h = self._table_host.numpy()
-            h[: self._sched_len] = sched.reshape(-1)
-            h[self._sched_len:] = t.astype(np.float32)
-            self._table.copy_(self._table_host, non_blocking=True)
-            self._table_ev.record(torch.cuda.current_stream(self.dev))
-            self.net.time_embed(self.t_dev, out=self.tvec_all)
-            self._table_key = key
+        self._table.write((float(eps), float(T)), lambda: heun_likelihood_schedule(self.n, eps, T, self.grid, self.rho))
 
     def launch_step(self, l):
         """Launch l of the chain (0 <= l < nlaunch) on the current stream."""
@@ -661,16 +651,7 @@ class HeunLikelihood:
         if not self.use_graph:
             self._launch_all()
         else:
-            if self.graph is None:
-                # warm-up launch outside capture (sets kernel attributes), then capture the chain once
-                self._launch_all()
-                torch.cuda.synchronize()
-                self.x.copy_(x)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self._launch_all()
-                self.captures += 1
-            self.graph.replay()
+            _replay_captured(self, x)
         self.last_stats = {"nfev": self.nlaunch - 1, "launches": self.nlaunch, "kernel": self.kernel_name, "n_attempts": self.n}
         return self.z, self.logp
 
