@@ -95,6 +95,11 @@ SIGNATURES = {
     "gp_dpm2m_step_plan": [c_int] * 7 + [NETP] + [P] * 9 + [P],
     "gp_dpm2m_step_bf16x9": [c_int] * 6 + [NETP] + [P] * 9 + [P] * 3 + [P],
     "gp_dpm2m_solve_tile": [c_int] * 6 + [NETP] + [P] * 9 + [P],
+    "gp_heun_layout_model": [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "gp_heun_step_plan_model": [c_int] * 8 + [NETP] + [P] * 9 + [P],
+    "gp_dpm2m_step_plan_model": [c_int] * 8 + [NETP] + [P] * 9 + [P],
+    "gp_heun_solve_tile_model": [c_int] * 7 + [NETP] + [P] * 9 + [P],
+    "gp_dpm2m_solve_tile_model": [c_int] * 7 + [NETP] + [P] * 9 + [P],
     "gp_heun_likelihood_launches": [c_int],
     "gp_heun_likelihood_step": [c_int] * 4 + [NETP] + [P] * 9 + [P],
     "gp_pc_step_grouped": [c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 11 + [P],

@@ -33,6 +33,7 @@ DEFAULTS = dict(
     likelihood_steps=None,  # (ours) N of likelihood_solver 'heun' (NFE = 2 N)
     likelihood_grid="geometric",  # (ours) sigma grid of likelihood_solver 'heun': 'geometric' or 'edm' (heun_grid's two)
     heun_grid="geometric",  # (ours) sampler_mode ['heun'] (the fixed-step Heun solver of the probability-flow ODE, samplers.HeunSampler; sampling_steps = its N) and ['dpm2m'] (the DPM-Solver++(2M) solver on the same grid, samplers.Dpm2mSampler: one evaluation per step): the sigma grid - 'geometric' (t uniform) or 'edm' (cond_edm_sampler's rho = 7 discretisation)
+    fixed_step_energy=False,  # (ours) True: opt-in - sampler_mode ['heun'] / ['dpm2m'] serve a posenet_mode='energy' agent too: the fixed-step solvers driven by the energy model's score, the gradient of its inner-product energy evaluated inside the kernels (samplers.HeunSampler / Dpm2mSampler(model='energy')); False: such an agent refuses both samplers, as before
     ode_trunk=None,  # (ours) 'bf16x9': opt-in exact-product split-bf16 trunk in the ODE sampler's chain-plan stage kernels (ODESampler(trunk=)); None / 'f32mfma': the fp32 MFMA kernels
     encoder_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products on the 128-196-256 grouping level (csrc/sa_bf16x3.hip)
     encoder_level2="auto",  # (ours) under encoder_precision 'f32', the arithmetic of grouping level 2 (128-196-256): 'bf16x9' = exact-product split bf16 on the BF16 matrix pipe (csrc/sa_bf16x9.hip, the fp32 kernels' error class), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the adaptive ODE sampler (its goldens pin RK45 attempt counts that move with the last bits of the features); encoder_precision='bf16x9' forces it

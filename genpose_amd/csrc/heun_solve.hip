@@ -10,7 +10,14 @@
 // beyond the workgroup barriers below.  d and score are not written.
 // SOLVER_DPM2M (dpm2m_solve_kernel, gp_dpm2m_solve_tile): the same loop over the launch indices of the DPM-Solver++(2M) chain (pc_rows.h;
 // dpm2m_step_kernel) - its schedule rows, dpm2m_update_row, the time row of the index itself; the slot of d_i holds D_{i-1}.
+// MODEL 1 (heun_solve_kernel<16, energy>, dpm2m_solve_kernel<16, energy>; gp_*_solve_tile_model): the ENERGY network's score drives the
+// solve (energynet.py:200-222) - score_vjp_tile<ENERGY> (score_bwd.h) in trunk_ftheta's place, as heun_step_tile<16, SOLVER, 1> has it.  The
+// row thread's slot sits behind the backward pass's block (gp_bwd::LDS_FLOATS); the previous score is read from the pass's output rows
+// (gp_bwd::OFF_U, stride LDS_OUT: behind the trunk's block and G3, so apart from X0) as it is - the chain stores these words undivided -
+// before the row thread writes its X0 row, and the barrier below orders that read before score_vjp_tile's seed loop rewrites the block.
+// Measured (profiles/fixed_step_energy.txt): the chain's bits, and 0.92 - 0.94x the chain's speed - for this model the chain is the faster form.
 #include "pc_rows.h"
+#include "score_bwd.h"
 
 namespace {
 
@@ -21,15 +28,16 @@ using namespace gp_trunk;
 // whole trunk (256 VGPRs and up to 118 spilled registers per lane, against the per-launch kernels' 128 - 184 and none).
 __device__ __forceinline__ void opaque(const float *&p) { asm volatile("" : "+s"(p)); }
 
-template <int P, int SOLVER>
+template <int P, int SOLVER, int MODEL = 0>
 __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) {
-    using L = TrunkLds<P>;
+    static_assert(MODEL == 0 || P == gp_bwd::DP, "the backward pass runs on 16-row tiles");
+    using L = TrunkLds<P, MODEL == 1>;
     constexpr int SROW = fixed_sched_row<SOLVER>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int row0 = blockIdx.x * P, tid = threadIdx.x, last = a.nsteps;
     const bool live = row0 + tid < a.nrows;
     const int r = live ? row0 + tid : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
-    float *mine = lds + L::TOTAL + tid;  // this row thread's slot: x_i at [j * P], d_i at [(9 + j) * P], the cloud centre at [(18 + j) * P]
+    float *mine = lds + (MODEL == 1 ? gp_bwd::LDS_FLOATS : L::TOTAL) + tid;  // this row thread's slot: x_i at [j * P], d_i at [(9 + j) * P], the cloud centre at [(18 + j) * P]
     if (tid < P) {
 #pragma unroll
         for (int j = 0; j < 9; ++j) mine[j * P] = a.x[(size_t)r * 9 + j];
@@ -42,6 +50,7 @@ __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) 
         const float *tvec = a.tvec_all + (size_t)pc_time_row<SOLVER>(l) * HEADS;
         gp_scorenet net = net0;
         opaque(net.w_pose0), opaque(net.b_pose0), opaque(net.w_pose2), opaque(net.b_pose2), opaque(net.w_headx), opaque(net.w_out), opaque(net.b_out);
+        if constexpr (MODEL == 1) opaque(net.w_headx_t), opaque(net.w_pose2_t), opaque(net.w_pose0_t);
         opaque(a.cvec);
         TrunkPre<P> pre;
         float sigma = 1.f;
@@ -59,13 +68,14 @@ __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) 
                 const int kind = (int)sc[3];
                 const float c = sc[1], h = sc[2];
                 // the previous index's f_theta (all of trunk_ftheta's barriers are behind us); the chain stores this quotient and reloads it
-                const float *F = lds + L::OFF_H1 + tid * L::LDH;
+                // (MODEL 1: the previous index's score itself, in the backward pass's output rows)
+                const float *F = MODEL == 1 ? lds + gp_bwd::OFF_U + tid * gp_bwd::LDS_OUT : lds + L::OFF_H1 + tid * L::LDH;
                 float gr[9], dv[9];
                 if constexpr (SOLVER == SOLVER_DPM2M) {
                     const bool has_d = (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) && sc[5] != 0.f;
 #pragma unroll
                     for (int j = 0; j < 9; ++j) {
-                        gr[j] = F[j] / (sigma_prev + 1e-7f);
+                        gr[j] = MODEL == 1 ? F[j] : F[j] / (sigma_prev + 1e-7f);
                         dv[j] = has_d ? mine[(9 + j) * P] : 0.f;
                     }
                     dpm2m_update_row(kind, ev, dv, gr, c, h, sc[4], sc[5]);
@@ -76,7 +86,7 @@ __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) 
                 } else {
 #pragma unroll
                     for (int j = 0; j < 9; ++j) {
-                        gr[j] = F[j] / (sigma_prev + 1e-7f);
+                        gr[j] = MODEL == 1 ? F[j] : F[j] / (sigma_prev + 1e-7f);
                         dv[j] = kind == HEUN_CORRECT || kind == HEUN_CORRECT_LAST ? mine[(9 + j) * P] : 0.f;
                     }
                     heun_update_row(kind, ev, dv, gr, c, h);
@@ -106,18 +116,21 @@ __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) 
         }
         if (l == last) break;
         __syncthreads();  // X0 is complete, and the row threads have read the previous f_theta out of H1, before layer 1 overwrites it
-        trunk_ftheta<P>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre);  // (ends on a barrier: f_theta is visible to the row threads)
+        if constexpr (MODEL == 1)
+            gp_bwd::score_vjp_tile<gp_bwd::ENERGY>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre, sigma);  // (ends on a barrier too)
+        else
+            trunk_ftheta<P>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre);  // (ends on a barrier: f_theta is visible to the row threads)
         sigma_prev = sigma;
     }
 }
 
-template <int P>
+template <int P, int MODEL = 0>
 __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_kernel(HeunArgs a, const gp_scorenet net0) {
-    heun_solve<P, SOLVER_HEUN>(a, net0);
+    heun_solve<P, SOLVER_HEUN, MODEL>(a, net0);
 }
-template <int P>
+template <int P, int MODEL = 0>
 __global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_solve_kernel(HeunArgs a, const gp_scorenet net0) {
-    heun_solve<P, SOLVER_DPM2M>(a, net0);
+    heun_solve<P, SOLVER_DPM2M, MODEL>(a, net0);
 }
 
 // the trunk's block and 21 floats per row behind it
@@ -126,24 +139,30 @@ constexpr size_t solve_lds_bytes() {
     return trunk_lds_bytes<P>() + (size_t)21 * P * sizeof(float);
 }
 
-template <int SOLVER, int P>
-constexpr auto solve_kernel = heun_solve_kernel<P>;
-template <int P>
-constexpr auto solve_kernel<SOLVER_DPM2M, P> = dpm2m_solve_kernel<P>;
+template <int SOLVER, int P, int MODEL = 0>
+constexpr auto solve_kernel = heun_solve_kernel<P, MODEL>;
+template <int P, int MODEL>
+constexpr auto solve_kernel<SOLVER_DPM2M, P, MODEL> = dpm2m_solve_kernel<P, MODEL>;
 
-// A whole solve as one launch (gp_heun_solve_tile, gp_dpm2m_solve_tile).
+// A whole solve as one launch (gp_heun_solve_tile, gp_dpm2m_solve_tile and their _model forms: model 1 on plan 16 only).
 template <int SOLVER>
-int solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec, const float *tvec_all,
+int solve_tile(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec, const float *tvec_all,
                const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj, hipStream_t st) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
+    if ((model != 0 && model != 1) || ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x ||
+        !d || !score || !out)
         return GP_EINVAL;
     const long long rg = (long long)nclouds_per_group * k, R = ngroups * rg;
     if (R > 0x7fffffffLL / 9) return GP_EINVAL;  // row and element indices are ints up to R * 9
     if (R == 0) return GP_OK;
     int P = 0;
-    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
+    const int rc = gp_heun_layout_model(model, tile, ngroups, nclouds_per_group, k, &P);
     if (rc != GP_OK) return rc;
     const HeunArgs a = heun_args((int)R, k, 0, fixed_launches<SOLVER>(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
+    if (model == 1) {
+        if (P != 16 || !net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t) return GP_EINVAL;  // (plan 128 keeps its per-launch kernels)
+        constexpr size_t lds = gp_bwd::LDS_BYTES + (size_t)21 * 16 * sizeof(float);  // the backward pass's block and 21 floats per row behind it
+        return gp_launch<solve_kernel<SOLVER, 16, 1>>(dim3(ngroups * (int)((rg + 15) / 16)), dim3(TrunkCfg<16>::NT), lds, st, a, *net);
+    }
     return gp_with_tile(P, [&](auto tile_rows) {  // (GP_EINVAL for plan 128: the chain form keeps its per-launch kernels)
         constexpr int T = decltype(tile_rows)::value;
         const int nwg = ngroups * (int)((rg + T - 1) / T);
@@ -156,11 +175,25 @@ int solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, 
 extern "C" int gp_heun_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                                   const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                                   gp_stream_t s) {
-    return solve_tile<SOLVER_HEUN>(tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj, (hipStream_t)s);
+    return solve_tile<SOLVER_HEUN>(0, tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj, (hipStream_t)s);
 }
 
 extern "C" int gp_dpm2m_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                                    const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                                    gp_stream_t s) {
-    return solve_tile<SOLVER_DPM2M>(tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj, (hipStream_t)s);
+    return solve_tile<SOLVER_DPM2M>(0, tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj, (hipStream_t)s);
+}
+
+extern "C" int gp_heun_solve_tile_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                                        const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                                        float *out, float *traj, gp_stream_t s) {
+    return solve_tile<SOLVER_HEUN>(model, tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                   (hipStream_t)s);
+}
+
+extern "C" int gp_dpm2m_solve_tile_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                                         const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                                         float *out, float *traj, gp_stream_t s) {
+    return solve_tile<SOLVER_DPM2M>(model, tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                    (hipStream_t)s);
 }

@@ -344,12 +344,16 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_seeded_kernel(PcArgs 
 // A launch of the fixed-step Heun solver of the probability-flow ODE (cond_edm_sampler's method, samplers.py:230-290, on the VE score
 // model; HeunArgs, pc_rows.h) in the tile form: pc_step_tile's shape - row work on tid < P, the evaluation point handed to the trunk
 // through LDS - with the row-local heun_update_row in place of the PC update: no noise, no gradient norm, no partial sums, so no barrier
-// before the update and nothing after the score stores.  Score model, whole tiles.
+// before the update and nothing after the score stores.  Whole tiles.
 // SOLVER_DPM2M (dpm2m_step_kernel): a launch of the DPM-Solver++(2M) solver (pc_rows.h) - its schedule row, dpm2m_update_row, `d` holds
 // D_{i-2}; everything else is the same text.
-template <int P, int SOLVER = SOLVER_HEUN>
+// MODEL 1 (heun_step_kernel<16, energy>, dpm2m_step_kernel<16, energy>): the ENERGY network drives the solver with ITS score, the gradient
+// of the inner-product energy (energynet.py:200-222) - forward + vector-Jacobian product in the tile as in pc_step_tile<16, 1>; the nine
+// words score_vjp_tile leaves are the score itself (f / sigma + J_f^T (x / sigma), no 1e-7f) and are stored as they come.
+template <int P, int SOLVER = SOLVER_HEUN, int MODEL = 0>
 __device__ __forceinline__ void heun_step_tile(const HeunArgs &a, const gp_scorenet &net) {
-    using L = TrunkLds<P>;
+    static_assert(MODEL == 0 || P == gp_bwd::DP, "the backward pass runs on 16-row tiles");
+    using L = TrunkLds<P, MODEL == 1>;
     constexpr int SROW = fixed_sched_row<SOLVER>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int row0 = blockIdx.x * P, tid = threadIdx.x, i = a.step;
@@ -404,20 +408,28 @@ __device__ __forceinline__ void heun_step_tile(const HeunArgs &a, const gp_score
         load_x_tile<P>(lds, a.x, row0, a.nrows);
     }
     __syncthreads();
-    trunk_ftheta<P>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre);
-    const float *F = lds + L::OFF_H1;
-    for (int e = tid; e < P * POSE; e += TrunkCfg<P>::NT) {
-        const int r = e / POSE, j = e - r * POSE;
-        if (row0 + r < a.nrows) a.score[(size_t)(row0 + r) * POSE + j] = F[r * L::LDH + j] / (sigma + 1e-7f);
+    if constexpr (MODEL == 0) {
+        trunk_ftheta<P>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre);
+        const float *F = lds + L::OFF_H1;
+        for (int e = tid; e < P * POSE; e += TrunkCfg<P>::NT) {
+            const int r = e / POSE, j = e - r * POSE;
+            if (row0 + r < a.nrows) a.score[(size_t)(row0 + r) * POSE + j] = F[r * L::LDH + j] / (sigma + 1e-7f);
+        }
+    } else {
+        const float *F = gp_bwd::score_vjp_tile<gp_bwd::ENERGY>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre, sigma);
+        for (int e = tid; e < P * POSE; e += TrunkCfg<P>::NT) {
+            const int r = e / POSE, j = e - r * POSE;
+            if (row0 + r < a.nrows) a.score[(size_t)(row0 + r) * POSE + j] = F[r * gp_bwd::LDS_OUT + j];
+        }
     }
 }
-template <int P>
+template <int P, int MODEL = 0>
 __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_step_kernel(HeunArgs a, gp_scorenet net) {
-    heun_step_tile<P>(a, net);
+    heun_step_tile<P, SOLVER_HEUN, MODEL>(a, net);
 }
-template <int P>
+template <int P, int MODEL = 0>
 __global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_step_kernel(HeunArgs a, gp_scorenet net) {
-    heun_step_tile<P, SOLVER_DPM2M>(a, net);
+    heun_step_tile<P, SOLVER_DPM2M, MODEL>(a, net);
 }
 
 // The same launch in the chain form (trunk_chain.h).  A wave owns 16 * PT rows from the sampler update to the score: every lane
@@ -430,11 +442,12 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_step_kernel(HeunArgs a,
 // SEEDED (pc_step_chain_seeded_kernel): PcRows draws the noise (pc_rows.h).
 // HEUN (heun_step_chain_kernel; Args = HeunArgs): a launch of the fixed-step Heun solver (samplers.py:230-290) - PcRows runs the row-local
 // update, the score is stored, and there is no partial sum.  SOLVER_DPM2M (dpm2m_step_chain_kernel): the DPM-Solver++(2M) launch, the
-// same through PcRows' other update; the time row is the launch's own index.
+// same through PcRows' other update; the time row is the launch's own index.  Both with MODEL 1 too (heun_step_chain_kernel<2, energy>,
+// dpm2m_step_chain_kernel<2, energy>): the energy model's score drives the solver.
 template <int PT, int MODEL, bool SEEDED, int SOLVER = SOLVER_PC, class Args = PcArgs>
 __device__ __forceinline__ void pc_step_chain(const Args &a, const gp_scorenet &net) {
     constexpr bool HEUN = SOLVER != SOLVER_PC;
-    static_assert(HEUN == std::is_same<Args, HeunArgs>::value && (!HEUN || (MODEL == 0 && !SEEDED)), "HeunArgs drive the HEUN instantiations: score model");
+    static_assert(HEUN == std::is_same<Args, HeunArgs>::value && (!HEUN || !SEEDED), "HeunArgs drive the HEUN instantiations: no noise");
     using C = gp_chain::Cfg<PT>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), pt = lane & 15, g = lane >> 4, i = a.step;
@@ -506,13 +519,13 @@ template <int PT>
 __global__ __launch_bounds__(gp_chain::NT, 1) void pc_step_chain_seeded_kernel(PcArgs a, gp_scorenet net) {
     pc_step_chain<PT, 0, true>(a, net);
 }
-template <int PT>
+template <int PT, int MODEL = 0>
 __global__ __launch_bounds__(gp_chain::NT, 1) void heun_step_chain_kernel(HeunArgs a, gp_scorenet net) {
-    pc_step_chain<PT, 0, false, SOLVER_HEUN>(a, net);
+    pc_step_chain<PT, MODEL, false, SOLVER_HEUN>(a, net);
 }
-template <int PT>
+template <int PT, int MODEL = 0>
 __global__ __launch_bounds__(gp_chain::NT, 1) void dpm2m_step_chain_kernel(HeunArgs a, gp_scorenet net) {
-    pc_step_chain<PT, 0, false, SOLVER_DPM2M>(a, net);
+    pc_step_chain<PT, MODEL, false, SOLVER_DPM2M>(a, net);
 }
 
 // The kernels of a host template's arguments.  PC: seeded or not, score model (the energy model has one tile kernel and no seeded one).
@@ -520,15 +533,16 @@ template <bool SEEDED, int P, bool SPLIT = false>
 constexpr auto pc_tile_kernel = pc_step_kernel<P, 0, SPLIT>;
 template <int P, bool SPLIT>
 constexpr auto pc_tile_kernel<true, P, SPLIT> = pc_step_seeded_kernel<P, SPLIT>;
-// The fixed-step solvers (SOLVER_HEUN / SOLVER_DPM2M): tile and chain form.
-template <int SOLVER, int P>
-constexpr auto fixed_step_kernel = heun_step_kernel<P>;
-template <int P>
-constexpr auto fixed_step_kernel<SOLVER_DPM2M, P> = dpm2m_step_kernel<P>;
-template <int SOLVER, int PT>
-constexpr auto fixed_chain_kernel = heun_step_chain_kernel<PT>;
-template <int PT>
-constexpr auto fixed_chain_kernel<SOLVER_DPM2M, PT> = dpm2m_step_chain_kernel<PT>;
+// The fixed-step solvers (SOLVER_HEUN / SOLVER_DPM2M): tile and chain form, score (MODEL 0) or energy model (MODEL 1: 16-row tiles and
+// the chain form only).
+template <int SOLVER, int P, int MODEL = 0>
+constexpr auto fixed_step_kernel = heun_step_kernel<P, MODEL>;
+template <int P, int MODEL>
+constexpr auto fixed_step_kernel<SOLVER_DPM2M, P, MODEL> = dpm2m_step_kernel<P, MODEL>;
+template <int SOLVER, int PT, int MODEL = 0>
+constexpr auto fixed_chain_kernel = heun_step_chain_kernel<PT, MODEL>;
+template <int PT, int MODEL>
+constexpr auto fixed_chain_kernel<SOLVER_DPM2M, PT, MODEL> = dpm2m_step_chain_kernel<PT, MODEL>;
 
 }  // namespace
 
@@ -580,21 +594,26 @@ static int pc_step_launch(int model, int tile, int ngroups, int nclouds_per_grou
     });
 }
 
-// A launch of a fixed-step solver (gp_heun_step_plan, gp_dpm2m_step_plan).
+// A launch of a fixed-step solver (gp_heun_step_plan, gp_dpm2m_step_plan and their _model forms).
 template <int SOLVER>
-static int fixed_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
+static int fixed_step_plan(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                            const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                            hipStream_t st) {
-    if (ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 || launch >= fixed_launches<SOLVER>(nsteps, denoise) || !net || !cvec ||
-        !tvec_all || !sched || !centre || !x || !d || !score || !out)
+    if ((model != 0 && model != 1) || ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 ||
+        launch >= fixed_launches<SOLVER>(nsteps, denoise) || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
         return GP_EINVAL;
     const int rg = nclouds_per_group * k, R = ngroups * rg;
     if (R == 0) return GP_OK;
     int P = 0;
-    const int rc = gp_heun_layout(tile, ngroups, nclouds_per_group, k, &P);
+    const int rc = gp_heun_layout_model(model, tile, ngroups, nclouds_per_group, k, &P);
     if (rc != GP_OK) return rc;
+    if (model == 1 && (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t)) return GP_EINVAL;
     const HeunArgs a = heun_args(R, k, launch, fixed_launches<SOLVER>(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
     const int nwg = ngroups * ((rg + P - 1) / P);
+    if (model == 1) {  // the energy model: the forward + vector-Jacobian kernels, with their LDS (gp_heun_layout_model: 16 or 128)
+        if (P == 128) return gp_launch<fixed_chain_kernel<SOLVER, 2, 1>>(dim3(nwg), dim3(gp_chain::NT), gp_chain::CfgV<2>::LDS_BYTES, st, a, *net);
+        return gp_launch<fixed_step_kernel<SOLVER, 16, 1>>(dim3(nwg), dim3(TrunkCfg<16>::NT), gp_bwd::LDS_BYTES, st, a, *net);
+    }
     if (P == 128) return gp_launch<fixed_chain_kernel<SOLVER, 2>>(dim3(nwg), dim3(gp_chain::NT), gp_chain::Cfg<2>::LDS_BYTES, st, a, *net);
     if (gp_prepare_lds<fixed_step_kernel<SOLVER, 16>>(trunk_lds_bytes<16>()) || gp_prepare_lds<fixed_step_kernel<SOLVER, 32>>(trunk_lds_bytes<32>()) ||
         gp_prepare_lds<fixed_step_kernel<SOLVER, 64>>(trunk_lds_bytes<64>()))
@@ -730,11 +749,32 @@ int gp_heun_layout(int tile, int ngroups, int nclouds_per_group, int k, int *til
     return GP_OK;
 }
 
+int gp_heun_layout_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int *tile_out) {
+    if (model == 0) return gp_heun_layout(tile, ngroups, nclouds_per_group, k, tile_out);
+    if (model != 1 || ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || !tile_out) return GP_EINVAL;
+    // the energy model's score needs the backward pass: 16-row tiles (score_bwd.h) or the 128-row chain form (trunk_chain_vjp.h), as gp_pc_layout
+    const int rg = nclouds_per_group * k;
+    int P = tile;
+    if (P == 0) P = score_plan_rows_vjp(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    if (P != 16 && P != 128) return GP_EINVAL;  // (32 / 64-row tiles and head-split included: the backward pass has none)
+    if (P == 128 && !gp_chain::Cfg<2>::fits(k)) return GP_EINVAL;
+    if (ngroups > 1 && rg % P != 0) return GP_EINVAL;  // a workgroup must not straddle two batches
+    *tile_out = P;
+    return GP_OK;
+}
+
 int gp_heun_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                       const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                       gp_stream_t s) {
-    return fixed_step_plan<SOLVER_HEUN>(tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
-                                        (hipStream_t)s);
+    return fixed_step_plan<SOLVER_HEUN>(0, tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out,
+                                        traj, (hipStream_t)s);
+}
+
+int gp_heun_step_plan_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                            const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                            float *traj, gp_stream_t s) {
+    return fixed_step_plan<SOLVER_HEUN>(model, tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score,
+                                        out, traj, (hipStream_t)s);
 }
 
 int gp_dpm2m_launches(int nsteps, int denoise) { return nsteps < 1 ? GP_EINVAL : nsteps + 1 + (denoise ? 1 : 0); }
@@ -742,8 +782,15 @@ int gp_dpm2m_launches(int nsteps, int denoise) { return nsteps < 1 ? GP_EINVAL :
 int gp_dpm2m_step_plan(int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                        const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                        gp_stream_t s) {
-    return fixed_step_plan<SOLVER_DPM2M>(tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
-                                         (hipStream_t)s);
+    return fixed_step_plan<SOLVER_DPM2M>(0, tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out,
+                                         traj, (hipStream_t)s);
+}
+
+int gp_dpm2m_step_plan_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                             const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                             float *traj, gp_stream_t s) {
+    return fixed_step_plan<SOLVER_DPM2M>(model, tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score,
+                                         out, traj, (hipStream_t)s);
 }
 
 int gp_pc_step_coupled(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,

@@ -163,8 +163,9 @@ class GFObjectPose:
     def sample(self, data, sampler, init_x=None, T0=None, noise=None, return_process=True):
         if sampler == "dpm2m":
             # (ours) the fixed-step DPM-Solver++(2M) solve of the same ODE (samplers.Dpm2mSampler): the 'heun' branch's rules
-            if self.cfg.posenet_mode == "energy":
-                raise NotImplementedError("sampler 'dpm2m' with posenet_mode='energy': the DPM-Solver++(2M) solver has no energy-model kernel (use 'ode' or 'pc')")
+            if self.cfg.posenet_mode == "energy" and not getattr(self.cfg, "fixed_step_energy", False):
+                raise NotImplementedError("sampler 'dpm2m' with posenet_mode='energy': the DPM-Solver++(2M) solver serves the energy model only with "
+                                          "cfg.fixed_step_energy=True (opt-in; or use 'ode' or 'pc')")
             if self.cfg.sampling_steps is None:
                 raise ValueError("the dpm2m sampler needs cfg.sampling_steps")
             if getattr(self.cfg, "heun_grid", "geometric") not in HEUN_GRIDS:
@@ -172,8 +173,9 @@ class GFObjectPose:
         if sampler == "heun":
             # (ours) cond_edm_sampler's fixed-step Heun method on the score model's probability-flow ODE: what it cannot serve is said
             # before anything is computed
-            if self.cfg.posenet_mode == "energy":
-                raise NotImplementedError("sampler 'heun' with posenet_mode='energy': the Heun solver has no energy-model kernel (use 'ode' or 'pc')")
+            if self.cfg.posenet_mode == "energy" and not getattr(self.cfg, "fixed_step_energy", False):
+                raise NotImplementedError("sampler 'heun' with posenet_mode='energy': the Heun solver serves the energy model only with "
+                                          "cfg.fixed_step_energy=True (opt-in; or use 'ode' or 'pc')")
             if self.cfg.sampling_steps is None:
                 raise ValueError("the Heun sampler needs cfg.sampling_steps")
             if getattr(self.cfg, "heun_grid", "geometric") not in HEUN_GRIDS:
@@ -265,6 +267,22 @@ class GFObjectPose:
             out = smp.run(cvec, centre, x0, T0, num_steps=self.cfg.sampling_steps, eps=self.sampling_eps, return_process=return_process)
             self.last_energy_ode_stats = {"nfev": int(smp.last_stats["nfev"]), "attempts": int(smp.last_stats["n_attempts"])}
             return out
+        if sampler in ("heun", "dpm2m"):
+            # (ours; cfg.fixed_step_energy, checked by sample()) the fixed-step solvers driven by the energy model's score: prior and warm
+            # start as the 'ode' branch above, the sampler keyed by the model
+            T0 = self.T if T0 is None else T0
+            pr = self._prior_to_device((R, 9), T=T0)
+            x0 = pr if init_x is None else init_x.float() + pr
+            B = cvec.shape[0]
+            n, grid = int(self.cfg.sampling_steps), getattr(self.cfg, "heun_grid", "geometric")
+            key = (sampler + "-energy", B, K, n, grid, return_process)
+            smp = self._samplers.get(key)
+            if smp is None:
+                cls = HeunSampler if sampler == "heun" else Dpm2mSampler
+                smp = self._samplers[key] = cls(self.pose_score_net, B, K, n, self.device, grid=grid, record_traj=return_process, model="energy")
+            self.last_sampler = smp
+            xs, res = smp.run(cvec, centre, x0, T0=T0, eps=self.sampling_eps)
+            return (xs.clone() if xs is not None else None), res.clone()
         raise NotImplementedError(sampler)
 
     def calc_likelihood(self, data, atol=1e-5, rtol=1e-5, divergence="hutchinson", solver=None, steps=None):

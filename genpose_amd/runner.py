@@ -42,14 +42,29 @@ class SingleFrameRunner:
     agent's own exact-divergence log-likelihood, PoseNet.get_likelihood under the agent's cfg.likelihood_solver / likelihood_steps, fills
     both columns of the [n,K,2] array, cast to float32, and goes through the same ranking - no energy agent needed) or 'consensus' (ours: no
     network at all - reward.consensus_rank_aggregate scores every candidate by its mean distance to the cloud's other candidates, rotation
-    and translation independently, and ranks and aggregates in the same launch; the stored 'energy' is that array)."""
+    and translation independently, and ranks and aggregates in the same launch; the stored 'energy' is that array).
+
+    sample_from: 'score' (default) or 'energy' (ours; opt-in) - the ENERGY agent (energy_agent; score_agent may be None) draws the
+    candidates itself with its pred_func (a posenet_mode='energy' agent: 'ode' / 'pc', or 'heun' / 'dpm2m' under cfg.fixed_step_energy) and
+    then ranks them with get_energy(extract_pts_feature=False) on the cloud features pred_func left in the dict: ONE encoder pass per batch,
+    one checkpoint.  ranker 'energy' or 'consensus'; 'likelihood' is refused - likelihoods come from the score model."""
 
     RANKERS = ("energy", "likelihood", "consensus")
+    SAMPLE_FROM = ("score", "energy")
 
-    def __init__(self, score_agent, energy_agent=None, repeat_num=50, T0=0.55, batch_size=256, ratio=0.6, ranker="energy"):
+    def __init__(self, score_agent, energy_agent=None, repeat_num=50, T0=0.55, batch_size=256, ratio=0.6, ranker="energy", sample_from="score"):
         if ranker not in self.RANKERS:
             raise NotImplementedError(f"ranker {ranker!r}: one of {self.RANKERS}")
-        self.score_agent, self.energy_agent, self.ranker = score_agent, energy_agent, ranker
+        if sample_from not in self.SAMPLE_FROM:
+            raise ValueError(f"SingleFrameRunner(sample_from={sample_from!r}): one of {self.SAMPLE_FROM}")
+        if sample_from == "energy":
+            if ranker == "likelihood":
+                raise ValueError("SingleFrameRunner(sample_from='energy', ranker='likelihood'): likelihoods come from the score model; "
+                                 "ranker 'energy' or 'consensus'")
+            if energy_agent is None or energy_agent.cfg.posenet_mode != "energy":
+                raise ValueError("SingleFrameRunner(sample_from='energy') needs energy_agent with posenet_mode='energy'"
+                                 + ("" if energy_agent is None else f", got {energy_agent.cfg.posenet_mode!r}"))
+        self.score_agent, self.energy_agent, self.ranker, self.sample_from = score_agent, energy_agent, ranker, sample_from
         self.repeat_num, self.T0, self.batch_size, self.ratio = repeat_num, T0, batch_size, ratio
 
     def infer_tensors(self, clouds, sym=None):
@@ -65,7 +80,8 @@ class SingleFrameRunner:
         out = {"pred_pose": [], "multi_hypothesis_pred_RTs": [], "energy": [], "sorted_RTs": [], "average_sRT": []}
         for s in range(0, n, self.batch_size):  # evaluation_single.py:380-382 batch slicing
             sample = make_batch_sample(clouds[s:s + self.batch_size])
-            pred = self.score_agent.pred_func(data=sample, repeat_num=self.repeat_num, save_path=None, T0=self.T0)
+            sampling_agent = self.energy_agent if self.sample_from == "energy" else self.score_agent
+            pred = sampling_agent.pred_func(data=sample, repeat_num=self.repeat_num, save_path=None, T0=self.T0)
             out["pred_pose"].append(pred)
             out["multi_hypothesis_pred_RTs"].append(rotation.pose9_to_RT(pred))
             if self.ranker == "consensus":
@@ -78,6 +94,9 @@ class SingleFrameRunner:
                     # (pred_func left the clouds' features in the dict) higher = more likely = first, in both columns
                     ll32 = self.score_agent.get_likelihood(sample, pred, extract_pts_feature=False).float()
                     energy = torch.stack([ll32, ll32], dim=-1).contiguous()
+                elif self.sample_from == "energy":
+                    # (pred_func left the clouds' features - this agent's own - in the dict) no second encoder pass
+                    energy = self.energy_agent.get_energy(data=sample, pose_samples=pred, T=1e-5, extract_pts_feature=False)
                 else:
                     energy = self.energy_agent.get_energy(data=sample, pose_samples=pred, T=1e-5)  # evaluation_single.py:339-343
                 r = reward.rank_aggregate(pred, energy, ratio=self.ratio)
@@ -469,11 +488,16 @@ class _ScoreEmbedGraph:
 
     SLOT = "fixed-step-tracker"
 
-    def __init__(self, snet):
+    def __init__(self, snet, T_energy=None):
         self.snet = snet
         self.enc = snet.pointnet2_encoder("FixedStepTracker")
         self._a = ShapeCache(_FrameGraphs.MAX_SHAPES, on_evict=_unpin_score_embed)
         self.ev_e = None
+        if T_energy is not None:  # `snet` is an ENERGY network that also ranks (FixedStepTracker(sample_from='energy')): as _FrameGraphs.__init__
+            from .sde import SIGMA_MAX, SIGMA_MIN
+            t = torch.full((1,), float(T_energy), device=snet.device)
+            self.tvec_e = snet.pose_score_net.time_embed(t)[0].contiguous()
+            self.sigma_e = (SIGMA_MIN * (SIGMA_MAX / SIGMA_MIN) ** t).contiguous()
 
     def _body(self, pts):
         return pts.mean(dim=1), self.snet.pose_score_net.cloud_embed(self.enc.forward(pts, slot=self.SLOT))
@@ -527,10 +551,16 @@ class FixedStepTracker:
     by that axis alone); None: no object is.  The flags are uploaded only in a step whose names differ from the previous step's.
     launches: 'single' / 'chain' force the solve's form; None takes 'single' below SINGLE_MAX_ROWS rows where the plan is a tile plan.
     solver: 'heun' (default) or 'dpm2m' - the same frame with samplers.Dpm2mSampler's solve (steps + 1 evaluations instead of 2 steps + 1)
-    in HeunSampler's place; everything around the solve is unchanged."""
+    in HeunSampler's place; everything around the solve is unchanged.
+    sample_from: 'score' (default) or 'energy' (ours; opt-in) - tracking from an ENERGY checkpoint alone: score_agent may be None, the solve
+    runs on the energy agent's network with the energy model's score inside the kernels (samplers.HeunSampler / Dpm2mSampler(model='energy'))
+    and ranker 'energy' evaluates the same network on the same cloud embedding - one encoder graph (no side stream) and the frame's graph,
+    last_stats['replays'] == 2.  ranker 'energy' or 'consensus'; 'likelihood' is refused (likelihoods come from the score model).
+    launches=None keeps the chain here: the energy model's one-launch solve measured slower than its chain (profiles/fixed_step_energy.txt)."""
 
     RANKERS = ("energy", "likelihood", "consensus")
     SOLVERS = ("heun", "dpm2m")
+    SAMPLE_FROM = ("score", "energy")
     LAUNCHES = (None, "single", "chain")
     # rows below which launches=None takes the one-launch solve.  profiles/fixed_step_tracking.txt: its median lay below the chain's minimum
     # at 250, 800 and 3 200 rows (16-row tiles, 1.09x) and above it at 12 800 rows (64-row tiles, 0.97x); nothing was measured in between
@@ -539,12 +569,22 @@ class FixedStepTracker:
     RING = 4  # pinned blocks in rotation: the host rewrites one only after the copy issued four steps earlier has completed
 
     def __init__(self, score_agent, energy_agent=None, steps=8, repeat_num=50, T0=0.15, ratio=0.6, ranker="energy", seed=0, launches=None,
-                 grid="geometric", max_objects_per_frame=8, solver="heun", symmetric=None):
+                 grid="geometric", max_objects_per_frame=8, solver="heun", symmetric=None, sample_from="score"):
         from .samplers import HEUN_GRIDS
         if solver not in self.SOLVERS:
             raise ValueError(f"FixedStepTracker(solver={solver!r}): one of {self.SOLVERS}")
-        if score_agent.cfg.posenet_mode != "score":
-            raise ValueError(f"FixedStepTracker: the score agent's posenet_mode is {score_agent.cfg.posenet_mode!r}, the Heun solver needs 'score'")
+        if sample_from not in self.SAMPLE_FROM:
+            raise ValueError(f"FixedStepTracker(sample_from={sample_from!r}): one of {self.SAMPLE_FROM}")
+        if sample_from == "energy":
+            if ranker == "likelihood":
+                raise ValueError("FixedStepTracker(sample_from='energy', ranker='likelihood'): likelihoods come from the score model; "
+                                 "ranker 'energy' or 'consensus'")
+            if energy_agent is None or energy_agent.cfg.posenet_mode != "energy":
+                raise ValueError("FixedStepTracker(sample_from='energy') needs energy_agent with posenet_mode='energy'"
+                                 + ("" if energy_agent is None else f", got {energy_agent.cfg.posenet_mode!r}"))
+        elif score_agent.cfg.posenet_mode != "score":
+            raise ValueError(f"FixedStepTracker: the score agent's posenet_mode is {score_agent.cfg.posenet_mode!r}, the Heun solver needs 'score' "
+                             "(sample_from='energy' solves with the energy agent)")
         if ranker not in self.RANKERS:
             raise ValueError(f"FixedStepTracker(ranker={ranker!r}): one of {self.RANKERS}")
         if ranker == "energy" and energy_agent is None:
@@ -559,12 +599,17 @@ class FixedStepTracker:
             raise ValueError(f"FixedStepTracker(steps={steps}): at least one step")
         if int(max_objects_per_frame) < 1 or int(repeat_num) < 1:
             raise ValueError(f"FixedStepTracker(max_objects_per_frame={max_objects_per_frame}, repeat_num={repeat_num}): at least one")
-        for a in (score_agent, energy_agent) if ranker == "energy" else (score_agent,):
+        # the agent whose network the solver runs on; sample_from 'energy': the energy agent, which then serves the energy ranker on the SAME
+        # cloud embedding - one network, one encoder graph
+        self.sample_from = sample_from
+        self.sampling_agent = energy_agent if sample_from == "energy" else score_agent
+        self._two_nets = ranker == "energy" and sample_from == "score"
+        for a in (score_agent, energy_agent) if self._two_nets else (self.sampling_agent,):
             a.net.pointnet2_encoder("FixedStepTracker")  # refuses pts_encoder='pointnet_and_pointnet2': the graphs drive the PointNet++ stages
-        if getattr(score_agent.net, "coupling_group", None) is not None:
+        if getattr(self.sampling_agent.net, "coupling_group", None) is not None:
             raise ValueError("FixedStepTracker: the score agent has a coupling_group (a batch sharded over a process group); the frame graphs build "
                              "an uncoupled solver - use the agent's pred_func")
-        self.score_agent, self.energy_agent = score_agent, energy_agent if ranker == "energy" else None
+        self.score_agent, self.energy_agent = score_agent, energy_agent if ranker == "energy" or sample_from == "energy" else None
         self.steps, self.repeat_num, self.T0, self.ratio = int(steps), int(repeat_num), float(T0), ratio
         self.ranker, self.seed, self.launches, self.grid = ranker, int(seed) % (1 << 64), launches, grid
         self.max_objects, self.solver, self.symmetric = int(max_objects_per_frame), solver, symmetric
@@ -602,6 +647,10 @@ class FixedStepTracker:
     def _solve_form(self, rows, plan):
         if self.launches is not None:
             return self.launches
+        if self.sample_from == "energy":
+            # profiles/fixed_step_energy.txt: the energy model's one-launch solve is SLOWER than its chain at 250 and 3 200 rows
+            # (chain / single 0.92 - 0.94x; an evaluation is a forward + backward pass of ~40 us, the launches between them are not what binds)
+            return "chain"
         return "single" if plan != 128 and rows < self.SINGLE_MAX_ROWS else "chain"
 
     # ------------------------------------------------------------------ the frame's second graph
@@ -638,6 +687,8 @@ class FixedStepTracker:
         pose = pred.clone()
         pose[:, :, 6:] -= centre.unsqueeze(1)  # posenet_agent.py:516: translations relative to the cloud centre
         if self.ranker == "energy":
+            if not self._two_nets:  # sample_from 'energy': the network that drew the candidates ranks them, on the embedding the solve used
+                cvec_e = cvec_s
             energy = self.energy_agent.net.pose_score_net.evaluate(cvec_e, K, pose.reshape(n * K, 9), self._embed.tvec_e, self._embed.sigma_e,
                                                                    "energy").reshape(n, K, 2)
         else:
@@ -653,13 +704,14 @@ class FixedStepTracker:
 
     def _capture(self, key, a_outs, pts):
         from .samplers import Dpm2mSampler, HeunLikelihood, HeunSampler
-        net = self.score_agent.net
+        net = self.sampling_agent.net
         K = self.repeat_num
         n, dev = sum(c for _, c in key), pts.device
         Solver = Dpm2mSampler if self.solver == "dpm2m" else HeunSampler
-        probe = Solver(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False)
+        kw = dict(grid=self.grid, use_graph=False, model=self.sample_from)
+        probe = Solver(net.pose_score_net, n, K, self.steps, dev, **kw)
         form = self._solve_form(n * K, probe.plan)
-        smp = probe if form == "chain" else Solver(net.pose_score_net, n, K, self.steps, dev, grid=self.grid, use_graph=False, launches=form)
+        smp = probe if form == "chain" else Solver(net.pose_score_net, n, K, self.steps, dev, launches=form, **kw)
         smp.cvec = a_outs[1]  # graph A's static output: nothing is copied
         ent = {"key": key, "smp": smp, "a_outs": a_outs, "sel": max(1, int(self.ratio * K)),
                "src": torch.full((n,), -1, dtype=torch.int32, device=dev), "fallback": torch.zeros(n, 4, 4, device=dev),
@@ -693,7 +745,7 @@ class FixedStepTracker:
         return ent
 
     def step(self, frames):
-        net = self.score_agent.net
+        net = self.sampling_agent.net
         K = self.repeat_num
         live = [i for i, f in enumerate(frames) if f is not None and f[0].shape[0] > 0]
         out = [None] * len(frames)
@@ -706,15 +758,15 @@ class FixedStepTracker:
         dev = frames[live[0]][0].device
         self._grow(len(frames), dev)
         if self._embed is None:
-            if self.ranker == "energy":
+            if self._two_nets:
                 self.energy_agent.net._need_weights()
                 self._embed = _FrameGraphs(net, self.energy_agent.net, K, max(1, int(self.ratio * K)))
-            else:
-                self._embed = _ScoreEmbedGraph(net)
+            else:  # one network: the score model's, or (sample_from 'energy') the energy model's, which then ranks on the same embedding
+                self._embed = _ScoreEmbedGraph(net, T_energy=1e-5 if self.sample_from == "energy" and self.ranker == "energy" else None)
         key = tuple((i, int(frames[i][0].shape[0])) for i in live)
         pts = torch.cat([frames[i][0].float() for i in live], dim=0)
         a_outs = self._embed.embed(pts)
-        replays = 2 if self.ranker == "energy" else 1
+        replays = 2 if self._two_nets else 1
         ent = self._b.get(key)
         if ent is None or ent["a_outs"][1] is not a_outs[1]:  # (graph A of this cloud count was dropped and captured again: new static tensors)
             ent = self._b[key] = self._capture(key, a_outs, pts)
@@ -754,7 +806,7 @@ class FixedStepTracker:
             ent["seed"].copy_(ent["pin_seed"][slot], non_blocking=True)
         cur = torch.cuda.current_stream(dev)
         ent["ev"][slot].record(cur)
-        if self.ranker == "energy":
+        if self._two_nets:
             cur.wait_event(self._embed.ev_e)  # the energy model's embedding (side stream)
         ent["graph"].replay()
         replays += 1

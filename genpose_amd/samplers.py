@@ -399,7 +399,12 @@ class HeunSampler:
 
     B clouds in `groups` batches laid out back to back share each launch (a workgroup never straddles two of them); the result of a row
     does not depend on its neighbours.  trunk: as PCSampler - 'bf16x9' on the chain plan by default, 'f32mfma' for A/B.  tile: forces a
-    plan (16 / 32 / 64 tiles, 128 chain form); the head-split plan, the energy model and bf16x3 have no Heun kernel.
+    plan (16 / 32 / 64 tiles, 128 chain form); the head-split plan and bf16x3 have no Heun kernel.
+
+    model: 'score' (default) | 'energy' (ours; opt-in) - `net` holds the ENERGY network's weights and ITS score, the gradient of the
+    inner-product energy (energynet.py:200-222), drives the solver: forward + vector-Jacobian product inside the kernels (the `_model` entry
+    points), plans 16 and 128 only (gp_heun_layout_model), fp32 MFMA only (trunk None / 'f32mfma'), launches='single' on plan 16.
+    Schedules, grids, buffers, run-time T0 / eps, graph capture and last_stats are the score model's.
 
     launches: 'chain' (default) - one kernel launch per launch index; 'single' - the whole solve in ONE launch (gp_heun_solve_tile: a
     workgroup takes its tile's rows through every index itself, tile plans only), the same bits in x, the pose and the trajectory.  nlaunch,
@@ -411,6 +416,7 @@ class HeunSampler:
     SCHED_ROW = 4
     ENTRY = ("gp_heun_step_bf16x9", "gp_heun_step_plan", "gp_heun_solve_tile")
     KERNELS = ("heun_step_chain_kernel", "heun_step_kernel", "heun_solve_kernel")
+    MODELS = ("score", "energy")
 
     @staticmethod
     def _launches(nsteps, denoise):
@@ -420,7 +426,7 @@ class HeunSampler:
         return heun_schedule(self.n, T0, eps, self.grid, self.rho, self.denoise)
 
     def __init__(self, net, B, K, nsteps, device, groups=1, grid="geometric", rho=7.0, trunk=None, tile=None, record_traj=False, denoise=True,
-                 use_graph=True, launches="chain"):
+                 use_graph=True, launches="chain", model="score"):
         import ctypes
         if B % groups:
             raise ValueError(f"{B} clouds do not split into {groups} equal batches")
@@ -428,6 +434,12 @@ class HeunSampler:
             raise ValueError(f"heun grid {grid!r}: one of {HEUN_GRIDS}")
         if trunk not in (None, "bf16x9", "f32mfma"):
             raise ValueError(f"trunk {trunk!r}: 'bf16x9' or 'f32mfma'")
+        if model not in self.MODELS:
+            raise ValueError(f"model {model!r}: one of {self.MODELS}")
+        if model == "energy" and trunk == "bf16x9":
+            raise ValueError("trunk 'bf16x9' with model='energy': the forward + vector-Jacobian pass of the energy model's score has no "
+                             "split-bf16 form; use trunk=None or 'f32mfma'")
+        self.model = self.MODELS.index(model)
         if tile and int(tile) & _lib.PLAN_HEADSPLIT:
             raise NotImplementedError("the head-split plan has no Heun kernel: whole 16-row tiles serve such sizes (tile=16)")
         if launches not in self.LAUNCHES:
@@ -438,9 +450,9 @@ class HeunSampler:
         self.dev = torch.device(device)
         R = self.R = B * K
         t_out = ctypes.c_int(0)
-        if _lib.lib().gp_heun_layout(int(tile or 0), groups, B // groups, K, ctypes.byref(t_out)) != 0:
-            raise ValueError(f"{B // groups} clouds x {K} candidates per batch do not split into workgroups of plan {tile or 'auto'}; "
-                             "run the batches separately")
+        if _lib.lib().gp_heun_layout_model(self.model, int(tile or 0), groups, B // groups, K, ctypes.byref(t_out)) != 0:
+            raise ValueError(f"{B // groups} clouds x {K} candidates per batch do not split into workgroups of plan {tile or 'auto'}"
+                             + (" (the energy model has plans 16 and 128)" if self.model else "") + "; run the batches separately")
         self.plan = self.tile = t_out.value
         if launches == "single" and self.tile == 128:
             raise ValueError(f"launches='single' serves the tile plans (16 / 32 / 64 rows); {B} clouds x {K} candidates on plan {tile or 'auto'} "
@@ -448,12 +460,13 @@ class HeunSampler:
         self.launches = launches
         self.trunk = None
         if self.tile == 128:
-            self.trunk = trunk or "bf16x9"
+            self.trunk = "f32mfma" if self.model else trunk or "bf16x9"
             if self.trunk == "bf16x9":
                 self._x9 = net.w.bf16x9_packs()
         kc, kt, ks = self.KERNELS
-        self.kernel_name = (f"{kc}<bf16x9>" if self.trunk == "bf16x9" else f"{kc}<2>" if self.tile == 128
-                            else f"{ks}<{self.tile}>" if launches == "single" else f"{kt}<{self.tile}>")
+        sfx = ",energy>" if self.model else ">"
+        self.kernel_name = (f"{kc}<bf16x9>" if self.trunk == "bf16x9" else f"{kc}<2{sfx}" if self.tile == 128
+                            else f"{ks}<{self.tile}{sfx}" if launches == "single" else f"{kt}<{self.tile}{sfx}")
         f = lambda *s: torch.empty(*s, device=self.dev)
         self.x, self.d, self.score, self.out = f(R, 9), f(R, 9), f(R, 9), f(R, 9)
         self.cvec, self.centre = f(B, 768), f(B, 3)
@@ -475,12 +488,14 @@ class HeunSampler:
                 ptr(self.traj))
         if self.trunk == "bf16x9":
             _lib.call(self.ENTRY[0], *shape, self.net.w.ref(), *bufs, *(ptr(w) for w in self._x9), stream_ptr())
+        elif self.model:
+            _lib.call(self.ENTRY[1] + "_model", self.model, self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
         else:
             _lib.call(self.ENTRY[1], self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
 
     def _launch_all(self):
         if self.launches == "single":
-            _lib.call(self.ENTRY[2], self.plan, self.groups, self.B // self.groups, self.K, self.n, int(self.denoise), self.net.w.ref(),
+            _lib.call(*((self.ENTRY[2] + "_model", self.model) if self.model else (self.ENTRY[2],)), self.plan, self.groups, self.B // self.groups, self.K, self.n, int(self.denoise), self.net.w.ref(),
                       ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
                       ptr(self.traj), stream_ptr())
             return

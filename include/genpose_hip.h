@@ -451,7 +451,7 @@ int gp_philox_raw(int64_t n, const void *counters, const void *keys, void *out, 
  * evaluates at row (l + 1) / 2).  x [R,9] in / state; d, score [R,9] scratch; out [R,9]; traj [nsteps][R][9] or NULL; centre [clouds][3].
  * Plans: 16 / 32 / 64-row tiles and the 128-row chain form (tile as in gp_pc_layout, 0 = gp_heun_layout's choice); every launch of a
  * chain uses the same plan.  Not served: the head-split plan (GP_EINVAL; gp_heun_layout gives such sizes whole 16-row tiles), the energy
- * model, bf16x3.  GP_EINVAL with nothing written for nsteps < 1, launch outside [0, launches), null buffers or a plan that does not fit. */
+ * model (the _model forms below serve it), bf16x3.  GP_EINVAL with nothing written for nsteps < 1, launch outside [0, launches), null buffers or a plan that does not fit. */
 int gp_heun_launches(int nsteps, int denoise);
 /* The plan of a Heun chain (samplers.py:230-290): gp_pc_layout's row thresholds for the score model minus head-split; tile = 0 asks for
  * the choice, else 16 / 32 / 64 / 128.  GP_EINVAL when a workgroup of the plan would straddle two groups. */
@@ -514,6 +514,36 @@ int gp_dpm2m_step_bf16x9(int ngroups, int nclouds_per_group, int k, int launch, 
 int gp_dpm2m_solve_tile(int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                         const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                         gp_stream_t s);
+
+/* THE FIXED-STEP SOLVERS ON THE ENERGY MODEL (opt-in; ours).  The `_model` forms of the five entry points above take a leading `model`:
+ * 0 launches exactly what the unsuffixed entry point launches; 1 drives the same solver, schedule, buffers and launch chain with the
+ * ENERGY network's score - the gradient of its inner-product energy, f / sigma + J_f^T (x / sigma) (energynet.py:200-222), evaluated
+ * inside the kernels by the forward + vector-Jacobian pass gp_pc_step_plan(model = 1) uses - in place of the score model's
+ * f / (sigma + 1e-7) (samplers.py:230-290).  `net` then holds the energy network's weights and must carry the transposed packs
+ * (w_headx_t, w_pose2_t, w_pose0_t): GP_EINVAL without them.  Model 1 has the 16-row tile form and the 128-row chain form only (fp32
+ * MFMA; no 32 / 64-row tiles, no head-split, no bf16x9): GP_EINVAL for any other plan, and for a model other than 0 / 1. */
+/* The plan of a fixed-step chain for `model` (samplers.py:230-290, energynet.py:200-222): model 0 is gp_heun_layout; model 1 takes
+ * gp_pc_layout(model = 1)'s choice for tile = 0 (16 or 128), else 16 / 128.  GP_EINVAL for 32 / 64 / head-split under model 1, when the
+ * chain form's workgroups would span more clouds than it stages (small k), or when a workgroup would straddle two groups. */
+int gp_heun_layout_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int *tile_out);
+/* One launch of the Heun chain for `model` (samplers.py:230-290, energynet.py:200-222); arguments after `model` as gp_heun_step_plan. */
+int gp_heun_step_plan_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                            const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                            float *traj, gp_stream_t s);
+/* One launch of the DPM-Solver++(2M) chain for `model` (samplers.py:230-290's grid, energynet.py:200-222); arguments after `model` as
+ * gp_dpm2m_step_plan. */
+int gp_dpm2m_step_plan_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                             const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                             float *traj, gp_stream_t s);
+/* The whole Heun / DPM-Solver++(2M) solve in one launch for `model` (samplers.py:230-290, energynet.py:200-222): the contract of
+ * gp_heun_solve_tile / gp_dpm2m_solve_tile - x, out and traj BIT FOR BIT what the chain of gp_*_step_plan_model calls on the same plan
+ * leaves.  Model 1 on plan 16 only (tile 16, or 0 where gp_heun_layout_model chooses 16): GP_EINVAL for the chain form. */
+int gp_heun_solve_tile_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                             const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                             float *out, float *traj, gp_stream_t s);
+int gp_dpm2m_solve_tile_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                              const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                              float *out, float *traj, gp_stream_t s);
 
 /* FIXED-STEP HEUN SOLVE OF THE EXACT-LIKELIHOOD ODE (opt-in; csrc/heun_likelihood.hip).  cond_ode_likelihood's system (samplers.py:22-99)
  * d[x; logp]/dt = -g^2/2 [score; div_x score] with the exact divergence of gp_score_div_exact, integrated in sigma from sigma(eps) UP to
