@@ -398,11 +398,16 @@ int gp_quat_trans_to_rt(int n, const float *quat_trans, float *out, gp_stream_t 
 
 int gp_rank_aggregate_rt(int b, int k, int sel, int is_f64, const void *poses, const float *energy, void *sorted_poses, float *sorted_energy,
                          int32_t *order, float *avg_pose, double *sorted_rt, float *avg_rt, gp_stream_t s) {
-    if (b < 0 || k <= 0 || k > 2048 || !poses || !energy) return GP_EINVAL;
+    if (b < 0 || k <= 0 || k > GP_RANK_MAX_K || !poses || !energy) return GP_EINVAL;
     if (avg_pose && (sel <= 0 || sel > k)) return GP_EINVAL;
     if (avg_rt && !avg_pose) return GP_EINVAL;
     if (b == 0) return GP_OK;
     const size_t lds = (size_t)k * 16 + 16 + (size_t)(avg_pose ? sel : 0) * 32;
+    // sel = k >= 1366 is above the 64 KB default.  Both kernels get the LARGEST request this entry point serves, whatever this call's own
+    // size and dtype: the first call - a runner's warm-up, outside any stream capture - then covers every later one.
+    constexpr size_t lds_max = (size_t)GP_RANK_MAX_K * (16 + 32) + 16;
+    static_assert(lds_max <= 160 * 1024, "the largest ranking must fit the CU's LDS");
+    if (gp_prepare_lds<rank_aggregate_kernel<float>, rank_aggregate_kernel<double>>(lds_max)) return GP_ELAUNCH;
     if (is_f64)
         hipLaunchKernelGGL(rank_aggregate_kernel<double>, dim3(b), dim3(64), lds, (hipStream_t)s, k, sel, (const double *)poses, energy,
                            (double *)sorted_poses, sorted_energy, order, avg_pose, sorted_rt, avg_rt);

@@ -71,6 +71,8 @@ class DepthToClouds:
         pcl = torch.empty(n, cap, 3, device=self.dev)
         count = torch.zeros(n, dtype=torch.int32, device=self.dev)
         dcount = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        if n == 0:  # a frame without detections: the empty tensors have no address to hand to the entry point (NULL is GP_EINVAL there)
+            return pcl, count, dcount
         _lib.call("gp_roi_to_cloud", H, W, n, self.img, ptr(depth), ptr(masks), ptr(minv), self.fx, self.fy, self.cx, self.cy, ptr(pcl),
                   ptr(count), ptr(dcount), stream_ptr())
         return pcl, count, dcount

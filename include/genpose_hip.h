@@ -685,7 +685,14 @@ int gp_rk45_set_dense_grouped(int ngroups, void *state, const double *t_eval_dev
  * ------------------------------------------------------------------------------------------------ */
 
 /* poses [b,k,9] f32/f64 (is_f64), energy [b,k,2] f32 -> sorted_poses (same dtype), sorted_energy [b,k,2],
- * order [b,k,2] i32 (stable descending), avg_pose [b,7] f32 (w,x,y,z,tx,ty,tz) over the top `sel` candidates. */
+ * order [b,k,2] i32 (stable descending), avg_pose [b,7] f32 (w,x,y,z,tx,ty,tz) over the top `sel` candidates.
+ * Limits: 1 <= k <= GP_RANK_MAX_K; 1 <= sel <= k when avg_pose is given (sel is ignored without it); b >= 0, b == 0 launches nothing.
+ * Anything else returns GP_EINVAL before a launch.  Every (k, sel) inside the limits is served: one wave per cloud keeps the energies,
+ * the ranking and the selected quaternions in 16 k + 16 + 32 sel bytes of LDS - above the 64 KB default from sel = k = 1366 on, 98 320 at
+ * sel = k = GP_RANK_MAX_K - and the entry point raises both kernels' dynamic-LDS limit to that maximum on its first call with b > 0, which
+ * therefore has to come outside a stream capture (the runners' warm-up); GP_ELAUNCH when the runtime refuses.  The ranking compares
+ * k (k - 1) pairs per column on ONE wave: meant for tens to hundreds of candidates, milliseconds at the limit. */
+#define GP_RANK_MAX_K 2048
 int gp_rank_aggregate(int b, int k, int sel, int is_f64, const void *poses, const float *energy, void *sorted_poses,
                       float *sorted_energy, int32_t *order, float *avg_pose, gp_stream_t s);
 /* The same launch with the 4x4 forms the runners hand on written by it as well (either may be NULL): sorted_rt [b,k,4,4] f64 =

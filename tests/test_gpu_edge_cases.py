@@ -44,6 +44,19 @@ def test_c_abi_rejects_bad_arguments_and_accepts_empty_batches():
     assert l.gp_rank_aggregate_rt(2, 50, 30, 0, _p(xyz), _p(xyz), None, None, None, None, None, _p(xyz), st) == -1  # an aggregated 4x4 without the aggregate
     assert l.gp_rank_aggregate_rt(2, 50, 51, 0, _p(xyz), _p(xyz), None, None, None, _p(xyz), None, None, st) == -1   # more selected than candidates
     assert l.gp_rank_aggregate_rt(2, 0, 0, 0, _p(xyz), _p(xyz), None, None, None, None, None, None, st) == -1        # k = 0
+    # the limits section D states: k <= GP_RANK_MAX_K = 2048, sel <= k; inside them every size is served, also where the request
+    # 16 k + 16 + 32 sel bytes of dynamic LDS passes the 64 KB a launch has by default (sel = k = 1365: exactly 65 536; 1366: above)
+    big = torch.randn(1, 2049, 9, device="cuda")
+    big_e = torch.randn(1, 2049, 2, device="cuda")
+    avg = torch.full((1, 7), float("nan"), device="cuda")
+    for k, sel, want in ((1365, 1365, 0), (1366, 1366, 0), (2048, 1228, 0), (2048, 2048, 0), (2048, 2049, -1), (2049, 1, -1), (2049, 2049, -1),
+                         (2048, 0, -1), (2048, -1, -1)):
+        avg.fill_(float("nan"))
+        assert l.gp_rank_aggregate_rt(1, k, sel, 0, _p(big), _p(big_e), None, None, None, _p(avg), None, None, st) == want, (k, sel)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(avg).all()) == (want == 0), (k, sel)  # served: the aggregate is written; refused: nothing is launched
+    assert l.gp_rank_aggregate_rt(1, 2049, 0, 0, _p(big), _p(big_e), None, None, None, None, None, None, st) == -1  # ranking only: the same cap on k
+    assert l.gp_rank_aggregate(1, 2049, 1, 0, _p(big), _p(big_e), None, None, None, _p(avg), st) == -1
     assert l.gp_rk45_partials_count(0, 0, 0, 5, 50) == -1 and l.gp_rk45_partials_count(3, 0, 1, 5, 50) == -1           # no group / unknown model
     assert l.gp_rk45_partials_count(0, 48, 1, 256, 50) == -1 and l.gp_rk45_partials_count(0, 0x200, 1, 256, 50) == -1  # 48 rows only under the shared plan; no tile size
     assert l.gp_rk45_plan_rows(0, 0, 5, 50) == -1 and l.gp_rk45_plan_rows_unshared(0, 1, 0, 50) == -1
