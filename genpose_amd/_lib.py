@@ -57,6 +57,7 @@ SIGNATURES = {
     "gp_sa_tail_position": [c_int, c_int],
     "gp_sa_pre_mlp_max_bf16x3": [c_int] * 7 + [P, P, P, P, c_int, c_int] + [P] * 7 + [c_int, c_int, P],
     "gp_sa_pre_mlp_max_bf16x9": [c_int] * 7 + [P, P, P, P, c_int, c_int] + [P] * 6 + [c_int, c_int, P],
+    "gp_sa_lds_bf16x9": [c_int] * 7 + [P, P, P, P, c_int, c_int] + [P] * 7 + [c_int, c_int, P],
     "gp_sa_groupall_bf16x9": [c_int] * 5 + [P, P] + ([c_int] + [P] * 5 + [c_int]) * 2 + [P, c_int, P],
     "gp_pointnet_stn_pool": [c_int, c_int] + [P] * 8 + [P],
     "gp_pointnet_feat_pool": [c_int, c_int] + [P] * 11 + [P],

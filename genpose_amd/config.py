@@ -37,6 +37,7 @@ DEFAULTS = dict(
     ode_trunk=None,  # (ours) 'bf16x9': opt-in exact-product split-bf16 trunk in the ODE sampler's chain-plan stage kernels (ODESampler(trunk=)); None / 'f32mfma': the fp32 MFMA kernels
     encoder_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products on the 128-196-256 grouping level (csrc/sa_bf16x3.hip)
     encoder_level2="auto",  # (ours) under encoder_precision 'f32', the arithmetic of grouping level 2 (128-196-256): 'bf16x9' = exact-product split bf16 on the BF16 matrix pipe (csrc/sa_bf16x9.hip, the fp32 kernels' error class), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the adaptive ODE sampler (its goldens pin RK45 attempt counts that move with the last bits of the features); encoder_precision='bf16x9' forces it
+    encoder_level1="auto",  # (ours) the arithmetic of grouping level 1 (64-64/96-128): 'bf16x9' = layers 2-3 as exact-product split bf16 with LDS-resident weights (csrc/sa_lds_bf16x9.hip, the fp32 kernels' error class; batches below Pointnet2EncoderHIP.LEVEL1_BF16X9_MIN_CLOUDS keep the fp32 kernels), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the ODE, Heun and DPM samplers (their goldens pin fp32 bits)
     encoder_level3="auto",  # (ours) the arithmetic of the GroupAll level (128 points x 512 -> 256 -> 256 | 384 -> 512): 'bf16x9' = all three layers of both scales as exact-product split bf16 in one launch (csrc/sa_groupall_bf16x9.hip, the fp32 kernels' error class; batches below Pointnet2EncoderHIP.LEVEL3_BF16X9_MIN_CLOUDS keep the fp32 kernels), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the ODE, Heun and DPM samplers (their goldens pin fp32 bits)
     dist_arith=DEFAULT_DIST_ARITH,  # (ours) contraction convention of the grouping operators' distances, see above
     synset_names=["bottle", "bowl", "camera", "can", "laptop", "mug"], img_size=256, max_eval_num=10000000, results_path="",
@@ -54,6 +55,17 @@ def encoder_precision_of(cfg):
         mode = getattr(cfg, "sampler_mode", None) or ["ode"]
         lvl2 = "bf16x9" if mode[0] == "pc" else "f32mfma"
     return "bf16x9" if prec == "f32" and lvl2 == "bf16x9" else prec
+
+
+def encoder_level1_of(cfg):
+    """The `level1` of Pointnet2EncoderHIP a namespace asks for (the reference's own namespace has no such field: 'auto')."""
+    lvl1 = getattr(cfg, "encoder_level1", "auto")
+    if lvl1 not in ("auto", "bf16x9", "f32mfma"):
+        raise ValueError(f"encoder_level1 {lvl1!r}: 'auto', 'bf16x9' or 'f32mfma'")
+    if lvl1 == "auto":
+        mode = getattr(cfg, "sampler_mode", None) or ["ode"]
+        lvl1 = "bf16x9" if mode[0] == "pc" else "f32mfma"
+    return lvl1
 
 
 def encoder_level3_of(cfg):

@@ -6,7 +6,9 @@ forward(pts [B,N,3] f32 on the GPU) -> [B,1024].  Launch sequence per call (all 
   L x gp_point_linear   hoisted feature half of the first layer, once per source point (both scales)
   2L x gp_sa_pre_mlp_max_layout  gather -> xyz half of layer 1 -> layers 2-3 on fp32 MFMA -> max-pool, per scale (register-chain kernels;
                         the hidden-layer layout the weights were packed for, weights.SAScale); grouping level 2 (128-196-256) by default
-                        through gp_sa_pre_mlp_max_bf16x9: the same job with layers 2-3 as exact-product split bf16
+                        through gp_sa_pre_mlp_max_bf16x9: the same job with layers 2-3 as exact-product split bf16; under level1 =
+                        'bf16x9', from LEVEL1_BF16X9_MIN_CLOUDS clouds up, grouping level 1 (64-64/96-128) through gp_sa_lds_bf16x9: the
+                        same arithmetic with both layers' weights LDS-resident
   1 + 2 x the same pair  GroupAll level: whole rounds of 256 clouds on the ring kernel (one cloud per workgroup), the rest on 32-row tiles
                         (the tiles of a cloud combine by integer atomic max into a zeroed buffer); under level3 = 'bf16x9', from
                         LEVEL3_BF16X9_MIN_CLOUDS clouds up, ONE gp_sa_groupall_bf16x9 instead: all three layers of both scales as
@@ -52,7 +54,7 @@ def _unpin_entry(key, ent):
 
 
 class Pointnet2EncoderHIP:
-    def __init__(self, state_dict, device="cuda", params="light", prefix="pts_encoder.", arith=None, precision="f32", level3=None):
+    def __init__(self, state_dict, device="cuda", params="light", prefix="pts_encoder.", arith=None, precision="f32", level3=None, level1=None):
         """arith: contraction convention of the squared distances in furthest point sampling and the ball queries ('A' | 'B' | 'C',
         config.DEFAULT_DIST_ARITH when None; include/genpose_hip.h GP_ARITH_*).
         precision: 'f32' (default of this class): every dense layer on the fp32 matrix pipe.
@@ -66,12 +68,19 @@ class Pointnet2EncoderHIP:
         (what an agent of the PC sampler asks for by default, config.encoder_level3_of): all three layers of both scales as exact-product
         split bf16 in one launch (csrc/sa_groupall_bf16x9.hip) for batches of LEVEL3_BF16X9_MIN_CLOUDS clouds or more; where one of the
         level's six folded matrices does not split exactly, or the level is not the light encoder's, it keeps the fp32 kernels
-        (`level3_kernel` says which serves it)."""
+        (`level3_kernel` says which serves it).
+        level1: grouping level 1 (64-64/96-128).  None / 'f32mfma' (default of this class): the fp32 kernels, bit for bit.  'bf16x9' (what an
+        agent of the PC sampler asks for by default, config.encoder_level1_of): layers 2-3 as exact-product split bf16 with LDS-resident
+        weights (csrc/sa_lds_bf16x9.hip) for batches of LEVEL1_BF16X9_MIN_CLOUDS clouds or more; a scale whose shape is not instantiated or
+        whose folded weights do not split exactly keeps the fp32 kernel (`sa_kernels[(1, i)]` says which serves scale i)."""
         if precision not in ("f32", "bf16x3", "bf16x9"):
             raise ValueError(f"encoder precision {precision!r}: 'f32', 'bf16x9' or 'bf16x3'")
         if level3 not in (None, "f32mfma", "bf16x9"):
             raise ValueError(f"encoder level3 {level3!r}: 'f32mfma' or 'bf16x9'")
+        if level1 not in (None, "f32mfma", "bf16x9"):
+            raise ValueError(f"encoder level1 {level1!r}: 'f32mfma' or 'bf16x9'")
         self.precision = precision
+        self.level1 = level1 or "f32mfma"
         self.level3 = level3 or "f32mfma"
         self.device = torch.device(device)
         self.arith = dist_arith_code(arith)
@@ -97,12 +106,22 @@ class Pointnet2EncoderHIP:
                     name = "bf16x3"
                 elif precision == "bf16x9" and k > 0 and shape in self.BF16X9_SHAPES and (npnt * shape[1]) % 32 == 0 and sc.bf16x9_packs() is not None:
                     name = "bf16x9"
+                elif (self.level1 == "bf16x9" and k > 0 and shape in self.LEVEL1_BF16X9_SHAPES and (npnt * shape[1]) % 32 == 0
+                      and sc.bf16x9_lds_packs() is not None):
+                    name = "bf16x9"
                 self.sa_kernels[(k, i)] = name
 
     MAX_WORKSPACES = 12
     # batches from this many clouds up take the split-bf16 GroupAll kernel under level3 = 'bf16x9' (one 128-row item per CU and scale:
     # below, the fp32 tile kernels split finer; measured crossover, profiles/sa_groupall_bf16x9.txt)
     LEVEL3_BF16X9_MIN_CLOUDS = 128
+    # batches from this many clouds up take the LDS-resident split-bf16 kernel under level1 = 'bf16x9': the smallest measured size at which
+    # both scales together win against the fp32 kernels (profiles/sa_lds_bf16x9.txt: at 5 clouds one 12-wave workgroup copies 72 KB of
+    # weights for a handful of units and the pair ties); below, the fp32 kernels with their bits
+    LEVEL1_BF16X9_MIN_CLOUDS = 64
+    # (layer widths, neighbourhood size) the LDS-resident exact-product split-bf16 kernel is instantiated for: grouping level 1 of the
+    # light / dense encoders (csrc/sa_lds_bf16x9.hip)
+    LEVEL1_BF16X9_SHAPES = {((64, 64, 128), 16), ((64, 96, 128), 32)}
     # (layer widths, neighbourhood size) the exact-product split-bf16 kernel is instantiated for: grouping level 2 (csrc/sa_bf16x9.hip)
     BF16X9_SHAPES = {((128, 196, 256), 16), ((128, 196, 256), 32)}
     # (layer widths, neighbourhood size) the opt-in split-bf16 kernel is instantiated for: grouping levels 1 and 2 (csrc/sa_bf16x3.hip)
@@ -416,7 +435,15 @@ class Pointnet2EncoderHIP:
                     off += sc.couts[2]
                     zoff += sc.couts[0]
                     continue
-                if self.sa_kernels[(k, i)] == "bf16x9":
+                if self.sa_kernels[(k, i)] == "bf16x9" and (tuple(sc.couts), nss[i]) in self.LEVEL1_BF16X9_SHAPES:
+                    if B >= self.LEVEL1_BF16X9_MIN_CLOUDS:
+                        w2x9, b2x9, w3x9, b3x9 = sc.bf16x9_lds_packs()
+                        _lib.call("gp_sa_lds_bf16x9", B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(src["bq"][k][i]), ptr(z),
+                                  zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(w2x9), ptr(b2x9), ptr(w3x9), ptr(b3x9), ptr(out), cout_total, off, st)
+                        off += sc.couts[2]
+                        zoff += sc.couts[0]
+                        continue
+                elif self.sa_kernels[(k, i)] == "bf16x9":
                     wx9, b2x9, b3x9 = sc.bf16x9_packs()
                     _lib.call("gp_sa_pre_mlp_max_bf16x9", B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(src["bq"][k][i]), ptr(z),
                               zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(wx9), ptr(b2x9), ptr(b3x9), ptr(out), cout_total, off, st)

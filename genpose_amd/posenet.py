@@ -14,7 +14,7 @@ and every cloud owns K consecutive pose rows - this is how PoseNet.pred_func avo
 """
 import torch
 
-from .config import encoder_level3_of, encoder_precision_of
+from .config import encoder_level1_of, encoder_level3_of, encoder_precision_of
 from .encoder import Pointnet2EncoderHIP
 from .lru import ShapeCache
 from .pointnet_encoder import ACT_RELU, PointNetEncoderHIP, dense_rows
@@ -61,7 +61,8 @@ class GFObjectPose:
         params = getattr(self.cfg, "pointnet2_params", "light")
         if self.cfg.pts_encoder == "pointnet_and_pointnet2":
             self.pts_pointnet2_encoder = Pointnet2EncoderHIP(sd, self.device, params, prefix="pts_pointnet2_encoder.", arith=getattr(self.cfg, "dist_arith", None),
-                                                             precision=encoder_precision_of(self.cfg), level3=encoder_level3_of(self.cfg))
+                                                             precision=encoder_precision_of(self.cfg), level3=encoder_level3_of(self.cfg),
+                                                             level1=encoder_level1_of(self.cfg))
             self.pts_pointnet_encoder = PointNetEncoderHIP(sd, self.device, prefix="pts_pointnet_encoder.")
             W, b = sd["fusion_layer.weight"].detach().float().cpu().contiguous(), sd["fusion_layer.bias"].detach().float().cpu().contiguous()
             if tuple(W.shape) != (1024, 2048) or b.numel() != 1024:
@@ -69,7 +70,7 @@ class GFObjectPose:
             self.fusion_layer = (W.to(self.device), b.to(self.device))
         else:
             self.pts_encoder = Pointnet2EncoderHIP(sd, self.device, params, arith=getattr(self.cfg, "dist_arith", None), precision=encoder_precision_of(self.cfg),
-                                                   level3=encoder_level3_of(self.cfg))
+                                                   level3=encoder_level3_of(self.cfg), level1=encoder_level1_of(self.cfg))
         self.pose_score_net = ScoreNetHIP(sd, self.device)
         self._samplers.clear()
         return self

@@ -89,6 +89,7 @@ class SAScale:
         self._device = device
         self._bf16x3 = None
         self._bf16x9 = None
+        self._bf16x9_lds = None
         c2 = self.couts[1]
         if c2 % 16:
             # hidden width not a multiple of 16 (light level 2: 196): the channels of the last, partly filled 16-channel block go to
@@ -141,6 +142,24 @@ class SAScale:
             dev = self._device
             self._bf16x9 = (w.to(dev), b2p.to(dev), b3.float().contiguous().to(dev))
         return self._bf16x9 or None
+
+    def bf16x9_lds_packs(self):
+        """Operands of the exact-product split-bf16 kernel with LDS-resident weights (csrc/sa_lds_bf16x9.hip: grouping level 1, hidden widths
+        that are whole 32-wide k-blocks) for layers 2 and 3: -> (w2 [c1/32][c2/16][3][64][8] int16, b2 [c2], w3 [c2/32][c3/16][3][64][8], b3 [c3])
+        as device tensors (pack_bf16x9, channel order as trained); or None where the widths are not whole k-blocks / chunks or a BN-folded
+        weight does not split exactly into three normal bf16 terms (split_bf16x9) - the caller keeps the fp32 kernel for this scale."""
+        if self._bf16x9_lds is None:
+            (_, _), (W2, b2), (W3, b3) = self._folded_plain
+            c1, c2, c3 = self.couts
+            self._bf16x9_lds = False
+            if c1 % 32 == 0 and c2 % 32 == 0 and c3 % 16 == 0:
+                try:
+                    w2, w3 = pack_bf16x9(W2, c2 // 16, c1 // 32), pack_bf16x9(W3, c3 // 16, c2 // 32)
+                except ValueError:
+                    return None
+                dev = self._device
+                self._bf16x9_lds = (w2.to(dev), b2.float().contiguous().to(dev), w3.to(dev), b3.float().contiguous().to(dev))
+        return self._bf16x9_lds or None
 
 
 def pack_bf16x3(W, n_chunks, k_blocks, chain=True):

@@ -196,6 +196,18 @@ int gp_sa_pre_mlp_max_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c
                              const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w23_x9, const float *bias2,
                              const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s);
 
+/* gp_sa_pre_mlp_max for grouping level 1 of the light / dense encoders ((c1, c2, c3), ns = (64, 64, 128), 16 | (64, 96, 128), 32; hoisted first
+ * layer: z required) with layers 2 and 3 as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (csrc/sa_lds_bf16x9.hip; the arithmetic of
+ * gp_sa_pre_mlp_max_bf16x9), both layers' weights LDS-resident as hi / mid / lo, no barrier in the row loop.  Layer 1, the pooling, the inputs
+ * and the [b, np, c3] output columns are gp_sa_pre_mlp_max's.  w2_x9 / w3_x9: the weights as hi / mid / lo bf16 triples in the fragment order
+ * of v_mfma_f32_16x16x32_bf16 (genpose_amd/weights.py: pack_bf16x9 - [c1 / 32][c2 / 16][3][64][8] and [c2 / 32][c3 / 16][3][64][8] bf16);
+ * bias2 [c2], bias3 [c3], channel order as trained.  b * np * ns must be a multiple of 32; GP_EINVAL (nothing launched) for any other shape,
+ * a null pointer or offsets that are not multiples of four floats; b = 0 returns GP_OK.  What an agent of the PC sampler runs for this
+ * level by default (genpose_amd/config.py: encoder_level1); the fp32 entry points above stay selectable. */
+int gp_sa_lds_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c3, const float *xyz, const float *new_xyz, const int32_t *idx, const float *z,
+                     int zstride, int zoff, const float *wxyz, const float *bias1, const void *w2_x9, const float *bias2, const void *w3_x9,
+                     const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s);
+
 /* The GroupAll level of the light encoder (n = 128 points, cin = 512 features, c1 = 256, c3 = 512, c2 = 256 | 384 per scale) in ONE launch
  * with all three dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (csrc/sa_groupall_bf16x9.hip; the arithmetic of
  * gp_sa_pre_mlp_max_bf16x9): the job of gp_point_linear (hoisted feature half of layer 1) + gp_sa_pre_mlp_max_layout per scale, from
