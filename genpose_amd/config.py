@@ -44,39 +44,38 @@ DEFAULTS = dict(
 )
 
 
-def encoder_precision_of(cfg):
-    """The `precision` of Pointnet2EncoderHIP a namespace asks for (the reference's own namespace has neither field: the defaults).
-    encoder_precision 'f32' names the accuracy class; within it encoder_level2 picks the matrix pipe of grouping level 2."""
-    prec = getattr(cfg, "encoder_precision", "f32")
-    lvl2 = getattr(cfg, "encoder_level2", "auto")
-    if lvl2 not in ("auto", "bf16x9", "f32mfma"):
-        raise ValueError(f"encoder_level2 {lvl2!r}: 'auto', 'bf16x9' or 'f32mfma'")
-    if lvl2 == "auto":
+def _pipe_of(cfg, field):
+    """An `auto | bf16x9 | f32mfma` field (the reference's own namespace has none of them: 'auto'); 'auto' resolves by sampler mode: 'bf16x9'
+    for an agent of the fixed-step PC sampler, 'f32mfma' for every other."""
+    v = getattr(cfg, field, "auto")
+    if v not in ("auto", "bf16x9", "f32mfma"):
+        raise ValueError(f"{field} {v!r}: 'auto', 'bf16x9' or 'f32mfma'")
+    if v == "auto":
         mode = getattr(cfg, "sampler_mode", None) or ["ode"]
-        lvl2 = "bf16x9" if mode[0] == "pc" else "f32mfma"
-    return "bf16x9" if prec == "f32" and lvl2 == "bf16x9" else prec
+        v = "bf16x9" if mode[0] == "pc" else "f32mfma"
+    return v
+
+
+def encoder_precision_of(cfg):
+    """The `precision` of Pointnet2EncoderHIP a namespace asks for.  encoder_precision 'f32' names the accuracy class; within it
+    encoder_level2 picks the matrix pipe of grouping level 2."""
+    prec = getattr(cfg, "encoder_precision", "f32")
+    return "bf16x9" if _pipe_of(cfg, "encoder_level2") == "bf16x9" and prec == "f32" else prec
 
 
 def encoder_level1_of(cfg):
-    """The `level1` of Pointnet2EncoderHIP a namespace asks for (the reference's own namespace has no such field: 'auto')."""
-    lvl1 = getattr(cfg, "encoder_level1", "auto")
-    if lvl1 not in ("auto", "bf16x9", "f32mfma"):
-        raise ValueError(f"encoder_level1 {lvl1!r}: 'auto', 'bf16x9' or 'f32mfma'")
-    if lvl1 == "auto":
-        mode = getattr(cfg, "sampler_mode", None) or ["ode"]
-        lvl1 = "bf16x9" if mode[0] == "pc" else "f32mfma"
-    return lvl1
+    """The `level1` of Pointnet2EncoderHIP a namespace asks for."""
+    return _pipe_of(cfg, "encoder_level1")
 
 
 def encoder_level3_of(cfg):
-    """The `level3` of Pointnet2EncoderHIP a namespace asks for (the reference's own namespace has no such field: 'auto')."""
-    lvl3 = getattr(cfg, "encoder_level3", "auto")
-    if lvl3 not in ("auto", "bf16x9", "f32mfma"):
-        raise ValueError(f"encoder_level3 {lvl3!r}: 'auto', 'bf16x9' or 'f32mfma'")
-    if lvl3 == "auto":
-        mode = getattr(cfg, "sampler_mode", None) or ["ode"]
-        lvl3 = "bf16x9" if mode[0] == "pc" else "f32mfma"
-    return lvl3
+    """The `level3` of Pointnet2EncoderHIP a namespace asks for."""
+    return _pipe_of(cfg, "encoder_level3")
+
+
+def encoder_kwargs_of(cfg):
+    """The keyword arguments of Pointnet2EncoderHIP a namespace asks for."""
+    return dict(arith=getattr(cfg, "dist_arith", None), precision=encoder_precision_of(cfg), level1=encoder_level1_of(cfg), level3=encoder_level3_of(cfg))
 
 
 def get_config(**overrides):

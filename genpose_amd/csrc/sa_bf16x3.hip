@@ -225,11 +225,9 @@ extern "C" {
 int gp_sa_pre_mlp_max_bf16x3(int b, int n, int np, int ns, int c1, int c2, int c3, const float *xyz, const float *new_xyz, const int32_t *idx,
                              const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w2_split, const float *bias2,
                              const void *w3_split, const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s) {
-    if (b < 0 || n <= 0 || np <= 0 || !xyz || !new_xyz || !idx || !z || !wxyz || !bias1 || !w2_split || !bias2 || !w3_split || !bias3 || !out)
+    if (!gp_sa_rows::units_args_ok(b, n, np, ns, c1, c3, zstride, zoff, cout_total, cout_off,
+                                   {xyz, new_xyz, idx, z, wxyz, bias1, w2_split, bias2, w3_split, bias3, out}))
         return GP_EINVAL;
-    if ((cout_total & 3) || (cout_off & 3) || cout_off < 0 || cout_off + c3 > cout_total || (zstride & 3) || (zoff & 3) || zoff < 0 || zoff + c1 > zstride)
-        return GP_EINVAL;
-    if (((size_t)b * np * ns) % 32 || ((size_t)b * np * ns) / 32 > 0x3ffffffu) return GP_EINVAL;  // whole 32-row units, row indices in an int
     if (b == 0) return GP_OK;
     SABfArgs a{n, np, zstride, zoff, xyz, new_xyz, z, idx, wxyz, bias1, reinterpret_cast<const bf16x8 *>(w2_split), bias2,
                reinterpret_cast<const bf16x8 *>(w3_split), bias3, out, cout_total, cout_off};

@@ -240,11 +240,9 @@ extern "C" {
 int gp_sa_pre_mlp_max_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c3, const float *xyz, const float *new_xyz, const int32_t *idx,
                              const float *z, int zstride, int zoff, const float *wxyz, const float *bias1, const void *w23_x9, const float *bias2,
                              const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s) {
-    if (b < 0 || n <= 0 || np <= 0 || !xyz || !new_xyz || !idx || !z || !wxyz || !bias1 || !w23_x9 || !bias2 || !bias3 || !out) return GP_EINVAL;
-    if (c1 != SX_C1 || c2 != SX_C2 || c3 != SX_C3 || (ns != 16 && ns != 32)) return GP_EINVAL;  // grouping level 2
-    if ((cout_total & 3) || (cout_off & 3) || cout_off < 0 || cout_off + c3 > cout_total || (zstride & 3) || (zoff & 3) || zoff < 0 || zoff + c1 > zstride)
+    if (!gp_sa_rows::units_args_ok(b, n, np, ns, c1, c3, zstride, zoff, cout_total, cout_off, {xyz, new_xyz, idx, z, wxyz, bias1, w23_x9, bias2, bias3, out}))
         return GP_EINVAL;
-    if (((size_t)b * np * ns) % 32 || ((size_t)b * np * ns) / 32 > 0x3ffffffu) return GP_EINVAL;  // whole 32-row units, row indices in an int
+    if (c1 != SX_C1 || c2 != SX_C2 || c3 != SX_C3 || (ns != 16 && ns != 32)) return GP_EINVAL;  // grouping level 2
     if (b == 0) return GP_OK;
     const SAX9Args a{n, np, zstride, zoff, xyz, new_xyz, z, idx, wxyz, bias1, reinterpret_cast<const bf16x8 *>(w23_x9), bias2, bias3, out, cout_total, cout_off};
     return ns == 32 ? launch_bf16x9<32>(a, b, (hipStream_t)s) : launch_bf16x9<16>(a, b, (hipStream_t)s);

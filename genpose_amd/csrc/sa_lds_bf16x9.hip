@@ -201,11 +201,9 @@ extern "C" {
 int gp_sa_lds_bf16x9(int b, int n, int np, int ns, int c1, int c2, int c3, const float *xyz, const float *new_xyz, const int32_t *idx, const float *z,
                      int zstride, int zoff, const float *wxyz, const float *bias1, const void *w2_x9, const float *bias2, const void *w3_x9,
                      const float *bias3, float *out, int cout_total, int cout_off, gp_stream_t s) {
-    if (b < 0 || n <= 0 || np <= 0 || !xyz || !new_xyz || !idx || !z || !wxyz || !bias1 || !w2_x9 || !bias2 || !w3_x9 || !bias3 || !out)
+    if (!gp_sa_rows::units_args_ok(b, n, np, ns, c1, c3, zstride, zoff, cout_total, cout_off,
+                                   {xyz, new_xyz, idx, z, wxyz, bias1, w2_x9, bias2, w3_x9, bias3, out}))
         return GP_EINVAL;
-    if ((cout_total & 3) || (cout_off & 3) || cout_off < 0 || cout_off + c3 > cout_total || (zstride & 3) || (zoff & 3) || zoff < 0 || zoff + c1 > zstride)
-        return GP_EINVAL;
-    if (((size_t)b * np * ns) % 32 || ((size_t)b * np * ns) / 32 > 0x3ffffffu) return GP_EINVAL;  // whole 32-row units, row indices in an int
     const bool s0 = c1 == 64 && c2 == 64 && c3 == 128 && ns == 16, s1 = c1 == 64 && c2 == 96 && c3 == 128 && ns == 32;
     if (!s0 && !s1) return GP_EINVAL;  // grouping level 1 of the light / dense encoders
     if (b == 0) return GP_OK;

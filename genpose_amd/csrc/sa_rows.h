@@ -5,9 +5,24 @@
 // b3, out, cout_total, cout_off).  Rings, accumulator layouts, the buffering of the hoisted feature rows and the launchers stay with each
 // kernel; the prefetched indices and coordinates live in the caller's locals.
 #pragma once
+#include <initializer_list>
+
 #include "gp_common.h"
 
 namespace gp_sa_rows {
+
+// Host side: what the per-scale entry points of the three split-bf16 kernels require of their arguments before their own shape check -
+// every pointer present (`ptrs`: the kernel's operands), output and z columns float4-aligned and inside their rows, whole 32-row units
+// with row indices that fit an int.
+inline bool units_args_ok(int b, int n, int np, int ns, int c1, int c3, int zstride, int zoff, int cout_total, int cout_off,
+                          std::initializer_list<const void *> ptrs) {
+    if (b < 0 || n <= 0 || np <= 0) return false;
+    for (const void *p : ptrs)
+        if (!p) return false;
+    if ((cout_total & 3) || (cout_off & 3) || cout_off < 0 || cout_off + c3 > cout_total || (zstride & 3) || (zoff & 3) || zoff < 0 || zoff + c1 > zstride)
+        return false;
+    return !(((size_t)b * np * ns) % 32 || ((size_t)b * np * ns) / 32 > 0x3ffffffu);
+}
 
 // layer-1 rows (wx, wy, wz, b1), NB2 floats of the layer-2 bias and NB3 of the layer-3 bias -> LDS, by NTH threads (a count of 0: that bias
 // stays in the kernel's registers)

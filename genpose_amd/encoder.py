@@ -3,17 +3,32 @@
 forward(pts [B,N,3] f32 on the GPU) -> [B,1024].  Launch sequence per call (all on torch's current stream):
   1 x gp_fps_chain      FPS + gather for every level (one workgroup per cloud)
   L x gp_ball_query_msg both radii of a level in one pass
-  L x gp_point_linear   hoisted feature half of the first layer, once per source point (both scales)
-  2L x gp_sa_pre_mlp_max_layout  gather -> xyz half of layer 1 -> layers 2-3 on fp32 MFMA -> max-pool, per scale (register-chain kernels;
-                        the hidden-layer layout the weights were packed for, weights.SAScale); grouping level 2 (128-196-256) by default
-                        through gp_sa_pre_mlp_max_bf16x9: the same job with layers 2-3 as exact-product split bf16; under level1 =
-                        'bf16x9', from LEVEL1_BF16X9_MIN_CLOUDS clouds up, grouping level 1 (64-64/96-128) through gp_sa_lds_bf16x9: the
-                        same arithmetic with both layers' weights LDS-resident
-  1 + 2 x the same pair  GroupAll level: whole rounds of 256 clouds on the ring kernel (one cloud per workgroup), the rest on 32-row tiles
-                        (the tiles of a cloud combine by integer atomic max into a zeroed buffer); under level3 = 'bf16x9', from
-                        LEVEL3_BF16X9_MIN_CLOUDS clouds up, ONE gp_sa_groupall_bf16x9 instead: all three layers of both scales as
-                        exact-product split bf16 from the level-2 features (no hoisted GEMM, no zeroing)
+  then per level, what launch_plan(B) lists:
+  1 x gp_point_linear   hoisted feature half of the first layer, once per source point (both scales; not at level 0, which has no features)
+  1 x the scale's kernel, per scale: gather -> xyz half of layer 1 -> layers 2-3 -> max-pool
 Intermediate features stay point-major [B, n, C]; the reference's grouped [B,C+3,np,ns] tensors never exist.
+
+The kernels of a scale.  The constructor decides once which one serves each (level, scale) - the table `_plan`, reported by `sa_kernels` and
+`level3_kernel` - and forward() only looks the entry up.  Earlier rows win; a kernel with a minimum batch gives way to the fp32 kernel
+below it, with that kernel's bits:
+  name     entry point                asked for by         serves                                       minimum batch
+  bf16x3   gp_sa_pre_mlp_max_bf16x3   precision='bf16x3'   grouping levels 1.., BF16X3_SHAPES           -
+           OPT-IN, exploratory: layers 2-3 as three-term split products, fp32 accumulation (csrc/sa_bf16x3.hip; ~2^-17 relative per product)
+  bf16x9   gp_sa_pre_mlp_max_bf16x9   precision='bf16x9'   grouping level 2, BF16X9_SHAPES              -
+           layers 2-3 on the BF16 matrix pipe as exact-product split bf16: every operand hi + mid + lo, all nine products exact, fp32
+           accumulation - the fp32 kernels' error class (csrc/sa_bf16x9.hip)
+  bf16x9   gp_sa_lds_bf16x9           level1='bf16x9'      grouping level 1, LEVEL1_BF16X9_SHAPES       LEVEL1_BF16X9_MIN_CLOUDS
+           the same arithmetic with both layers' weights LDS-resident (csrc/sa_lds_bf16x9.hip)
+  bf16x9   gp_sa_groupall_bf16x9      level3='bf16x9'      the light encoder's GroupAll level, whole    LEVEL3_BF16X9_MIN_CLOUDS
+           ONE launch for the level: all three layers of both scales in that arithmetic, straight from the level-2 features - no hoisted GEMM,
+           no zeroing (csrc/sa_groupall_bf16x9.hip)
+  f32mfma  gp_sa_pre_mlp_max_layout   default              everything                                   -
+           layers 2-3 on the fp32 matrix pipe (register-chain kernels; the hidden-layer layout the weights were packed for, weights.SAScale).
+           GroupAll: whole rounds of 256 clouds on the ring kernel (one cloud per workgroup), the rest on 32-row tiles - the tiles of a cloud
+           combine by integer atomic max into a zeroed buffer
+The three per-scale split kernels work on whole 32-row units, so they serve a scale only where npoint * nsample is a multiple of 32, and a
+bf16x9 kernel only where the folded weights split exactly into three normal bf16 terms (weights.split_bf16x9) - for the GroupAll kernel all
+six matrices of the level.  Centres and neighbourhoods are unaffected by any of them.
 
 Points per cloud.  Any N >= the first level's npoint (512 in every shipped configuration) is served; fewer points than level 0 selects
 raise GenposeHipError (the reference would read past the cloud).  Only the grouping front end depends on N:
@@ -27,6 +42,7 @@ raise GenposeHipError (the reference would read past the cloud).  Only the group
             + 1) bytes fit 60 KiB, candidates from global memory beyond.  A single-scale level always takes the per-scale form.
 Levels 1.. see at most 512 source points, so they never leave the small-cloud kernels.  encode() captures whichever sequence applies.
 """
+import collections
 import ctypes
 import itertools
 import weakref
@@ -53,26 +69,23 @@ def _unpin_entry(key, ent):
         ws["_pins"] = ws.get("_pins", 1) - 1
 
 
+class _Kernel(collections.namedtuple("_Kernel", "name entry operands min_clouds fallback")):
+    """One entry of the launch plan.  name: what `sa_kernels` / `level3_kernel` report; entry: the C entry point; operands(): the weight
+    operands between bias1 and the output (device tensors, packed on first use); min_clouds: the encoder attribute that holds the smallest
+    batch the kernel serves, or None; fallback: the entry that serves smaller batches."""
+
+    def at(self, enc, B):
+        # (the threshold is read through the instance at call time: it can be set on one encoder)
+        return self.fallback if self.min_clouds is not None and B < getattr(enc, self.min_clouds) else self
+
+
 class Pointnet2EncoderHIP:
     def __init__(self, state_dict, device="cuda", params="light", prefix="pts_encoder.", arith=None, precision="f32", level3=None, level1=None):
         """arith: contraction convention of the squared distances in furthest point sampling and the ball queries ('A' | 'B' | 'C',
         config.DEFAULT_DIST_ARITH when None; include/genpose_hip.h GP_ARITH_*).
-        precision: 'f32' (default of this class): every dense layer on the fp32 matrix pipe.
-        'bf16x9' (what an agent of the PC sampler asks for by default, config.encoder_precision_of): grouping level 2 (128-196-256) on the
-        BF16 matrix pipe as exact-product split bf16 (csrc/sa_bf16x9.hip: every operand hi + mid + lo, all nine products exact, fp32
-        accumulation - the fp32 kernels' error class), every other dense layer on the fp32 matrix pipe; a scale whose folded weights do
-        not split exactly keeps the fp32 kernel (`sa_kernels` says which kernel serves each scale).
-        'bf16x3' (OPT-IN, exploratory, round 5): grouping levels 1 and 2 (64-64/96-128, 128-196-256) as three-term split products with
-        fp32 accumulation (csrc/sa_bf16x3.hip; ~2^-17 relative per product).  Centres and neighbourhoods are unaffected by any of them.
-        level3: the GroupAll level.  None / 'f32mfma' (default of this class): gp_point_linear + the fp32 ring / tile kernels.  'bf16x9'
-        (what an agent of the PC sampler asks for by default, config.encoder_level3_of): all three layers of both scales as exact-product
-        split bf16 in one launch (csrc/sa_groupall_bf16x9.hip) for batches of LEVEL3_BF16X9_MIN_CLOUDS clouds or more; where one of the
-        level's six folded matrices does not split exactly, or the level is not the light encoder's, it keeps the fp32 kernels
-        (`level3_kernel` says which serves it).
-        level1: grouping level 1 (64-64/96-128).  None / 'f32mfma' (default of this class): the fp32 kernels, bit for bit.  'bf16x9' (what an
-        agent of the PC sampler asks for by default, config.encoder_level1_of): layers 2-3 as exact-product split bf16 with LDS-resident
-        weights (csrc/sa_lds_bf16x9.hip) for batches of LEVEL1_BF16X9_MIN_CLOUDS clouds or more; a scale whose shape is not instantiated or
-        whose folded weights do not split exactly keeps the fp32 kernel (`sa_kernels[(1, i)]` says which serves scale i)."""
+        precision ('f32' | 'bf16x9' | 'bf16x3'), level1 and level3 (None / 'f32mfma' | 'bf16x9') ask for the split-bf16 kernels of the
+        module text's table; the defaults of this class are the fp32 kernels throughout, an agent's come from config.encoder_kwargs_of
+        (a PC-sampler agent asks for all three bf16x9 kernels)."""
         if precision not in ("f32", "bf16x3", "bf16x9"):
             raise ValueError(f"encoder precision {precision!r}: 'f32', 'bf16x9' or 'bf16x3'")
         if level3 not in (None, "f32mfma", "bf16x9"):
@@ -92,24 +105,32 @@ class Pointnet2EncoderHIP:
         self._ws = ShapeCache(self.MAX_WORKSPACES, can_evict=_unpinned)
         self._pass_graphs = ShapeCache(self.MAX_PASS_GRAPHS, on_evict=_unpin_entry)  # (no closure over self: no reference cycle)
         self._seen_once = ShapeCache(4 * self.MAX_PASS_GRAPHS)
-        # which kernel serves each (level, scale) of the grouping levels: 'f32mfma' | 'bf16x9' | 'bf16x3' (bf16x3 also needs whole 32-row
-        # units of the batch at hand, see forward)
-        self.level3_kernel = "bf16x9" if self.level3 == "bf16x9" and self.w.groupall_bf16x9_packs() is not None else "f32mfma"
-        self.sa_kernels = {}
+        # The launch plan: _plan[k][i] serves scale i of level k, _groupall the GroupAll level as a whole (its fp32 fallback = that level's
+        # _plan row behind gp_point_linear).  Rows in order of precedence, as in the module text.  All three per-scale split kernels need
+        # whole 32-row units, (B * npoint * nsample) % 32 == 0: decided here for any B as (npoint * nsample) % 32 == 0, which holds for
+        # every shape of the three tables under the light, dense and lighter configurations (every npoint is a multiple of 32).
+        self._plan = []
         for k, npnt in enumerate(self.cfg["npoints"]):
-            if npnt is None:
-                break
-            for i, sc in enumerate(self.w.levels[k]):
-                shape = (tuple(sc.couts), self.cfg["nsamples"][k][i])
-                name = "f32mfma"
-                if precision == "bf16x3" and k > 0 and shape in self.BF16X3_SHAPES:
-                    name = "bf16x3"
-                elif precision == "bf16x9" and k > 0 and shape in self.BF16X9_SHAPES and (npnt * shape[1]) % 32 == 0 and sc.bf16x9_packs() is not None:
-                    name = "bf16x9"
-                elif (self.level1 == "bf16x9" and k > 0 and shape in self.LEVEL1_BF16X9_SHAPES and (npnt * shape[1]) % 32 == 0
-                      and sc.bf16x9_lds_packs() is not None):
-                    name = "bf16x9"
-                self.sa_kernels[(k, i)] = name
+            row = []
+            for sc, ns in zip(self.w.levels[k], self.cfg["nsamples"][k]):
+                fp32 = _Kernel("f32mfma", "gp_sa_pre_mlp_max_layout", lambda sc=sc: sc.layers[1] + sc.layers[2], None, None)  # (w2, b2, w3, b3)
+                shape = (tuple(sc.couts), ns)
+                kern = fp32
+                if k > 0 and npnt is not None and (npnt * ns) % 32 == 0:
+                    if precision == "bf16x3" and shape in self.BF16X3_SHAPES:
+                        kern = _Kernel("bf16x3", "gp_sa_pre_mlp_max_bf16x3", sc.bf16x3_packs, None, None)
+                    elif precision == "bf16x9" and shape in self.BF16X9_SHAPES and sc.bf16x9_packs() is not None:
+                        kern = _Kernel("bf16x9", "gp_sa_pre_mlp_max_bf16x9", sc.bf16x9_packs, None, None)
+                    elif self.level1 == "bf16x9" and shape in self.LEVEL1_BF16X9_SHAPES and sc.bf16x9_lds_packs() is not None:
+                        kern = _Kernel("bf16x9", "gp_sa_lds_bf16x9", sc.bf16x9_lds_packs, "LEVEL1_BF16X9_MIN_CLOUDS", fp32)
+                row.append(kern)
+            self._plan.append(row)
+        self._groupall = None
+        if self.level3 == "bf16x9" and self.w.groupall_bf16x9_packs() is not None:
+            self._groupall = _Kernel("bf16x9", "gp_sa_groupall_bf16x9", self.w.groupall_bf16x9_packs, "LEVEL3_BF16X9_MIN_CLOUDS", tuple(self._plan[-1]))
+        # which kernel serves each (level, scale) of the grouping levels, and the GroupAll level: 'f32mfma' | 'bf16x9' | 'bf16x3'
+        self.sa_kernels = {(k, i): kern.name for k, row in enumerate(self._plan) if self.cfg["npoints"][k] is not None for i, kern in enumerate(row)}
+        self.level3_kernel = self._groupall.name if self._groupall is not None else "f32mfma"
 
     MAX_WORKSPACES = 12
     # batches from this many clouds up take the split-bf16 GroupAll kernel under level3 = 'bf16x9' (one 128-row item per CU and scale:
@@ -354,6 +375,26 @@ class Pointnet2EncoderHIP:
         ws = self.prepare_grouping(pts, defer_join=True)
         return self.forward(pts, grouping=ws), ws
 
+    def _whole_level(self, k, B):
+        """The kernel that serves all of level k in one launch for B clouds, or None: gp_point_linear + one kernel per scale."""
+        if self.cfg["npoints"][k] is None and self._groupall is not None and self._groupall.at(self, B) is self._groupall:
+            return self._groupall
+        return None
+
+    def launch_plan(self, B):
+        """The C entry points the set-abstraction levels of a pass over B clouds call, in launch order (what forward() issues after the
+        grouping front end, whose launches depend on N: module text).  Pure host logic: no device is touched."""
+        names = []
+        for k, row in enumerate(self._plan):
+            whole = self._whole_level(k, B)
+            if whole is not None:
+                names.append(whole.entry)
+                continue
+            if k > 0:  # (a level behind another has input features, and with them the hoisted half of layer 1: _workspace's `z`)
+                names.append("gp_point_linear")
+            names += [kern.at(self, B).entry for kern in row]
+        return names
+
     def forward(self, pts, return_intermediates=False, slot=0, centres_done=False, grouping=None):
         """grouping: workspace returned by prepare_grouping() of an encoder with the same grouping configuration, for the SAME
         clouds: its centres and neighbourhood indices are used instead of being recomputed."""
@@ -377,42 +418,29 @@ class Pointnet2EncoderHIP:
             if not centres_done:
                 self.sample_centres(pts, slot)
             self._ball_queries(ws, xyz0, B, N)
-        # ---- set abstraction levels
+        # ---- set abstraction levels: the launches launch_plan(B) lists
         xyz, feats, n, cin = xyz0, None, N, 0
         for k, npnt in enumerate(cfg["npoints"]):
             scales = self.w.levels[k]
             out = ws["feat"][k]
             cout_total = out.shape[-1]
+            if self._whole_level(k, B) is not None:
+                # GroupAll in one launch, straight from the level-2 features: every output column written whole (no hoisted rows, no zeroing)
+                wx9, offs = self._groupall.operands()
+                sargs = []
+                for i, sc in enumerate(scales):
+                    (_, b1), (_, b2), (_, b3) = sc.layers
+                    sargs += [sc.couts[1], ptr(wx9[offs[i]:]), ptr(sc.wxyz), ptr(b1), ptr(b2), ptr(b3), i * sc.couts[2]]
+                _lib.call(self._groupall.entry, B, n, cin, scales[0].couts[0], scales[0].couts[2], ptr(xyz), ptr(feats), *sargs, ptr(out), cout_total, st)
+                xyz, feats, n, cin = None, out, 1, cout_total
+                continue
             if npnt is None:
-                # GroupAll: same hoisted form - layer 1's feature half is one GEMM over all B*n points (both scales), the
-                # tiles of a cloud combine through an integer atomic max into the zeroed output
-                if self.level3_kernel == "bf16x9" and B >= self.LEVEL3_BF16X9_MIN_CLOUDS:
-                    # all three layers of both scales as exact-product split bf16, straight from the level-2 features: one launch, every
-                    # output column written whole (no hoisted rows, no zeroing)
-                    wx9, offs = self.w.groupall_bf16x9_packs()
-                    sargs = []
-                    for i, sc in enumerate(scales):
-                        (_, b1), (_, b2), (_, b3) = sc.layers
-                        sargs += [sc.couts[1], ptr(wx9[offs[i]:]), ptr(sc.wxyz), ptr(b1), ptr(b2), ptr(b3), i * sc.couts[2]]
-                    _lib.call("gp_sa_groupall_bf16x9", B, n, cin, scales[0].couts[0], scales[0].couts[2], ptr(xyz), ptr(feats), *sargs, ptr(out), cout_total, st)
-                    feats, n, cin = out, 1, cout_total
-                    break
+                # GroupAll is one neighbourhood of all n points around no centre; the tiles of a cloud combine through an integer atomic
+                # max into the zeroed output
                 out.zero_()
-                z = ws["z"][k]
-                zstride = sum(sc.couts[0] for sc in scales)
-                if z is not None:
-                    _lib.call("gp_point_linear", B * n, cin, zstride, ptr(feats), ptr(self.w.z_weights[k]), ptr(z), st)
-                off, zoff = 0, 0
-                for sc in scales:
-                    (w1, b1), (w2, b2), (w3, b3) = sc.layers
-                    _lib.call("gp_sa_pre_mlp_max_layout", sc.hidden_layout, B, n, 1, n, sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), None, None, ptr(z), zstride,
-                              zoff, ptr(sc.wxyz), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(out), cout_total, off, st)
-                    off += sc.couts[2]
-                    zoff += sc.couts[0]
-                feats, n, cin = out, 1, cout_total
-                break
-            new_xyz = src["new_xyz"][k]
-            nss = cfg["nsamples"][k]
+                new_xyz, npnt, nss, idx = None, 1, [n] * len(scales), [None] * len(scales)
+            else:
+                new_xyz, nss, idx = src["new_xyz"][k], cfg["nsamples"][k], src["bq"][k]
             # first layer hoisted: feature half once per source point, xyz half while gathering (csrc/sa_mlp.hip)
             z = ws["z"][k]
             zstride = sum(sc.couts[0] for sc in scales)
@@ -426,33 +454,10 @@ class Pointnet2EncoderHIP:
                     src.pop("_join")
             off, zoff = 0, 0
             for i, sc in enumerate(scales):
-                (w1, b1), (w2, b2), (w3, b3) = sc.layers
-                if (self.precision == "bf16x3" and z is not None and (tuple(sc.couts), nss[i]) in self.BF16X3_SHAPES
-                        and (B * npnt * nss[i]) % 32 == 0):
-                    w2s, b2s, w3s, b3s = sc.bf16x3_packs()
-                    _lib.call("gp_sa_pre_mlp_max_bf16x3", B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(src["bq"][k][i]), ptr(z),
-                              zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(w2s), ptr(b2s), ptr(w3s), ptr(b3s), ptr(out), cout_total, off, st)
-                    off += sc.couts[2]
-                    zoff += sc.couts[0]
-                    continue
-                if self.sa_kernels[(k, i)] == "bf16x9" and (tuple(sc.couts), nss[i]) in self.LEVEL1_BF16X9_SHAPES:
-                    if B >= self.LEVEL1_BF16X9_MIN_CLOUDS:
-                        w2x9, b2x9, w3x9, b3x9 = sc.bf16x9_lds_packs()
-                        _lib.call("gp_sa_lds_bf16x9", B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(src["bq"][k][i]), ptr(z),
-                                  zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(w2x9), ptr(b2x9), ptr(w3x9), ptr(b3x9), ptr(out), cout_total, off, st)
-                        off += sc.couts[2]
-                        zoff += sc.couts[0]
-                        continue
-                elif self.sa_kernels[(k, i)] == "bf16x9":
-                    wx9, b2x9, b3x9 = sc.bf16x9_packs()
-                    _lib.call("gp_sa_pre_mlp_max_bf16x9", B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(src["bq"][k][i]), ptr(z),
-                              zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(wx9), ptr(b2x9), ptr(b3x9), ptr(out), cout_total, off, st)
-                    off += sc.couts[2]
-                    zoff += sc.couts[0]
-                    continue
-                _lib.call("gp_sa_pre_mlp_max_layout", sc.hidden_layout, B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz),
-                          ptr(src["bq"][k][i]), ptr(z), zstride, zoff, ptr(sc.wxyz), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(out),
-                          cout_total, off, st)
+                kern = self._plan[k][i].at(self, B)
+                lead = (sc.hidden_layout,) if kern.entry == "gp_sa_pre_mlp_max_layout" else ()
+                _lib.call(kern.entry, *lead, B, n, npnt, nss[i], sc.couts[0], sc.couts[1], sc.couts[2], ptr(xyz), ptr(new_xyz), ptr(idx[i]), ptr(z), zstride, zoff,
+                          ptr(sc.wxyz), ptr(sc.layers[0][1]), *map(ptr, kern.operands()), ptr(out), cout_total, off, st)
                 off += sc.couts[2]
                 zoff += sc.couts[0]
             xyz, feats, n, cin = new_xyz, out, npnt, cout_total

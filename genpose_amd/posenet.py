@@ -14,7 +14,7 @@ and every cloud owns K consecutive pose rows - this is how PoseNet.pred_func avo
 """
 import torch
 
-from .config import encoder_level1_of, encoder_level3_of, encoder_precision_of
+from .config import encoder_kwargs_of
 from .encoder import Pointnet2EncoderHIP
 from .lru import ShapeCache
 from .pointnet_encoder import ACT_RELU, PointNetEncoderHIP, dense_rows
@@ -60,17 +60,14 @@ class GFObjectPose:
         sd = {k[7:] if k.startswith("module.") else k: v for k, v in state_dict.items()}
         params = getattr(self.cfg, "pointnet2_params", "light")
         if self.cfg.pts_encoder == "pointnet_and_pointnet2":
-            self.pts_pointnet2_encoder = Pointnet2EncoderHIP(sd, self.device, params, prefix="pts_pointnet2_encoder.", arith=getattr(self.cfg, "dist_arith", None),
-                                                             precision=encoder_precision_of(self.cfg), level3=encoder_level3_of(self.cfg),
-                                                             level1=encoder_level1_of(self.cfg))
+            self.pts_pointnet2_encoder = Pointnet2EncoderHIP(sd, self.device, params, prefix="pts_pointnet2_encoder.", **encoder_kwargs_of(self.cfg))
             self.pts_pointnet_encoder = PointNetEncoderHIP(sd, self.device, prefix="pts_pointnet_encoder.")
             W, b = sd["fusion_layer.weight"].detach().float().cpu().contiguous(), sd["fusion_layer.bias"].detach().float().cpu().contiguous()
             if tuple(W.shape) != (1024, 2048) or b.numel() != 1024:
                 raise ValueError(f"fusion_layer.weight is {tuple(W.shape)}, expected (1024, 2048)")
             self.fusion_layer = (W.to(self.device), b.to(self.device))
         else:
-            self.pts_encoder = Pointnet2EncoderHIP(sd, self.device, params, arith=getattr(self.cfg, "dist_arith", None), precision=encoder_precision_of(self.cfg),
-                                                   level3=encoder_level3_of(self.cfg), level1=encoder_level1_of(self.cfg))
+            self.pts_encoder = Pointnet2EncoderHIP(sd, self.device, params, **encoder_kwargs_of(self.cfg))
         self.pose_score_net = ScoreNetHIP(sd, self.device)
         self._samplers.clear()
         return self

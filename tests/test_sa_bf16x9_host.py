@@ -3,12 +3,12 @@ per-element definition, the exactness of the split on the level-2 weights of the
 that does not split, and gp_sa_pre_mlp_max_bf16x9's declaration / export / ctypes signature."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
 from oracle import genpose_oracle as go
+from sa_split_host import prototype
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CKPT = os.path.join(ROOT, "tests", "golden", "trained", "ckpt_score.pth")
@@ -79,23 +79,15 @@ def test_a_weight_that_does_not_split_gives_no_pack():
     assert w.levels[2][1].bf16x9_packs() is None and w.levels[2][0].bf16x9_packs() is not None
 
 
-def _prototype(name):
-    hdr = open(os.path.join(ROOT, "include", "genpose_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, f"{name} is not declared in include/genpose_hip.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
 def test_signature_matches_header_and_is_the_bf16x3_one_with_one_weight_stream():
     from genpose_amd import _lib
-    args = _prototype("gp_sa_pre_mlp_max_bf16x9")
+    args = prototype("gp_sa_pre_mlp_max_bf16x9")
     sig = _lib.SIGNATURES["gp_sa_pre_mlp_max_bf16x9"]
     assert len(sig) == len(args)
     for decl, ct in zip(args, sig):
         want = "pointer" if "*" in decl or decl.startswith("gp_stream_t") else "int"
         assert want == ("int" if ct is ctypes.c_int else "pointer"), (decl, ct)
-    x3 = _prototype("gp_sa_pre_mlp_max_bf16x3")
+    x3 = prototype("gp_sa_pre_mlp_max_bf16x3")
     assert args == [a.replace("w2_split", "w23_x9") for a in x3 if a != "const void *w3_split"]
 
 

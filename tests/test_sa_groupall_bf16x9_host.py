@@ -2,15 +2,12 @@
 pack_bf16x9's fragments and against the weights themselves, the all-or-nothing fallback of the level, the config field, and
 gp_sa_groupall_bf16x9's declaration / export / ctypes signature."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from oracle import genpose_oracle as go
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from sa_split_host import prototype
 
 
 def _weights(c2, seed=3):
@@ -96,17 +93,9 @@ def test_level_pack_is_both_scales_or_nothing():
         assert EncoderWeights(bad, "cpu").groupall_bf16x9_packs() is None, key
 
 
-def _prototype(name):
-    hdr = open(os.path.join(ROOT, "include", "genpose_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, f"{name} is not declared in include/genpose_hip.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
 def test_signature_matches_header_and_library_exports_it():
     from genpose_amd import _lib, build
-    args = _prototype("gp_sa_groupall_bf16x9")
+    args = prototype("gp_sa_groupall_bf16x9")
     sig = _lib.SIGNATURES["gp_sa_groupall_bf16x9"]
     assert len(sig) == len(args) == 24
     for decl, ct in zip(args, sig):

@@ -2,29 +2,14 @@
 the weights themselves in pack_bf16x9's k order, the per-scale fallback, the config field, and gp_sa_lds_bf16x9's declaration / export /
 ctypes signature."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from oracle import genpose_oracle as go
+from sa_split_host import k_of, prototype, terms
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C2 = (64, 96)
-
-
-def _k_of(kb, g, e):
-    """Input channel of element e of lane group g in k-block kb: two consecutive D fragments of the previous layer (pack_bf16x9, chain order)."""
-    return 32 * kb + (4 * g + e if e < 4 else 16 + 4 * g + e - 4)
-
-
-def _terms(W):
-    hi = W.to(torch.bfloat16)
-    r = W - hi.float()
-    mid = r.to(torch.bfloat16)
-    lo = (r - mid.float()).to(torch.bfloat16)
-    return hi, mid, lo
 
 
 def test_packs_have_the_documented_shapes_and_hold_the_three_terms_in_k_order():
@@ -39,7 +24,7 @@ def test_packs_have_the_documented_shapes_and_hold_the_three_terms_in_k_order():
         assert w2.dtype == w3.dtype == torch.int16 and w2.is_contiguous() and w3.is_contiguous()
         assert b2.shape == (C2[i],) and b3.shape == (128,) and torch.equal(b2, B2.float()) and torch.equal(b3, B3.float())
         for pack, W in ((w2, W2), (w3, W3)):
-            terms = _terms(W.float())
+            hml = terms(W.float())
             nkb, nch = pack.shape[0], pack.shape[1]
             # spot checks: all four lane groups, both halves of a k-block (e < 4, e >= 4), first / last k-block and chunk
             for kb in (0, nkb - 1):
@@ -48,7 +33,7 @@ def test_packs_have_the_documented_shapes_and_hold_the_three_terms_in_k_order():
                         n, g = lane % 16, lane // 16
                         for e in (0, 3, 4, 7):
                             for t in range(3):
-                                want = terms[t][16 * nc + n, _k_of(kb, g, e)].view(torch.int16)
+                                want = hml[t][16 * nc + n, k_of(kb, g, e)].view(torch.int16)
                                 assert pack[kb, nc, t, lane, e] == want, (kb, nc, t, lane, e)
             # and whole: the three terms of every fragment element sum to the weight pack_bf16x9's k order names, each weight once
             back = (pack[:, :, 0].view(torch.bfloat16).double() + pack[:, :, 1].view(torch.bfloat16).double()) + pack[:, :, 2].view(torch.bfloat16).double()
@@ -77,17 +62,9 @@ def test_subnormal_weight_gives_none_for_that_scale_only():
     assert EncoderWeights(sd, "cpu").levels[2][0].bf16x9_lds_packs() is None
 
 
-def _prototype(name):
-    hdr = open(os.path.join(ROOT, "include", "genpose_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, f"{name} is not declared in include/genpose_hip.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
 def test_signature_matches_header_and_library_exports_it():
     from genpose_amd import _lib, build
-    args = _prototype("gp_sa_lds_bf16x9")
+    args = prototype("gp_sa_lds_bf16x9")
     sig = _lib.SIGNATURES["gp_sa_lds_bf16x9"]
     assert len(sig) == len(args) == 23
     names = [a.split()[-1].lstrip("*") for a in args]
@@ -99,7 +76,7 @@ def test_signature_matches_header_and_library_exports_it():
     assert "sa_lds_bf16x9.hip" in build.SOURCES
     build.build()
     assert hasattr(ctypes.CDLL(_lib.SO_PATH), "gp_sa_lds_bf16x9")
-    assert _prototype("gp_sa_pre_mlp_max_bf16x9")  # the level-2 entry point keeps its own name
+    assert prototype("gp_sa_pre_mlp_max_bf16x9")  # the level-2 entry point keeps its own name
 
 
 def test_config_field_resolves_by_sampler():
