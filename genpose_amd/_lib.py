@@ -101,6 +101,11 @@ SIGNATURES = {
     "gp_dpm2m_step_plan_model": [c_int] * 8 + [NETP] + [P] * 9 + [P],
     "gp_heun_solve_tile_model": [c_int] * 7 + [NETP] + [P] * 9 + [P],
     "gp_dpm2m_solve_tile_model": [c_int] * 7 + [NETP] + [P] * 9 + [P],
+    "gp_heun_step_classes": [c_int] * 8 + [NETP] + [P] * 9 + [c_int, P] + [P],
+    "gp_dpm2m_step_classes": [c_int] * 8 + [NETP] + [P] * 9 + [c_int, P] + [P],
+    "gp_heun_solve_classes": [c_int] * 7 + [NETP] + [P] * 9 + [c_int, P] + [P],
+    "gp_dpm2m_solve_classes": [c_int] * 7 + [NETP] + [P] * 9 + [c_int, P] + [P],
+    "gp_track_start_classes": [c_int, c_int, P, P, c_int] + [P] * 6 + [c_int, P],
     "gp_heun_likelihood_launches": [c_int],
     "gp_heun_likelihood_step": [c_int] * 4 + [NETP] + [P] * 9 + [P],
     "gp_pc_step_grouped": [c_int, c_int, c_int, c_int, c_int, NETP] + [P] * 11 + [P],

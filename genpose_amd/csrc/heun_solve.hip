@@ -28,15 +28,20 @@ using namespace gp_trunk;
 // whole trunk (256 VGPRs and up to 118 spilled registers per lane, against the per-launch kernels' 128 - 184 and none).
 __device__ __forceinline__ void opaque(const float *&p) { asm volatile("" : "+s"(p)); }
 
-template <int P, int SOLVER, int MODEL = 0>
-__device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) {
+// Args = HeunClsArgs (heun_solve_classes_kernel, dpm2m_solve_classes_kernel; gp_*_solve_classes): SCHEDULE CLASSES (pc_rows.h), as
+// heun_step_tile has them - the row thread's schedule rows (sigma_prev among them) are its cloud's class's, the trunk adds the class's time
+// embedding per cloud, the kind and DPM2M's first-step flag come from class 0.
+template <int P, int SOLVER, int MODEL = 0, class Args = HeunArgs>
+__device__ __forceinline__ void heun_solve(Args a, const gp_scorenet &net0) {
     static_assert(MODEL == 0 || P == gp_bwd::DP, "the backward pass runs on 16-row tiles");
+    static_assert(MODEL == 0 || std::is_same<Args, HeunArgs>::value, "schedule classes: the score model");
     using L = TrunkLds<P, MODEL == 1>;
     constexpr int SROW = fixed_sched_row<SOLVER>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int row0 = blockIdx.x * P, tid = threadIdx.x, last = a.nsteps;
     const bool live = row0 + tid < a.nrows;
     const int r = live ? row0 + tid : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
+    const int rcls = heun_row_class(a, r);           // the row's schedule class (0 without classes)
     float *mine = lds + (MODEL == 1 ? gp_bwd::LDS_FLOATS : L::TOTAL) + tid;  // this row thread's slot: x_i at [j * P], d_i at [(9 + j) * P], the cloud centre at [(18 + j) * P]
     if (tid < P) {
 #pragma unroll
@@ -55,8 +60,8 @@ __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) 
         TrunkPre<P> pre;
         float sigma = 1.f;
         if (l < last) {
-            trunk_begin<P>(net, pre, a.cvec, tvec, row0, a.nrows, a.kcand);
-            sigma = a.sched[(size_t)l * SROW + 0];  // requested now, used after the trunk
+            trunk_begin<P>(net, pre, a.cvec, tvec, row0, a.nrows, a.kcand, heun_times(a));
+            sigma = heun_sched_row<SROW>(a, rcls, l)[0];  // requested now, used after the trunk
             gp_pin(sigma);
         }
         if (tid < P) {
@@ -64,15 +69,15 @@ __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) 
 #pragma unroll
             for (int j = 0; j < 9; ++j) ev[j] = mine[j * P];
             if (l > 0) {
-                const float *sc = a.sched + (size_t)l * SROW;
-                const int kind = (int)sc[3];
+                const float *sc0 = a.sched + (size_t)l * SROW, *sc = heun_sched_row<SROW>(a, rcls, l);  // control flow from class 0
+                const int kind = (int)sc0[3];
                 const float c = sc[1], h = sc[2];
                 // the previous index's f_theta (all of trunk_ftheta's barriers are behind us); the chain stores this quotient and reloads it
                 // (MODEL 1: the previous index's score itself, in the backward pass's output rows)
                 const float *F = MODEL == 1 ? lds + gp_bwd::OFF_U + tid * gp_bwd::LDS_OUT : lds + L::OFF_H1 + tid * L::LDH;
                 float gr[9], dv[9];
                 if constexpr (SOLVER == SOLVER_DPM2M) {
-                    const bool has_d = (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) && sc[5] != 0.f;
+                    const bool has_d = (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) && sc0[5] != 0.f;
 #pragma unroll
                     for (int j = 0; j < 9; ++j) {
                         gr[j] = MODEL == 1 ? F[j] : F[j] / (sigma_prev + 1e-7f);
@@ -119,7 +124,7 @@ __device__ __forceinline__ void heun_solve(HeunArgs a, const gp_scorenet &net0) 
         if constexpr (MODEL == 1)
             gp_bwd::score_vjp_tile<gp_bwd::ENERGY>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre, sigma);  // (ends on a barrier too)
         else
-            trunk_ftheta<P>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre);  // (ends on a barrier: f_theta is visible to the row threads)
+            trunk_ftheta<P, false, TrunkNoEmit, false, (P == 48)>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre, TrunkNoEmit(), 0, heun_times(a));  // (ends on a barrier: f_theta is visible to the row threads)
         sigma_prev = sigma;
     }
 }
@@ -132,6 +137,14 @@ template <int P, int MODEL = 0>
 __global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_solve_kernel(HeunArgs a, const gp_scorenet net0) {
     heun_solve<P, SOLVER_DPM2M, MODEL>(a, net0);
 }
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_solve_classes_kernel(HeunClsArgs a, const gp_scorenet net0) {
+    heun_solve<P, SOLVER_HEUN, 0>(a, net0);
+}
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_solve_classes_kernel(HeunClsArgs a, const gp_scorenet net0) {
+    heun_solve<P, SOLVER_DPM2M, 0>(a, net0);
+}
 
 // the trunk's block and 21 floats per row behind it
 template <int P>
@@ -143,14 +156,21 @@ template <int SOLVER, int P, int MODEL = 0>
 constexpr auto solve_kernel = heun_solve_kernel<P, MODEL>;
 template <int P, int MODEL>
 constexpr auto solve_kernel<SOLVER_DPM2M, P, MODEL> = dpm2m_solve_kernel<P, MODEL>;
+template <int SOLVER, int P>
+constexpr auto solve_classes_kernel = heun_solve_classes_kernel<P>;
+template <int P>
+constexpr auto solve_classes_kernel<SOLVER_DPM2M, P> = dpm2m_solve_classes_kernel<P>;
 
-// A whole solve as one launch (gp_heun_solve_tile, gp_dpm2m_solve_tile and their _model forms: model 1 on plan 16 only).
-template <int SOLVER>
+// A whole solve as one launch (gp_heun_solve_tile, gp_dpm2m_solve_tile and their _model forms: model 1 on plan 16 only; CLASSES:
+// gp_heun_solve_classes, gp_dpm2m_solve_classes - schedule classes, the score model).
+template <int SOLVER, bool CLASSES = false>
 int solve_tile(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net, const float *cvec, const float *tvec_all,
-               const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj, hipStream_t st) {
+               const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj, hipStream_t st, int ncls = 1,
+               const int *cls = nullptr) {
     if ((model != 0 && model != 1) || ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || !net || !cvec || !tvec_all || !sched || !centre || !x ||
         !d || !score || !out)
         return GP_EINVAL;
+    if (CLASSES && (model != 0 || ncls < 1 || ncls > GP_MAX_SCHED_CLASSES || !cls)) return GP_EINVAL;
     const long long rg = (long long)nclouds_per_group * k, R = ngroups * rg;
     if (R > 0x7fffffffLL / 9) return GP_EINVAL;  // row and element indices are ints up to R * 9
     if (R == 0) return GP_OK;
@@ -166,7 +186,10 @@ int solve_tile(int model, int tile, int ngroups, int nclouds_per_group, int k, i
     return gp_with_tile(P, [&](auto tile_rows) {  // (GP_EINVAL for plan 128: the chain form keeps its per-launch kernels)
         constexpr int T = decltype(tile_rows)::value;
         const int nwg = ngroups * (int)((rg + T - 1) / T);
-        return gp_launch<solve_kernel<SOLVER, T>>(dim3(nwg), dim3(TrunkCfg<T>::NT), solve_lds_bytes<T>(), st, a, *net);
+        if constexpr (CLASSES)
+            return gp_launch<solve_classes_kernel<SOLVER, T>>(dim3(nwg), dim3(TrunkCfg<T>::NT), solve_lds_bytes<T>(), st, heun_cls_args(a, ncls, cls, nsteps + 1), *net);
+        else
+            return gp_launch<solve_kernel<SOLVER, T>>(dim3(nwg), dim3(TrunkCfg<T>::NT), solve_lds_bytes<T>(), st, a, *net);
     });
 }
 
@@ -182,6 +205,20 @@ extern "C" int gp_dpm2m_solve_tile(int tile, int ngroups, int nclouds_per_group,
                                    const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
                                    gp_stream_t s) {
     return solve_tile<SOLVER_DPM2M>(0, tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj, (hipStream_t)s);
+}
+
+extern "C" int gp_heun_solve_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                                     const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                                     float *out, float *traj, int ncls, const int *cls, gp_stream_t s) {
+    return solve_tile<SOLVER_HEUN, true>(model, tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                         (hipStream_t)s, ncls, cls);
+}
+
+extern "C" int gp_dpm2m_solve_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                                      const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                                      float *out, float *traj, int ncls, const int *cls, gp_stream_t s) {
+    return solve_tile<SOLVER_DPM2M, true>(model, tile, ngroups, nclouds_per_group, k, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score, out, traj,
+                                          (hipStream_t)s, ncls, cls);
 }
 
 extern "C" int gp_heun_solve_tile_model(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,

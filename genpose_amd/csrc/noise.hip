@@ -32,23 +32,53 @@ __global__ __launch_bounds__(256) void pc_noise_fill_kernel(const uint32_t *__re
 // The tracker's warm start, one thread per row (cloud i, candidate c): x0 = init_i + sigma * z, the product and the sum rounded separately (a
 // host restatement in fp32 gives the same bits).  init_i = [R[:,0], R[:,1], t - centre[i]] of a row-major 4x4: the previous frame's
 // aggregated pose src[i] when src[i] >= 0, else the cloud's own fallback (the jittered ground truth).
-__global__ __launch_bounds__(256) void track_warm_start_kernel(int n, int k, const uint32_t *__restrict__ seed_state, const float *__restrict__ sigma,
-                                                               const float *__restrict__ prev_sRT, const int *__restrict__ src,
-                                                               const float *__restrict__ fallback_sRT, const float *__restrict__ centre,
-                                                               float *__restrict__ x0) {
+// CLASSES (track_start_classes_kernel, gp_track_start_classes): `sigma` is the solve's schedule block, class c's sigma(T0_c) at
+// sigma[c * class_stride].  A cloud without a predecessor is ACQUIRED when `acquire` is set: x0 = sigma_1 * z, the pure prior (samplers.py:180
+// with init_x = None) on the same draw, and no pose is read for it.  The first row of every cloud writes the cloud's class for the solve.
+template <bool CLASSES>
+__device__ __forceinline__ void track_start_row(int n, int k, const uint32_t *__restrict__ seed_state, const float *__restrict__ sigma, int class_stride,
+                                                const float *__restrict__ prev_sRT, const int *__restrict__ src, const float *__restrict__ fallback_sRT,
+                                                const float *__restrict__ centre, float *__restrict__ x0, int *__restrict__ cls_out, int acquire) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)n * k) return;
     const int i = (int)(e / k);
     const int sp = src[i];
+    auto draw = [&](float (&z)[9]) {  // the prior's draw of this row
+        const gp_philox::Seed sd = gp_philox::load_seed(seed_state);
+        gp_philox::draw9(sd, gp_philox::PRIOR_STEP, gp_philox::STREAM_LANGEVIN, sd.row_base + (uint64_t)e, z);
+    };
+    if constexpr (CLASSES) {
+        const bool prior = acquire && sp < 0;
+        if (e == (long long)i * k) cls_out[i] = prior ? 1 : 0;
+        if (prior) {
+            float z[9];
+            draw(z);
+            const float s1 = sigma[class_stride];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) x0[e * 9 + j] = __fmul_rn(s1, z[j]);
+            return;
+        }
+    }
     const float *m = sp >= 0 ? prev_sRT + (size_t)sp * 16 : fallback_sRT + (size_t)i * 16;
     const float *cp = centre + (size_t)i * 3;
     const float init[9] = {m[0], m[4], m[8], m[1], m[5], m[9], m[3] - cp[0], m[7] - cp[1], m[11] - cp[2]};
-    const gp_philox::Seed sd = gp_philox::load_seed(seed_state);
     float z[9];
-    gp_philox::draw9(sd, gp_philox::PRIOR_STEP, gp_philox::STREAM_LANGEVIN, sd.row_base + (uint64_t)e, z);
+    draw(z);
     const float sg = *sigma;
 #pragma unroll
     for (int j = 0; j < 9; ++j) x0[e * 9 + j] = __fadd_rn(init[j], __fmul_rn(sg, z[j]));
+}
+__global__ __launch_bounds__(256) void track_warm_start_kernel(int n, int k, const uint32_t *__restrict__ seed_state, const float *__restrict__ sigma,
+                                                               const float *__restrict__ prev_sRT, const int *__restrict__ src,
+                                                               const float *__restrict__ fallback_sRT, const float *__restrict__ centre,
+                                                               float *__restrict__ x0) {
+    track_start_row<false>(n, k, seed_state, sigma, 0, prev_sRT, src, fallback_sRT, centre, x0, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void track_start_classes_kernel(int n, int k, const uint32_t *__restrict__ seed_state, const float *__restrict__ sched,
+                                                                  int class_stride, const float *__restrict__ prev_sRT, const int *__restrict__ src,
+                                                                  const float *__restrict__ fallback_sRT, const float *__restrict__ centre,
+                                                                  float *__restrict__ x0, int *__restrict__ cls_out, int acquire) {
+    track_start_row<true>(n, k, seed_state, sched, class_stride, prev_sRT, src, fallback_sRT, centre, x0, cls_out, acquire);
 }
 
 // the prior's draws as a buffer: z_out [nrows][9], the row of the launch is row0 + r
@@ -97,6 +127,18 @@ int gp_track_warm_start(int n, int k, const void *seed_state, const float *sigma
     if ((rows + 255) / 256 > 0x7fffffffLL) return GP_EINVAL;
     hipLaunchKernelGGL(track_warm_start_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)s, n, k, (const uint32_t *)seed_state, sigma,
                        prev_sRT, src, fallback_sRT, centre, x0);
+    return gp_launch_status();
+}
+
+int gp_track_start_classes(int n, int k, const void *seed_state, const float *sched, int class_stride, const float *prev_sRT, const int *src,
+                           const float *fallback_sRT, const float *centre, float *x0, int *cls_out, int acquire, gp_stream_t s) {
+    if (n < 0 || k <= 0 || class_stride < 1 || !seed_state || !sched || !prev_sRT || !src || (!fallback_sRT && !acquire) || !centre || !x0 || !cls_out)
+        return GP_EINVAL;
+    const long long rows = (long long)n * k;
+    if (rows == 0) return GP_OK;
+    if ((rows + 255) / 256 > 0x7fffffffLL) return GP_EINVAL;
+    hipLaunchKernelGGL(track_start_classes_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)s, n, k, (const uint32_t *)seed_state, sched,
+                       class_stride, prev_sRT, src, fallback_sRT, centre, x0, cls_out, acquire);
     return gp_launch_status();
 }
 

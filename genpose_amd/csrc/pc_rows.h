@@ -77,6 +77,33 @@ static inline HeunArgs heun_args(int nrows, int k, int launch, int last_launch, 
     a.x = x, a.d = d, a.score = score, a.out = out, a.traj = traj;
     return a;
 }
+// SCHEDULE CLASSES (the tile kernels heun_step_tile / heun_solve with HeunClsArgs; gp_*_step_classes, gp_*_solve_classes): a solve whose clouds
+// start from different times in the same launches.  `cls [clouds]` gives every cloud's class, clamped into [0, ncls - 1] on the device;
+// sched is [ncls][launches][row] and tvec_all [ncls][N+1][768].  Row r reads its cloud's class's schedule row (the score's divisor and the
+// update's coefficients) and adds that class's time embedding; the launch kind - and DPM2M's "there is a previous denoiser" - is read from
+// class 0 (the host keeps the kind column identical in every class), so control flow stays uniform and a row's bits are those of a uniform
+// solve on its class's tables.
+struct HeunClsArgs : HeunArgs {
+    const int *cls;  // [clouds]
+    int ncls;
+    int tstride;     // floats between two classes' blocks of tvec_all: (N + 1) * 768
+};
+static inline HeunClsArgs heun_cls_args(const HeunArgs &u, int ncls, const int *cls, int ntimes) {
+    HeunClsArgs a;
+    static_cast<HeunArgs &>(a) = u;
+    a.cls = cls, a.ncls = ncls, a.tstride = ntimes * HEADS;
+    return a;
+}
+// how a row's cloud picks its time embedding, row r's class, and the schedule row (SROW floats) of launch l for a class
+__device__ __forceinline__ TrunkOneTime heun_times(const HeunArgs &) { return TrunkOneTime(); }
+__device__ __forceinline__ TrunkClassTime heun_times(const HeunClsArgs &a) { return TrunkClassTime{a.cls, a.ncls, (size_t)a.tstride}; }
+__device__ __forceinline__ int heun_row_class(const HeunArgs &, int) { return 0; }
+__device__ __forceinline__ int heun_row_class(const HeunClsArgs &a, int r) { return heun_times(a).cloud_class(r / a.kcand); }
+template <int SROW>
+__device__ __forceinline__ const float *heun_sched_row(const HeunArgs &a, int c, int l) {
+    return a.sched + ((size_t)c * (a.nsteps + 1) + l) * SROW;
+}
+
 // The DPM-Solver++(2M) fixed-step solver (dpm2m_update_row, score_trunk.h) runs on the same launch shape, arguments and buffers: SOLVER
 // below is a template value of the kernels' shared code, HeunArgs serve both.  With N steps there are N + 1 launches (+ 1 with denoise):
 // launch 0 evaluates score(x_0, t_0); launch i = 1 .. N forms x_i from the stored score, x_{i-1} and D_{i-2}, stores x_i, D_{i-1} (in `d`,

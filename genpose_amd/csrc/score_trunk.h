@@ -63,11 +63,28 @@ struct TrunkPreT {
 template <int P>
 using TrunkPre = TrunkPreT<TrunkCfg<P>::NV, (P * 9 + TrunkCfg<P>::NT - 1) / TrunkCfg<P>::NT, trunk_staged_clouds<P>()>;
 
+// Which time embedding a cloud's rows add to its cvec: the offset (floats) from `tvec` to the cloud's own row.  TrunkOneTime: one diffusion
+// time per launch, the offset is zero and folds away.  TrunkClassTime (the fixed-step solvers' schedule classes, pc_rows.h): cloud c reads
+// the row of its class cls[c], clamped into [0, ncls - 1], `stride` floats per class.
+struct TrunkOneTime {
+    __device__ __forceinline__ size_t offset(int) const { return 0; }
+};
+struct TrunkClassTime {
+    const int *cls;
+    int ncls;
+    size_t stride;
+    __device__ __forceinline__ int cloud_class(int cloud) const {
+        const int c = cls[cloud];
+        return c < 0 ? 0 : (c < ncls ? c : ncls - 1);
+    }
+    __device__ __forceinline__ size_t offset(int cloud) const { return (size_t)cloud_class(cloud) * stride; }
+};
+
 // Entry sequence shared by every kernel that evaluates the trunk: request the first layer's weights and bias
 // (call BEFORE any prologue work so the latency overlaps it).
-template <int P>
+template <int P, class TV = TrunkOneTime>
 __device__ __forceinline__ void trunk_begin(const gp_scorenet &net, TrunkPre<P> &pre, const float *__restrict__ cvec,
-                                            const float *__restrict__ tvec, int row0, int nrows, int kcand) {
+                                            const float *__restrict__ tvec, int row0, int nrows, int kcand, TV tv = TV()) {
     constexpr int NW = TrunkCfg<P>::NW, NV = TrunkCfg<P>::NV, NT = TrunkCfg<P>::NT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ncl[4] = {wave, wave + NW, wave + 2 * NW, wave + 3 * NW};  // first NV entries are this wave's chunks
@@ -101,7 +118,7 @@ __device__ __forceinline__ void trunk_begin(const gp_scorenet &net, TrunkPre<P> 
             int cl = pre.cloud0 + c;
             cl = cl < nclouds ? cl : nclouds - 1;
             pre.scv[q] = reinterpret_cast<const f32x4 *>(cvec + (size_t)cl * HEADS)[o];
-            pre.stv[q] = reinterpret_cast<const f32x4 *>(tvec)[o];
+            pre.stv[q] = reinterpret_cast<const f32x4 *>(tvec + tv.offset(cl))[o];
         }
     }
 }
@@ -170,9 +187,10 @@ struct HeadOps {
     f32x4 w0[NV], w1[NV], w2[NV], cv[NV][PT];
 };
 
-template <int P, int PT, int NV, bool KEEP = false>
+template <int P, int PT, int NV, bool KEEP = false, class TV = TrunkOneTime>
 __device__ __forceinline__ void head_ops_load(HeadOps<PT, NV> &o, const float *lds, bool staged, const float *__restrict__ cvec,
-                                              const float *__restrict__ tvec, int h, const int (&nc)[4], const int (&cloud)[PT], int cloud0) {
+                                              const float *__restrict__ tvec, int h, const int (&nc)[4], const int (&cloud)[PT], int cloud0,
+                                              TV tv = TV()) {
     using L = TrunkLds<P, KEEP>;
     const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -185,10 +203,14 @@ __device__ __forceinline__ void head_ops_load(HeadOps<PT, NV> &o, const float *l
         if (staged) {
 #pragma unroll
             for (int p = 0; p < PT; ++p) o.cv[i][p] = *reinterpret_cast<const f32x4 *>(lds + L::OFF_CVT + (cloud[p] - cloud0) * L::LDC + ch);
-        } else {
-            const f32x4 tv = *reinterpret_cast<const f32x4 *>(tvec + ch);
+        } else if constexpr (__is_same(TV, TrunkOneTime)) {
+            const f32x4 t4 = *reinterpret_cast<const f32x4 *>(tvec + ch);
 #pragma unroll
-            for (int p = 0; p < PT; ++p) o.cv[i][p] = *reinterpret_cast<const f32x4 *>(cvec + (size_t)cloud[p] * HEADS + ch) + tv;
+            for (int p = 0; p < PT; ++p) o.cv[i][p] = *reinterpret_cast<const f32x4 *>(cvec + (size_t)cloud[p] * HEADS + ch) + t4;
+        } else {  // every row's cloud adds the time embedding of its own class
+#pragma unroll
+            for (int p = 0; p < PT; ++p)
+                o.cv[i][p] = *reinterpret_cast<const f32x4 *>(cvec + (size_t)cloud[p] * HEADS + ch) + *reinterpret_cast<const f32x4 *>(tvec + tv.offset(cloud[p]) + ch);
         }
     }
 }
@@ -211,9 +233,10 @@ struct TrunkNoEmit {};
 // it keeps TWO running sums (chunks w, w + 8 -> "wave" w; chunks w + 4, w + 12 -> "wave" w + 4), reduces each over the lane groups and
 // parks eight partials.  Same products, same additions in the same order: the tile's f_theta equals the 32- / 64-row tiles' BIT FOR BIT,
 // which is what lets the RK45 driver's shared-chunk plan (48-row own tiles + 16-row shared tiles) return the whole-tile plans' poses.
-template <int P, bool KEEP_H1 = false, class Emit = TrunkNoEmit, bool SPLIT = false, bool ORDER8 = (P == 48)>
+// TV (TrunkClassTime): the time embedding is the row's cloud's class's - what trunk_begin staged, or the slow path's per-row read.
+template <int P, bool KEEP_H1 = false, class Emit = TrunkNoEmit, bool SPLIT = false, bool ORDER8 = (P == 48), class TV = TrunkOneTime>
 __device__ __forceinline__ void trunk_ftheta(float *lds, const gp_scorenet &net, const float *__restrict__ cvec, const float *__restrict__ tvec,
-                                             int row0, int nrows, int kcand, TrunkPre<P> &pre, Emit emit = Emit(), int hsel = 0) {
+                                             int row0, int nrows, int kcand, TrunkPre<P> &pre, Emit emit = Emit(), int hsel = 0, TV tv = TV()) {
     using L = TrunkLds<P, KEEP_H1>;
     constexpr int PT = P / 16, NW = TrunkCfg<P>::NW, NV = TrunkCfg<P>::NV, NT = TrunkCfg<P>::NT;
     static_assert(!ORDER8 || (NW == 4 && NV == 4 && L::NRED >= 8 && !SPLIT), "ORDER8: a four-wave tile reproducing the eight-wave order");
@@ -261,7 +284,7 @@ __device__ __forceinline__ void trunk_ftheta(float *lds, const gp_scorenet &net,
 #pragma unroll
             for (int p = 0; p < PT; ++p) part[e][p][0] = part[e][p][1] = part[e][p][2] = 0.f;
         HeadOps<PT, NV> o;
-        head_ops_load<P, PT, NV, KEEP_H1>(o, lds, pre.staged, cvec, tvec, hh, nch[h], cloud, pre.cloud0);
+        head_ops_load<P, PT, NV, KEEP_H1>(o, lds, pre.staged, cvec, tvec, hh, nch[h], cloud, pre.cloud0, tv);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int e = ORDER8 ? (i & 1) : 0;

@@ -350,31 +350,48 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void pc_step_seeded_kernel(PcArgs 
 // MODEL 1 (heun_step_kernel<16, energy>, dpm2m_step_kernel<16, energy>): the ENERGY network drives the solver with ITS score, the gradient
 // of the inner-product energy (energynet.py:200-222) - forward + vector-Jacobian product in the tile as in pc_step_tile<16, 1>; the nine
 // words score_vjp_tile leaves are the score itself (f / sigma + J_f^T (x / sigma), no 1e-7f) and are stored as they come.
-template <int P, int SOLVER = SOLVER_HEUN, int MODEL = 0>
-__device__ __forceinline__ void heun_step_tile(const HeunArgs &a, const gp_scorenet &net) {
+// Args = HeunClsArgs (heun_step_classes_kernel, dpm2m_step_classes_kernel; score model): SCHEDULE CLASSES (pc_rows.h) - the row thread reads
+// its cloud's class's schedule row, the trunk adds that class's time embedding per cloud, and every score entry is divided by its own row's
+// sigma (requested before the trunk like the launch-wide one); the kind and DPM2M's first-step flag come from class 0.  The same text
+// otherwise, so a row's bits are the uniform launch's on its class's tables.
+template <int P, int SOLVER = SOLVER_HEUN, int MODEL = 0, class Args = HeunArgs>
+__device__ __forceinline__ void heun_step_tile(const Args &a, const gp_scorenet &net) {
     static_assert(MODEL == 0 || P == gp_bwd::DP, "the backward pass runs on 16-row tiles");
+    constexpr bool CLS = std::is_same<Args, HeunClsArgs>::value;
+    static_assert(!CLS || MODEL == 0, "schedule classes: the score model");
     using L = TrunkLds<P, MODEL == 1>;
-    constexpr int SROW = fixed_sched_row<SOLVER>();
+    constexpr int SROW = fixed_sched_row<SOLVER>(), NSG = (P * POSE + TrunkCfg<P>::NT - 1) / TrunkCfg<P>::NT;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int row0 = blockIdx.x * P, tid = threadIdx.x, i = a.step;
-    const float *tvec = a.tvec_all + (size_t)pc_time_row<SOLVER>(i) * HEADS;
+    const float *tvec = a.tvec_all + (size_t)pc_time_row<SOLVER>(i) * HEADS;  // (class 0's row)
+    const auto tv = heun_times(a);
     TrunkPre<P> pre;
     float sigma = 1.f;
+    float sg[NSG];  // CLS: the sigma of the row of each score entry this thread stores
     if (i < a.nsteps) {
-        trunk_begin<P>(net, pre, a.cvec, tvec, row0, a.nrows, a.kcand);
-        sigma = a.sched[(size_t)i * SROW + 0];  // requested now, used after the trunk
-        gp_pin(sigma);
+        trunk_begin<P>(net, pre, a.cvec, tvec, row0, a.nrows, a.kcand, tv);
+        if constexpr (CLS) {
+#pragma unroll
+            for (int q = 0; q < NSG; ++q) {
+                const int r = row0 + (tid + q * TrunkCfg<P>::NT) / POSE;
+                sg[q] = heun_sched_row<SROW>(a, heun_row_class(a, r < a.nrows ? r : a.nrows - 1), i)[0];
+                gp_pin(sg[q]);
+            }
+        } else {
+            sigma = a.sched[(size_t)i * SROW + 0];  // requested now, used after the trunk
+            gp_pin(sigma);
+        }
     }
     if (i > 0) {
         if (tid < P) {
             const bool live = row0 + tid < a.nrows;
             const int r = live ? row0 + tid : a.nrows - 1;  // rows past the end: clamped duplicates (computed, never stored)
-            const float *sc = a.sched + (size_t)i * SROW;
-            const int kind = (int)sc[3];
+            const float *sc0 = a.sched + (size_t)i * SROW, *sc = heun_sched_row<SROW>(a, heun_row_class(a, r), i);  // control flow from class 0, numbers from the row's class
+            const int kind = (int)sc0[3];
             const float c = sc[1], h = sc[2];
             float xv[9], gr[9], dv[9], cen[3];
             if constexpr (SOLVER == SOLVER_DPM2M) {
-                const bool has_d = (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) && sc[5] != 0.f;
+                const bool has_d = (kind == DPM2M_STEP || kind == DPM2M_STEP_LAST) && sc0[5] != 0.f;
 #pragma unroll
                 for (int j = 0; j < 9; ++j) {
                     xv[j] = a.x[(size_t)r * 9 + j];
@@ -409,11 +426,19 @@ __device__ __forceinline__ void heun_step_tile(const HeunArgs &a, const gp_score
     }
     __syncthreads();
     if constexpr (MODEL == 0) {
-        trunk_ftheta<P>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre);
+        trunk_ftheta<P, false, TrunkNoEmit, false, (P == 48)>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre, TrunkNoEmit(), 0, tv);
         const float *F = lds + L::OFF_H1;
-        for (int e = tid; e < P * POSE; e += TrunkCfg<P>::NT) {
-            const int r = e / POSE, j = e - r * POSE;
-            if (row0 + r < a.nrows) a.score[(size_t)(row0 + r) * POSE + j] = F[r * L::LDH + j] / (sigma + 1e-7f);
+        if constexpr (CLS) {
+#pragma unroll
+            for (int q = 0; q < NSG; ++q) {
+                const int e = tid + q * TrunkCfg<P>::NT, r = e / POSE, j = e - r * POSE;
+                if (e < P * POSE && row0 + r < a.nrows) a.score[(size_t)(row0 + r) * POSE + j] = F[r * L::LDH + j] / (sg[q] + 1e-7f);
+            }
+        } else {
+            for (int e = tid; e < P * POSE; e += TrunkCfg<P>::NT) {
+                const int r = e / POSE, j = e - r * POSE;
+                if (row0 + r < a.nrows) a.score[(size_t)(row0 + r) * POSE + j] = F[r * L::LDH + j] / (sigma + 1e-7f);
+            }
         }
     } else {
         const float *F = gp_bwd::score_vjp_tile<gp_bwd::ENERGY>(lds, net, a.cvec, tvec, row0, a.nrows, a.kcand, pre, sigma);
@@ -430,6 +455,14 @@ __global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_step_kernel(HeunArgs a, 
 template <int P, int MODEL = 0>
 __global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_step_kernel(HeunArgs a, gp_scorenet net) {
     heun_step_tile<P, SOLVER_DPM2M, MODEL>(a, net);
+}
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void heun_step_classes_kernel(HeunClsArgs a, gp_scorenet net) {
+    heun_step_tile<P, SOLVER_HEUN, 0>(a, net);
+}
+template <int P>
+__global__ __launch_bounds__(TrunkCfg<P>::NT) void dpm2m_step_classes_kernel(HeunClsArgs a, gp_scorenet net) {
+    heun_step_tile<P, SOLVER_DPM2M, 0>(a, net);
 }
 
 // The same launch in the chain form (trunk_chain.h).  A wave owns 16 * PT rows from the sampler update to the score: every lane
@@ -539,6 +572,10 @@ template <int SOLVER, int P, int MODEL = 0>
 constexpr auto fixed_step_kernel = heun_step_kernel<P, MODEL>;
 template <int P, int MODEL>
 constexpr auto fixed_step_kernel<SOLVER_DPM2M, P, MODEL> = dpm2m_step_kernel<P, MODEL>;
+template <int SOLVER, int P>
+constexpr auto fixed_classes_kernel = heun_step_classes_kernel<P>;
+template <int P>
+constexpr auto fixed_classes_kernel<SOLVER_DPM2M, P> = dpm2m_step_classes_kernel<P>;
 template <int SOLVER, int PT, int MODEL = 0>
 constexpr auto fixed_chain_kernel = heun_step_chain_kernel<PT, MODEL>;
 template <int PT, int MODEL>
@@ -594,14 +631,16 @@ static int pc_step_launch(int model, int tile, int ngroups, int nclouds_per_grou
     });
 }
 
-// A launch of a fixed-step solver (gp_heun_step_plan, gp_dpm2m_step_plan and their _model forms).
-template <int SOLVER>
+// A launch of a fixed-step solver (gp_heun_step_plan, gp_dpm2m_step_plan and their _model forms; CLASSES: gp_heun_step_classes,
+// gp_dpm2m_step_classes - schedule classes (pc_rows.h), the score model's tile plans only).
+template <int SOLVER, bool CLASSES = false>
 static int fixed_step_plan(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net, const float *cvec,
                            const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out, float *traj,
-                           hipStream_t st) {
+                           hipStream_t st, int ncls = 1, const int *cls = nullptr) {
     if ((model != 0 && model != 1) || ngroups <= 0 || nclouds_per_group < 0 || k <= 0 || nsteps < 1 || launch < 0 ||
         launch >= fixed_launches<SOLVER>(nsteps, denoise) || !net || !cvec || !tvec_all || !sched || !centre || !x || !d || !score || !out)
         return GP_EINVAL;
+    if (CLASSES && (model != 0 || ncls < 1 || ncls > GP_MAX_SCHED_CLASSES || !cls)) return GP_EINVAL;
     const int rg = nclouds_per_group * k, R = ngroups * rg;
     if (R == 0) return GP_OK;
     int P = 0;
@@ -610,6 +649,13 @@ static int fixed_step_plan(int model, int tile, int ngroups, int nclouds_per_gro
     if (model == 1 && (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t)) return GP_EINVAL;
     const HeunArgs a = heun_args(R, k, launch, fixed_launches<SOLVER>(nsteps, denoise) - 1, cvec, tvec_all, sched, centre, x, d, score, out, traj);
     const int nwg = ngroups * ((rg + P - 1) / P);
+    if constexpr (CLASSES) {  // (GP_EINVAL for plan 128: the chain form keeps its one time per launch)
+        const HeunClsArgs ac = heun_cls_args(a, ncls, cls, nsteps + 1);
+        return gp_with_tile(P, [&](auto tile_rows) {
+            constexpr int T = decltype(tile_rows)::value;
+            return gp_launch<fixed_classes_kernel<SOLVER, T>>(dim3(nwg), dim3(TrunkCfg<T>::NT), trunk_lds_bytes<T>(), st, ac, *net);
+        });
+    }
     if (model == 1) {  // the energy model: the forward + vector-Jacobian kernels, with their LDS (gp_heun_layout_model: 16 or 128)
         if (P == 128) return gp_launch<fixed_chain_kernel<SOLVER, 2, 1>>(dim3(nwg), dim3(gp_chain::NT), gp_chain::CfgV<2>::LDS_BYTES, st, a, *net);
         return gp_launch<fixed_step_kernel<SOLVER, 16, 1>>(dim3(nwg), dim3(TrunkCfg<16>::NT), gp_bwd::LDS_BYTES, st, a, *net);
@@ -775,6 +821,20 @@ int gp_heun_step_plan_model(int model, int tile, int ngroups, int nclouds_per_gr
                             float *traj, gp_stream_t s) {
     return fixed_step_plan<SOLVER_HEUN>(model, tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d, score,
                                         out, traj, (hipStream_t)s);
+}
+
+int gp_heun_step_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                         const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                         float *traj, int ncls, const int *cls, gp_stream_t s) {
+    return fixed_step_plan<SOLVER_HEUN, true>(model, tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d,
+                                              score, out, traj, (hipStream_t)s, ncls, cls);
+}
+
+int gp_dpm2m_step_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                          const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                          float *traj, int ncls, const int *cls, gp_stream_t s) {
+    return fixed_step_plan<SOLVER_DPM2M, true>(model, tile, ngroups, nclouds_per_group, k, launch, nsteps, denoise, net, cvec, tvec_all, sched, centre, x, d,
+                                               score, out, traj, (hipStream_t)s, ncls, cls);
 }
 
 int gp_dpm2m_launches(int nsteps, int denoise) { return nsteps < 1 ? GP_EINVAL : nsteps + 1 + (denoise ? 1 : 0); }

@@ -556,9 +556,18 @@ class FixedStepTracker:
     runs on the energy agent's network with the energy model's score inside the kernels (samplers.HeunSampler / Dpm2mSampler(model='energy'))
     and ranker 'energy' evaluates the same network on the same cloud embedding - one encoder graph (no side stream) and the frame's graph,
     last_stats['replays'] == 2.  ranker 'energy' or 'consensus'; 'likelihood' is refused (likelihoods come from the score model).
-    launches=None keeps the chain here: the energy model's one-launch solve measured slower than its chain (profiles/fixed_step_energy.txt)."""
+    launches=None keeps the chain here: the energy model's one-launch solve measured slower than its chain (profiles/fixed_step_energy.txt).
+    init: 'gt' (default) - the reference's evaluation protocol as above: an object without a predecessor starts from a jittered gt_RT.
+    'prior' (ours; opt-in) - the tracker ACQUIRES such objects itself and needs no ground truth: frames[i][2] is ignored and may be None,
+    nothing is drawn on the host.  Objects without a predecessor form schedule class 1 and start from the pure prior sigma(acquire_T0) z
+    (cond_ode_sampler with init_x = None, samplers.py:180); the tracked ones are class 0 at T0; both run the same N steps in the same
+    launches (gp_track_start_classes makes the class table on the device, samplers.HeunSampler / Dpm2mSampler(classes=2) solve).  The graph
+    key stays (sequence, object count): a frame in which an object enters, leaves or is re-acquired after reset() captures nothing new.
+    The class-aware solve runs in every frame of this mode; init_x of an acquired object is a zero row, last_stats['acquired'] counts them.
+    Score model only (sample_from='energy' is refused)."""
 
     RANKERS = ("energy", "likelihood", "consensus")
+    INITS = ("gt", "prior")
     SOLVERS = ("heun", "dpm2m")
     SAMPLE_FROM = ("score", "energy")
     LAUNCHES = (None, "single", "chain")
@@ -569,8 +578,14 @@ class FixedStepTracker:
     RING = 4  # pinned blocks in rotation: the host rewrites one only after the copy issued four steps earlier has completed
 
     def __init__(self, score_agent, energy_agent=None, steps=8, repeat_num=50, T0=0.15, ratio=0.6, ranker="energy", seed=0, launches=None,
-                 grid="geometric", max_objects_per_frame=8, solver="heun", symmetric=None, sample_from="score"):
+                 grid="geometric", max_objects_per_frame=8, solver="heun", symmetric=None, sample_from="score", init="gt", acquire_T0=0.55):
         from .samplers import HEUN_GRIDS
+        if init not in self.INITS:
+            raise ValueError(f"FixedStepTracker(init={init!r}): one of {self.INITS}")
+        if init == "prior" and sample_from == "energy":
+            raise ValueError("FixedStepTracker(init='prior', sample_from='energy'): schedule classes run on the score model; init='gt' or sample_from='score'")
+        if init == "prior" and not 0.0 < float(acquire_T0) <= 1.0:
+            raise ValueError(f"FixedStepTracker(acquire_T0={acquire_T0}): a diffusion time in (0, 1]")
         if solver not in self.SOLVERS:
             raise ValueError(f"FixedStepTracker(solver={solver!r}): one of {self.SOLVERS}")
         if sample_from not in self.SAMPLE_FROM:
@@ -613,6 +628,7 @@ class FixedStepTracker:
         self.steps, self.repeat_num, self.T0, self.ratio = int(steps), int(repeat_num), float(T0), ratio
         self.ranker, self.seed, self.launches, self.grid = ranker, int(seed) % (1 << 64), launches, grid
         self.max_objects, self.solver, self.symmetric = int(max_objects_per_frame), solver, symmetric
+        self.init, self.acquire_T0 = init, float(acquire_T0)
         self.buffers, self.frame_index = [], []
         self._embed = self._prev = None
         self._b = ShapeCache(self.MAX_SHAPES)
@@ -620,7 +636,8 @@ class FixedStepTracker:
         self.last_stats = {}
 
     def reset(self, seq=None):
-        """Forget the previous poses (the next frame starts from jittered ground truth) and restart the frame count, of one sequence or all."""
+        """Forget the previous poses (the next frame starts from jittered ground truth, or with init='prior' acquires every object again) and
+        restart the frame count, of one sequence or all."""
         for i in (range(len(self.buffers)) if seq is None else [seq]):
             self.buffers[i], self.frame_index[i] = [], 0
 
@@ -673,10 +690,17 @@ class FixedStepTracker:
         src = ent["src"].long()
         init_sRT = torch.where((src >= 0).view(n, 1, 1), self._prev.index_select(0, src.clamp(min=0)), ent["fallback"])
         init_x = torch.cat([init_sRT[:, :3, 0], init_sRT[:, :3, 1], init_sRT[:, :3, 3] - centre], dim=1)
+        if self.init == "prior":  # an acquired object starts from the prior alone: a zero row
+            init_x = torch.where((src >= 0).view(n, 1), init_x, torch.zeros_like(init_x))
         lo = 0
         for q, (_, c) in enumerate(key):  # one launch per sequence: its own row base and frame index
-            _lib.call("gp_track_warm_start", c, K, ptr(ent["seed"][q]), ptr(smp.sched), ptr(self._prev), ptr(ent["src"][lo:lo + c]),
-                      ptr(ent["fallback"][lo:lo + c]), ptr(centre[lo:lo + c]), ptr(smp.x[lo * K:(lo + c) * K]), stream_ptr())
+            if self.init == "prior":  # the start states and the solve's class table (class 1: acquired), no fallback pose
+                _lib.call("gp_track_start_classes", c, K, ptr(ent["seed"][q]), ptr(smp.sched), smp.nlaunch * smp.SCHED_ROW, ptr(self._prev),
+                          ptr(ent["src"][lo:lo + c]), None, ptr(centre[lo:lo + c]), ptr(smp.x[lo * K:(lo + c) * K]), ptr(smp.cls[lo:lo + c]), 1,
+                          stream_ptr())
+            else:
+                _lib.call("gp_track_warm_start", c, K, ptr(ent["seed"][q]), ptr(smp.sched), ptr(self._prev), ptr(ent["src"][lo:lo + c]),
+                          ptr(ent["fallback"][lo:lo + c]), ptr(centre[lo:lo + c]), ptr(smp.x[lo * K:(lo + c) * K]), stream_ptr())
             lo += c
         smp._launch_all()
         pred = smp.out.view(n, K, 9)
@@ -709,6 +733,8 @@ class FixedStepTracker:
         n, dev = sum(c for _, c in key), pts.device
         Solver = Dpm2mSampler if self.solver == "dpm2m" else HeunSampler
         kw = dict(grid=self.grid, use_graph=False, model=self.sample_from)
+        if self.init == "prior":
+            kw["classes"] = 2  # class 0: tracked at T0; class 1: acquired at acquire_T0
         probe = Solver(net.pose_score_net, n, K, self.steps, dev, **kw)
         form = self._solve_form(n * K, probe.plan)
         smp = probe if form == "chain" else Solver(net.pose_score_net, n, K, self.steps, dev, launches=form, **kw)
@@ -722,7 +748,7 @@ class FixedStepTracker:
                "pin_src": [torch.zeros(n, dtype=torch.int32).pin_memory() for _ in range(self.RING)],
                "pin_fb": [torch.zeros(n, 4, 4).pin_memory() for _ in range(self.RING)],
                "ev": [None] * self.RING}
-        smp._write_schedule(self.T0, net.sampling_eps)
+        smp._write_schedule((self.T0, self.acquire_T0) if self.init == "prior" else self.T0, net.sampling_eps)
         if self.ranker == "consensus":  # the symmetry flags: static, read by the captured launch; NULL (no object symmetric) without `symmetric`
             ent["sym"] = ent["sym_host"] = None
             if self.symmetric is not None:
@@ -776,7 +802,7 @@ class FixedStepTracker:
             names = self.buffers[i]
             for name in frames[i][1]:
                 src.append(i * self.max_objects + names.index(name) if name in names else -1)
-                fresh = fresh or src[-1] < 0
+                fresh = fresh or (src[-1] < 0 and self.init == "gt")  # init 'prior': no fallback pose, nothing drawn or uploaded for it
         ent["pts"].copy_(pts)
         slot = ent["ring"] = (ent["ring"] + 1) % self.RING
         if ent["ev"][slot] is not None:
@@ -814,6 +840,8 @@ class FixedStepTracker:
         smp = ent["smp"]
         self.last_stats = {"replays": replays, "captures": self.captures, "launches": smp.launches, "kernel": smp.kernel_name, "plan": smp.plan,
                            "nfev": smp.nlaunch - 1, "rows": pts.shape[0] * K, "uploaded_src": uploaded, "uploaded_fallback": fresh}
+        if self.init == "prior":
+            self.last_stats["acquired"] = sum(1 for v in src if v < 0)
         lo = 0
         for i in live:
             c = int(frames[i][0].shape[0])

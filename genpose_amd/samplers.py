@@ -252,11 +252,13 @@ def _replay_captured(smp, restore, graph_events=None):
 
 class _ScheduleTable:
     """A fixed-step solver's run-time schedule: [launches][row] floats + the N + 1 times, one pinned block -> one device block (sched,
-    t_dev) -> the time-embedding table (tvec_all), refilled in stream order when the key changes."""
+    t_dev) -> the time-embedding table (tvec_all), refilled in stream order when the key changes.  classes = C > 1 (schedule classes): C
+    schedules [C][launches][row] and C x (N + 1) times in the same one block, one gp_time_embed over all of them -> tvec_all [C (N+1), 768]."""
 
-    def __init__(self, net, nlaunch, row, ntimes, device):
+    def __init__(self, net, nlaunch, row, ntimes, device, classes=1):
         self.net, self.dev = net, device
-        self._sched_len = nlaunch * row
+        self._sched_len = classes * nlaunch * row
+        ntimes = classes * ntimes
         self._table = torch.zeros(self._sched_len + ntimes, device=device)
         self._host = torch.zeros(self._sched_len + ntimes).pin_memory()
         self._ev = None
@@ -266,7 +268,8 @@ class _ScheduleTable:
         self.tvec_all = torch.empty(ntimes, 768, device=device)
 
     def write(self, key, schedule):
-        """schedule() -> (times [N + 1], sched [launches][row]); called only when `key` is not the one the buffers hold."""
+        """schedule() -> (times [N + 1], sched [launches][row]) - with classes, both stacked over the classes; called only when `key` is not
+        the one the buffers hold."""
         if key == self._key:
             return
         t, sched = schedule()
@@ -276,7 +279,7 @@ class _ScheduleTable:
             self._ev = torch.cuda.Event()
         h = self._host.numpy()
         h[: self._sched_len] = sched.reshape(-1)
-        h[self._sched_len:] = t.astype(np.float32)
+        h[self._sched_len:] = t.astype(np.float32).reshape(-1)
         self._table.copy_(self._host, non_blocking=True)
         self._ev.record(torch.cuda.current_stream(self.dev))
         self.net.time_embed(self.t_dev, out=self.tvec_all)
@@ -325,6 +328,31 @@ def track_warm_start(seed_state, sigma, prev_sRT, src, fallback_sRT, centre, K, 
         out = torch.empty(n * int(K), 9, device=centre.device)
     _lib.call("gp_track_warm_start", n, int(K), ptr(seed_state), ptr(sigma), ptr(prev_sRT), ptr(src), ptr(fallback_sRT), ptr(centre), ptr(out), stream_ptr())
     return out
+
+
+def track_start_classes(seed_state, sched, class_stride, prev_sRT, src, fallback_sRT, centre, K, acquire=True, out=None, cls_out=None):
+    """The tracker's start states with a schedule class per cloud (gp_track_start_classes): track_warm_start that can ACQUIRE.  sched: a
+    class-aware sampler's schedule block (HeunSampler(classes=C).sched), class_stride = launches * floats per row.  Cloud i with src[i] >= 0
+    gets track_warm_start's bits on class 0's sigma; with src[i] < 0 and acquire, the pure prior sigma_1 z on the same draw (samplers.py:180
+    with init_x = None; fallback_sRT may be None), without acquire the fallback pose.  Returns (x0 [n K, 9], cls [n] int32: the class table of
+    the solve, made on the device)."""
+    n = int(centre.shape[0])
+    for t, dt in ((sched, torch.float32), (prev_sRT, torch.float32), (centre, torch.float32), (src, torch.int32)) + (() if fallback_sRT is None else ((fallback_sRT, torch.float32),)):
+        if t.dtype != dt:
+            raise ValueError(f"track_start_classes: expected {dt}, got {t.dtype}")
+    if fallback_sRT is None and not acquire:
+        raise ValueError("track_start_classes: fallback_sRT=None needs acquire=True")
+    if src.shape[0] != n or (fallback_sRT is not None and fallback_sRT.shape[0] != n):
+        raise ValueError(f"track_start_classes: {n} clouds, src {tuple(src.shape)}, fallback_sRT {None if fallback_sRT is None else tuple(fallback_sRT.shape)}")
+    if acquire and sched.numel() <= int(class_stride):
+        raise ValueError("track_start_classes: acquire reads class 1's sigma, the schedule block holds one class")
+    if out is None:
+        out = torch.empty(n * int(K), 9, device=centre.device)
+    if cls_out is None:
+        cls_out = torch.empty(n, dtype=torch.int32, device=centre.device)
+    _lib.call("gp_track_start_classes", n, int(K), ptr(seed_state), ptr(sched), int(class_stride), ptr(prev_sRT), ptr(src), ptr(fallback_sRT), ptr(centre),
+              ptr(out), ptr(cls_out), int(bool(acquire)), stream_ptr())
+    return out, cls_out
 
 
 def philox_raw(counters, keys):
@@ -408,14 +436,24 @@ class HeunSampler:
 
     launches: 'chain' (default) - one kernel launch per launch index; 'single' - the whole solve in ONE launch (gp_heun_solve_tile: a
     workgroup takes its tile's rows through every index itself, tile plans only), the same bits in x, the pose and the trajectory.  nlaunch,
-    NFE and the schedule are those of the chain either way."""
+    NFE and the schedule are those of the chain either way.
+
+    classes: C > 1 (ours; opt-in) - SCHEDULE CLASSES: every cloud carries a class and each class its own T0, so clouds that start from
+    different times (a tracker's tracked and newly acquired objects) share the launches of one solve (gp_heun_step_classes /
+    gp_heun_solve_classes; csrc/pc_rows.h).  run(..., T0=(T0_0 .. T0_{C-1}), eps=, cls=int32 device tensor [B]): all three are run-time
+    values refilled in stream order - one capture per geometry.  A row's result is, bit for bit, the uniform sampler's at its class's T0 on
+    the same plan and form.  Score model, tile plans: where the automatic layout would take plan 128 the sampler takes the 64-row tiles
+    (last_stats['plan']); model='energy', trunk='bf16x9' and tile=128 are refused.  classes=1 is the sampler without classes."""
 
     LAUNCHES = ("chain", "single")
+    MAX_CLASSES = 8  # GP_MAX_SCHED_CLASSES
     # what a solver on the same launch shape, plans and buffers replaces (Dpm2mSampler): the floats per schedule row, the entry points
     # (chain plan on bf16x9, any plan, one launch) and the kernels' names
     SCHED_ROW = 4
     ENTRY = ("gp_heun_step_bf16x9", "gp_heun_step_plan", "gp_heun_solve_tile")
     KERNELS = ("heun_step_chain_kernel", "heun_step_kernel", "heun_solve_kernel")
+    ENTRY_CLASSES = ("gp_heun_step_classes", "gp_heun_solve_classes")
+    KERNELS_CLASSES = ("heun_step_classes_kernel", "heun_solve_classes_kernel")
     MODELS = ("score", "energy")
 
     @staticmethod
@@ -425,9 +463,25 @@ class HeunSampler:
     def _schedule(self, T0, eps):
         return heun_schedule(self.n, T0, eps, self.grid, self.rho, self.denoise)
 
+    def _class_schedules(self, T0s, eps):
+        """The C-class block: every class's own schedule, stacked - (t [C, N+1], sched [C, launches, row]).  The kind column depends on the
+        launch index alone, so it is the same in every class (the kernels read it from class 0)."""
+        per = [self._schedule(T0, eps) for T0 in T0s]
+        return np.stack([t for t, _ in per]), np.stack([sc for _, sc in per])
+
     def __init__(self, net, B, K, nsteps, device, groups=1, grid="geometric", rho=7.0, trunk=None, tile=None, record_traj=False, denoise=True,
-                 use_graph=True, launches="chain", model="score"):
+                 use_graph=True, launches="chain", model="score", classes=1):
         import ctypes
+        if not 1 <= int(classes) <= self.MAX_CLASSES:
+            raise ValueError(f"classes {classes!r}: 1 .. {self.MAX_CLASSES} schedule classes")
+        self.classes = int(classes)
+        if self.classes > 1:
+            if model == "energy":
+                raise ValueError("model='energy' with classes > 1: schedule classes run on the score model's tile kernels")
+            if trunk == "bf16x9":
+                raise ValueError("trunk='bf16x9' with classes > 1: the split-bf16 trunk is the 128-row chain form, which keeps one time per launch")
+            if tile and int(tile) == 128:
+                raise ValueError("tile=128 with classes > 1: the 128-row chain form keeps one time per launch; schedule classes run on tiles 16 / 32 / 64")
         if B % groups:
             raise ValueError(f"{B} clouds do not split into {groups} equal batches")
         if grid not in HEUN_GRIDS:
@@ -453,6 +507,10 @@ class HeunSampler:
         if _lib.lib().gp_heun_layout_model(self.model, int(tile or 0), groups, B // groups, K, ctypes.byref(t_out)) != 0:
             raise ValueError(f"{B // groups} clouds x {K} candidates per batch do not split into workgroups of plan {tile or 'auto'}"
                              + (" (the energy model has plans 16 and 128)" if self.model else "") + "; run the batches separately")
+        if self.classes > 1 and t_out.value == 128:
+            # the automatic layout took the chain form, which has no classes: the 64-row tiles, the next plan of the ladder, serve the size
+            if _lib.lib().gp_heun_layout_model(0, 64, groups, B // groups, K, ctypes.byref(t_out)) != 0:
+                raise ValueError(f"classes > 1: {B // groups} clouds x {K} candidates per batch take plan 128 and do not split into 64-row tiles; force a tile")
         self.plan = self.tile = t_out.value
         if launches == "single" and self.tile == 128:
             raise ValueError(f"launches='single' serves the tile plans (16 / 32 / 64 rows); {B} clouds x {K} candidates on plan {tile or 'auto'} "
@@ -464,6 +522,8 @@ class HeunSampler:
             if self.trunk == "bf16x9":
                 self._x9 = net.w.bf16x9_packs()
         kc, kt, ks = self.KERNELS
+        if self.classes > 1:
+            kt, ks = self.KERNELS_CLASSES
         sfx = ",energy>" if self.model else ">"
         self.kernel_name = (f"{kc}<bf16x9>" if self.trunk == "bf16x9" else f"{kc}<2{sfx}" if self.tile == 128
                             else f"{ks}<{self.tile}{sfx}" if launches == "single" else f"{kt}<{self.tile}{sfx}")
@@ -471,14 +531,21 @@ class HeunSampler:
         self.x, self.d, self.score, self.out = f(R, 9), f(R, 9), f(R, 9), f(R, 9)
         self.cvec, self.centre = f(B, 768), f(B, 3)
         self.traj = f(self.n, R, 9) if record_traj else None
-        self._table = _ScheduleTable(net, self.nlaunch, self.SCHED_ROW, self.n + 1, self.dev)
+        self._table = _ScheduleTable(net, self.nlaunch, self.SCHED_ROW, self.n + 1, self.dev, classes=self.classes)
         self.sched, self.t_dev, self.tvec_all = self._table.sched, self._table.t_dev, self._table.tvec_all
+        self.cls = torch.zeros(B, dtype=torch.int32, device=self.dev) if self.classes > 1 else None  # the class of every cloud (static)
         self.use_graph = use_graph
         self.graph = None
         self.captures = 0
         self.last_stats = {}
 
     def _write_schedule(self, T0, eps):
+        if self.classes > 1:
+            T0s = tuple(float(t) for t in (T0 if isinstance(T0, (tuple, list)) else (T0,)))
+            if len(T0s) != self.classes:
+                raise ValueError(f"T0 {T0!r}: a sampler with {self.classes} schedule classes takes one T0 per class")
+            self._table.write((T0s, float(eps)), lambda: self._class_schedules(T0s, eps))
+            return
         self._table.write((float(T0), float(eps)), lambda: self._schedule(T0, eps))
 
     def launch_step(self, l):
@@ -486,7 +553,9 @@ class HeunSampler:
         shape = (self.groups, self.B // self.groups, self.K, l, self.n, int(self.denoise))
         bufs = (ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
                 ptr(self.traj))
-        if self.trunk == "bf16x9":
+        if self.classes > 1:
+            _lib.call(self.ENTRY_CLASSES[0], 0, self.plan, *shape, self.net.w.ref(), *bufs, self.classes, ptr(self.cls), stream_ptr())
+        elif self.trunk == "bf16x9":
             _lib.call(self.ENTRY[0], *shape, self.net.w.ref(), *bufs, *(ptr(w) for w in self._x9), stream_ptr())
         elif self.model:
             _lib.call(self.ENTRY[1] + "_model", self.model, self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
@@ -494,6 +563,11 @@ class HeunSampler:
             _lib.call(self.ENTRY[1], self.plan, *shape, self.net.w.ref(), *bufs, stream_ptr())
 
     def _launch_all(self):
+        if self.launches == "single" and self.classes > 1:
+            _lib.call(self.ENTRY_CLASSES[1], 0, self.plan, self.groups, self.B // self.groups, self.K, self.n, int(self.denoise), self.net.w.ref(),
+                      ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
+                      ptr(self.traj), self.classes, ptr(self.cls), stream_ptr())
+            return
         if self.launches == "single":
             _lib.call(*((self.ENTRY[2] + "_model", self.model) if self.model else (self.ENTRY[2],)), self.plan, self.groups, self.B // self.groups, self.K, self.n, int(self.denoise), self.net.w.ref(),
                       ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.centre), ptr(self.x), ptr(self.d), ptr(self.score), ptr(self.out),
@@ -502,11 +576,18 @@ class HeunSampler:
         for l in range(self.nlaunch):
             self.launch_step(l)
 
-    def run(self, cvec, centre, x0, T0=1.0, eps=EPS):
+    def run(self, cvec, centre, x0, T0=1.0, eps=EPS, cls=None):
         """cvec [B,768], centre [B,3], x0 [R,9] (the state at T0).  Returns (xs [R,N,9] or None, pose [R,9]) float32: x_1 .. x_N and the
-        final pose, rotations normalised and cloud centres added."""
+        final pose, rotations normalised and cloud centres added.  With schedule classes: T0 one per class, cls [B] int32 on the device,
+        x0 every cloud's state at its class's T0."""
         if cvec.shape[0] != self.B or x0.shape[0] != self.R:
             raise ValueError(f"Heun sampler set up for {self.B} clouds x {self.K} candidates got {cvec.shape[0]} clouds / {x0.shape[0]} rows")
+        if (cls is not None) != (self.classes > 1):
+            raise ValueError("cls= goes with a sampler built with classes > 1" if cls is not None else f"a sampler with {self.classes} schedule classes needs cls=")
+        if cls is not None:
+            if cls.dtype != torch.int32 or tuple(cls.shape) != (self.B,):
+                raise ValueError(f"cls: int32 [{self.B}], got {cls.dtype} {tuple(cls.shape)}")
+            self.cls.copy_(cls)
         self.cvec.copy_(cvec)
         self.centre.copy_(centre)
         self.x.copy_(x0)
@@ -580,6 +661,8 @@ class Dpm2mSampler(HeunSampler):
     SCHED_ROW = DPM2M_SCHED_ROW
     ENTRY = ("gp_dpm2m_step_bf16x9", "gp_dpm2m_step_plan", "gp_dpm2m_solve_tile")
     KERNELS = ("dpm2m_step_chain_kernel", "dpm2m_step_kernel", "dpm2m_solve_kernel")
+    ENTRY_CLASSES = ("gp_dpm2m_step_classes", "gp_dpm2m_solve_classes")
+    KERNELS_CLASSES = ("dpm2m_step_classes_kernel", "dpm2m_solve_classes_kernel")
 
     @staticmethod
     def _launches(nsteps, denoise):

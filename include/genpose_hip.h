@@ -557,6 +557,50 @@ int gp_dpm2m_solve_tile_model(int model, int tile, int ngroups, int nclouds_per_
                               const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
                               float *out, float *traj, gp_stream_t s);
 
+/* SCHEDULE CLASSES ON THE FIXED-STEP SOLVERS (opt-in; ours): clouds that start from DIFFERENT times share the launches of one solve - a
+ * tracker's objects continue from T0 = 0.15 around their previous pose while a newly seen one starts from the prior at T0 = 0.55 .. 1.
+ * The `_classes` forms take the arguments of the `_model` forms above plus `ncls` (1 .. GP_MAX_SCHED_CLASSES) and `cls` [clouds] (device,
+ * int32): the class of every cloud, clamped into [0, ncls - 1] on the device, so a bad table reads nothing outside the buffers.
+ *     sched     [ncls][launches][row]     one schedule per class, each as gp_heun_step_plan / gp_dpm2m_step_plan describe it
+ *     tvec_all  [ncls][nsteps + 1][768]   gp_time_embed of every class's times
+ * Row r belongs to cloud r / k and class cls[r / k]; per row and launch it reads ITS class's values where the other entry points read the
+ * launch's: the score's divisor sched[c][l][0], the update's coefficients (c, h; s2, ratio, wc, wp) and the time embedding added to the
+ * cloud's cvec.  Control flow stays uniform: the launch kind - and DPM-Solver++(2M)'s "there is a previous denoiser", sched[.][l][5] != 0 -
+ * is read from class 0, and the caller keeps the kind column identical in every class (the same nsteps and denoise for all).
+ * CONTRACT: for every row of a cloud of class c, x, out and traj (and d, score on the chain) hold BIT FOR BIT what the entry point without
+ * classes leaves for that row on the same plan and form when run uniformly on class c's sched / tvec_all; with ncls = 1 a `_classes` entry
+ * equals its twin.  Served: model 0, the 16 / 32 / 64-row tile plans, per-launch chain and one-launch solve.  GP_EINVAL with nothing
+ * written for model 1, the 128-row chain form (tile 128, or tile 0 where gp_heun_layout chooses it), the head-split plan, ncls outside
+ * 1 .. GP_MAX_SCHED_CLASSES, a null cls, and everything the twins refuse.  Stateless, allocation-free, capturable. */
+#define GP_MAX_SCHED_CLASSES 8
+/* One launch of the Heun chain with schedule classes (samplers.py:230-290; the denoising launch: :209-218). */
+int gp_heun_step_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                         const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                         float *traj, int ncls, const int *cls, gp_stream_t s);
+/* One launch of the DPM-Solver++(2M) chain with schedule classes (samplers.py:230-290's grid; the denoising launch: :209-218). */
+int gp_dpm2m_step_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int launch, int nsteps, int denoise, const gp_scorenet *net,
+                          const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score, float *out,
+                          float *traj, int ncls, const int *cls, gp_stream_t s);
+/* The whole Heun solve in one launch with schedule classes (samplers.py:230-290, :209-218): gp_heun_solve_tile's contract per class. */
+int gp_heun_solve_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                          const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                          float *out, float *traj, int ncls, const int *cls, gp_stream_t s);
+/* The whole DPM-Solver++(2M) solve in one launch with schedule classes (samplers.py:230-290's grid, :209-218). */
+int gp_dpm2m_solve_classes(int model, int tile, int ngroups, int nclouds_per_group, int k, int nsteps, int denoise, const gp_scorenet *net,
+                           const float *cvec, const float *tvec_all, const float *sched, const float *centre, float *x, float *d, float *score,
+                           float *out, float *traj, int ncls, const int *cls, gp_stream_t s);
+/* The tracker's start states with a class per cloud (csrc/noise.hip): gp_track_warm_start that can ACQUIRE.  sched: the solve's schedule
+ * block [ncls][launches][row], class_stride = launches * row floats; sigma_c = sched[c * class_stride], class c's sigma(T0_c).
+ *     src[i] >= 0               x0 = init_i + sigma_0 z: gp_track_warm_start's arithmetic and bits (evaluation_tracking.py:302-310)
+ *     src[i] < 0, acquire != 0  x0 = sigma_1 z: the pure prior of cond_ode_sampler with init_x = None (samplers.py:180) on class 1's T0, z the
+ *                               draw the warm start would have used for the row (the same counters); fallback_sRT is not read, may be NULL
+ *     src[i] < 0, acquire == 0  gp_track_warm_start's fallback_sRT[i], class 0
+ * (acquire != 0 reads class 1's row: the block holds at least two classes.)
+ * cls_out [n] (int32) <- the class of cloud i for the solve: src[i] < 0 when acquire != 0, else 0 - the class table is made on the device.
+ * GP_EINVAL on null pointers (fallback_sRT only when acquire == 0), negative sizes, k <= 0, class_stride < 1; zero rows: GP_OK, nothing written. */
+int gp_track_start_classes(int n, int k, const void *seed_state, const float *sched, int class_stride, const float *prev_sRT, const int *src,
+                           const float *fallback_sRT, const float *centre, float *x0, int *cls_out, int acquire, gp_stream_t s);
+
 /* FIXED-STEP HEUN SOLVE OF THE EXACT-LIKELIHOOD ODE (opt-in; csrc/heun_likelihood.hip).  cond_ode_likelihood's system (samplers.py:22-99)
  * d[x; logp]/dt = -g^2/2 [score; div_x score] with the exact divergence of gp_score_div_exact, integrated in sigma from sigma(eps) UP to
  * sigma(T) by Heun's method on a fixed grid (-g^2/2 dt = -sigma dsigma: slope d = -sigma [score; div]).  x and the slopes are fp32, the
