@@ -52,21 +52,12 @@ import torch
 from . import _lib
 from ._lib import ptr, stream_ptr
 from .config import dist_arith_code
+from .graphs import CapturedPasses, capture, pin, unpinned
 from .lru import ShapeCache
 from .weights import EncoderWeights
 
 
 _GENERATION = itertools.count(1)  # process-wide: every write of a workspace's grouping buffers gets a generation no other write has
-
-
-def _unpinned(ws):
-    return ws.get("_pins", 0) == 0
-
-
-def _unpin_entry(key, ent):
-    """A captured pass leaves the cache: the workspaces its replays wrote into return to the eviction order."""
-    for ws in ent.get("pinned", ()):
-        ws["_pins"] = ws.get("_pins", 1) - 1
 
 
 class _Kernel(collections.namedtuple("_Kernel", "name entry operands min_clouds fallback")):
@@ -102,9 +93,8 @@ class Pointnet2EncoderHIP:
         self.out_dim = self.w.out_dim
         # workspaces (~1.5 MB per cloud) per (batch, points, slot): least recently used first, except those a captured graph writes
         # into (`_pins`: taken by whoever captures, given back when that graph is dropped)
-        self._ws = ShapeCache(self.MAX_WORKSPACES, can_evict=_unpinned)
-        self._pass_graphs = ShapeCache(self.MAX_PASS_GRAPHS, on_evict=_unpin_entry)  # (no closure over self: no reference cycle)
-        self._seen_once = ShapeCache(4 * self.MAX_PASS_GRAPHS)
+        self._ws = ShapeCache(self.MAX_WORKSPACES, can_evict=unpinned)
+        self._pass_graphs = CapturedPasses(self.MAX_PASS_GRAPHS)
         # The launch plan: _plan[k][i] serves scale i of level k, _groupall the GroupAll level as a whole (its fp32 fallback = that level's
         # _plan row behind gp_point_linear).  Rows in order of precedence, as in the module text.  All three per-scale split kernels need
         # whole 32-row units, (B * npoint * nsample) % 32 == 0: decided here for any B as (npoint * nsample) % 32 == 0, which holds for
@@ -151,10 +141,8 @@ class Pointnet2EncoderHIP:
     def pin_workspaces(self, B, N, slot=0):
         """For whoever CAPTURES launches of this encoder in a hipGraph: the workspace of that geometry stays out of the eviction order
         while the graph lives (its buffers were allocated outside the capture; nothing but this cache holds them).  Returns the
-        workspace; give the pin back with `ws['_pins'] -= 1` when the graph is dropped."""
-        ws = self._workspace(B, N, slot)
-        ws["_pins"] = ws.get("_pins", 0) + 1
-        return ws
+        workspace; graphs.capture(pins=) takes the pin this way and graphs.release gives it back when the graph is dropped."""
+        return pin(self._workspace(B, N, slot))
 
     def _wait_pending_join(self, ws):
         """A deferred grouping (prepare_grouping(defer_join=True)) whose consumer never ran - an exception in between, a caller that only
@@ -331,45 +319,26 @@ class Pointnet2EncoderHIP:
         ~25 launches replayed instead of issued (they dominate a small batch: a 5-cloud pass is launch-bound).  The first call of a shape
         runs launch by launch (warm-up; a shape seen once never pays a capture), the second captures, later ones copy the clouds into the
         graph's static input and replay.  Results are the launch-by-launch pass's, bit for bit (same kernels, same order)."""
-        direct = (lambda: self.forward(pts, grouping=grouping)) if grouping is not None else (lambda: self._forward_with_grouping(pts))
+        run = (lambda p: self.forward(p, grouping=grouping)) if grouping is not None else self._forward_with_grouping
         if not use_graph or not pts.is_cuda or pts.dtype != torch.float32 or torch.cuda.is_current_stream_capturing():
-            return direct()  # (wrong device / dtype: the launch-by-launch path raises what it always raised)
+            return run(pts)  # (wrong device / dtype: the launch-by-launch path raises what it always raised)
+
+        def captured():
+            buf = pts[..., 0:3].contiguous().clone()
+            # (no warm-up: the first call of the shape was one; `grouping` is kept alive - its id() is part of the key)
+            return capture(lambda: run(buf), bufs=(buf,), pins=[lambda: self.pin_workspaces(buf.shape[0], buf.shape[1], 0)],
+                           extra={"grouping": grouping})
         # (the id() of `grouping` is part of the key: an entry with a graph keeps its `grouping` alive, so the id cannot be reused
         # while the entry lives; a shape only SEEN so far is remembered by shape alone)
         key = (tuple(pts.shape), id(grouping) if grouping is not None else None)
-        ent = self._pass_graphs.get(key)
+        ent = self._pass_graphs.entry(key, (tuple(pts.shape), grouping is not None), captured)
         if ent is None:
-            seen = (tuple(pts.shape), grouping is not None)
-            if seen not in self._seen_once:
-                # first call of a shape: launch by launch (a shape that never returns never pays a capture, and - kept apart from the
-                # captured graphs - never evicts one: with more shapes in rotation than the cache holds, a shape is simply captured
-                # again when it comes back, instead of every newcomer throwing out a live graph)
-                self._seen_once[seen] = True
-                return direct()
-            buf = pts[..., 0:3].contiguous().clone()
-            B, N = buf.shape[0], buf.shape[1]
-            # the workspace the replay writes into is pinned BEFORE the capture: were it evicted between the first (direct) call and this
-            # one, _workspace() would otherwise allocate it inside torch.cuda.graph - in the graph's private pool - while the cache holds it
-            pinned = [self.pin_workspaces(B, N, 0)]
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g):
-                    out = self.forward(buf, grouping=grouping) if grouping is not None else self._forward_with_grouping(buf)
-            except BaseException:
-                for ws in pinned:
-                    ws["_pins"] -= 1
-                raise
-            # `grouping` is kept alive (its id() is part of the key)
-            ent = {"graph": g, "buf": buf, "out": out, "grouping": grouping, "pinned": pinned}
-            self._pass_graphs[key] = ent
-        ent["buf"].copy_(pts[..., 0:3])
-        if grouping is None:
-            ent["out"][1]["_gen"] = next(_GENERATION)  # the replay rewrites the grouping buffers: tickets for the previous contents die here
-            ent["graph"].replay()
-            return ent["out"][0].clone(), ent["out"][1]
-        ent["graph"].replay()
-        return ent["out"].clone()
+            return run(pts)
+        if grouping is not None:
+            return ent.replay(pts[..., 0:3]).clone()
+        ent.outs[1]["_gen"] = next(_GENERATION)  # the replay rewrites the grouping buffers: tickets for the previous contents die here
+        feat, ws = ent.replay(pts[..., 0:3])
+        return feat.clone(), ws
 
     def _forward_with_grouping(self, pts):
         ws = self.prepare_grouping(pts, defer_join=True)

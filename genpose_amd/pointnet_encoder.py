@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr, stream_ptr
+from .graphs import CapturedPasses, capture, pin, unpinned
 from .lru import ShapeCache
 from .weights import PointNetWeights
 
@@ -38,9 +39,8 @@ class PointNetEncoderHIP:
         self.device = torch.device(device)
         self.w = PointNetWeights(state_dict, self.device, prefix)
         self.out_dim = self.w.out_dim
-        self._ws = ShapeCache(self.MAX_WORKSPACES, can_evict=lambda ws: ws.get("_pins", 0) == 0)
-        self._pass_graphs = ShapeCache(self.MAX_PASS_GRAPHS, on_evict=_unpin_entry)
-        self._seen_once = ShapeCache(4 * self.MAX_PASS_GRAPHS)
+        self._ws = ShapeCache(self.MAX_WORKSPACES, can_evict=unpinned)
+        self._pass_graphs = CapturedPasses(self.MAX_PASS_GRAPHS)
 
     # ------------------------------------------------------------------ workspace (cached per batch / size)
     def _workspace(self, B, n):
@@ -56,7 +56,7 @@ class PointNetEncoderHIP:
         total = sum(t.numel() * t.element_size() for t in self._workspace(B, n).values() if torch.is_tensor(t))
         ent = self._pass_graphs.get((B, n, 3))
         if ent is not None:  # static input [B,n,3] and static output [B,1024] of the captured pass
-            total += sum(t.numel() * t.element_size() for t in (ent["buf"], ent["out"]))
+            total += sum(t.numel() * t.element_size() for t in (*ent.bufs, ent.outs))
         return total
 
     # ------------------------------------------------------------------ the pass
@@ -91,28 +91,12 @@ class PointNetEncoderHIP:
         if not use_graph or not pts.is_cuda or pts.dtype != torch.float32 or torch.cuda.is_current_stream_capturing():
             return self.forward(pts)
         key = (pts.shape[0], pts.shape[1], 3)
-        ent = self._pass_graphs.get(key)
-        if ent is None:
-            if key not in self._seen_once:
-                self._seen_once[key] = True
-                return self.forward(pts)
+
+        def captured():
             buf = pts[..., 0:3].contiguous().clone()
-            ws = self._workspace(key[0], key[1])  # allocated (and pinned) BEFORE the capture: the replay writes into it
-            ws["_pins"] = ws.get("_pins", 0) + 1
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g):
-                    out = self.forward(buf)
-            except BaseException:
-                ws["_pins"] -= 1
-                raise
-            ent = self._pass_graphs[key] = {"graph": g, "buf": buf, "out": out, "pinned": [ws]}
-        ent["buf"].copy_(pts[..., 0:3])
-        ent["graph"].replay()
-        return ent["out"].clone()
-
-
-def _unpin_entry(key, ent):
-    for ws in ent.get("pinned", ()):
-        ws["_pins"] = ws.get("_pins", 1) - 1
+            # (no warm-up: the first call of the shape was one; the workspace is allocated and pinned BEFORE the capture: the replay writes into it)
+            return capture(lambda: self.forward(buf), bufs=(buf,), pins=[lambda: pin(self._workspace(key[0], key[1]))])
+        ent = self._pass_graphs.entry(key, key, captured)
+        if ent is None:
+            return self.forward(pts)
+        return ent.replay(pts[..., 0:3]).clone()

@@ -16,6 +16,7 @@ import torch
 
 from .config import encoder_kwargs_of
 from .encoder import Pointnet2EncoderHIP
+from .graphs import PinnedBlock
 from .lru import ShapeCache
 from .pointnet_encoder import ACT_RELU, PointNetEncoderHIP, dense_rows
 from .samplers import HEUN_GRIDS, Dpm2mSampler, HeunSampler, ODESampler, PCSampler
@@ -140,14 +141,8 @@ class GFObjectPose:
         key = tuple(cpu.shape)
         st = self._staging.get(key)
         if st is None:
-            st = self._staging[key] = (torch.empty(key, dtype=torch.float32).pin_memory(), torch.cuda.Event())
-            st[1].record()
-        pinned, ev = st
-        ev.synchronize()  # the previous copy out of the pinned buffer has completed
-        pinned.copy_(cpu)
-        dev = pinned.to(self.device, non_blocking=True)
-        ev.record()
-        return dev
+            st = self._staging[key] = PinnedBlock(key)
+        return st.send(self.device, lambda host: host.copy_(cpu))
 
     def _pc_precision(self, B, K, coupling=None, groups=1):
         """cfg.sampler_precision = 'bf16x3' (opt-in, exploratory): the PC sampler's score network on split-bf16 products where the 128-row

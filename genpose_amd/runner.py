@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import reward, rotation
+from .graphs import capture, holding, release
 from .lru import ShapeCache
 
 
@@ -172,11 +173,6 @@ def add_noise_to_RT(RT, r=5.0, t=0.03, draws=None):
     return out
 
 
-def _unpin_frame_entry(key, ent):
-    for ws in ent[4]:
-        ws["_pins"] -= 1
-
-
 class _FrameGraphs:
     """hipGraphs of the launch sequences of a tracking frame that need no host decision, keyed by the clouds' shape:
       A   clouds [n,1024,3] -> centres, the SCORE model's per-cloud embedding: grouping (furthest point sampling with its deeper levels on a
@@ -187,27 +183,35 @@ class _FrameGraphs:
           the small conversions); waits for A'.
     Between A and B sits the adaptive ODE solve, whose attempts are graph replays of their own.  A 5-object frame is then A + the
     solve's replay(s) + B instead of ~70 individually launched kernels.  Inputs are copied into static buffers, outputs are static
-    tensors that the NEXT frame of the same shape overwrites (callers that keep them clone)."""
+    tensors that the NEXT frame of the same shape overwrites (callers that keep them clone).
 
-    def __init__(self, snet, enet, K, sel, T_energy=1e-5):
+    enet None (a tracker on one network, FixedStepTracker): A alone - one plain encoder pass, no side stream (ev_e is None), cvec_e is
+    None; with T_energy, `snet` is an ENERGY network that also ranks, on the embedding A leaves."""
+
+    def __init__(self, snet, enet=None, K=None, sel=None, T_energy=1e-5):
+        """T_energy: the time the ranking network (enet, else snet) is evaluated at; None: nothing ranks by energy."""
         from .sde import SIGMA_MAX, SIGMA_MIN
         self.snet, self.enet, self.K, self.sel = snet, enet, K, sel
-        for net in (snet, enet):
+        self.nets = (snet,) if enet is None else (snet, enet)
+        for net in self.nets:
             net.pointnet2_encoder("the frame-graph runner")  # refuses an agent whose features are not the PointNet++ encoder's alone
         dev = snet.device
-        t = torch.full((1,), float(T_energy), device=dev)
-        self.tvec_e = enet.pose_score_net.time_embed(t)[0].contiguous()
-        self.sigma_e = (SIGMA_MIN * (SIGMA_MAX / SIGMA_MIN) ** t).contiguous()
-        self.share = snet.pts_encoder.grouping_key() == enet.pts_encoder.grouping_key()
-        self.side = torch.cuda.Stream(dev)
-        self.ev_a, self.ev_e = torch.cuda.Event(), torch.cuda.Event()
+        if T_energy is not None:
+            t = torch.full((1,), float(T_energy), device=dev)
+            self.tvec_e = self.nets[-1].pose_score_net.time_embed(t)[0].contiguous()
+            self.sigma_e = (SIGMA_MIN * (SIGMA_MAX / SIGMA_MIN) ** t).contiguous()
+        # the replays write into encoder workspaces of their own: no ticket of the agent path ever points at them
+        self.SLOT = "frame-graphs" if enet is not None else "fixed-step-tracker"
+        self.share = enet is not None and snet.pts_encoder.grouping_key() == enet.pts_encoder.grouping_key()
+        self.side = self.ev_a = self.ev_e = None
+        if enet is not None:
+            self.side = torch.cuda.Stream(dev)
+            self.ev_a, self.ev_e = torch.cuda.Event(), torch.cuda.Event()
         # per object count of a frame: bounded (lru.py); a dropped entry gives its encoder workspaces back to their eviction order
-        self._a = ShapeCache(self.MAX_SHAPES, on_evict=_unpin_frame_entry)
+        self._a = ShapeCache(self.MAX_SHAPES, on_evict=release)
         self._b = ShapeCache(self.MAX_SHAPES)
 
     MAX_SHAPES = 8
-
-    SLOT = "frame-graphs"  # the replays write into encoder workspaces of their own: no ticket of the agent path ever points at them
 
     def _score_body(self, pts):
         enc_s = self.snet.pts_encoder
@@ -224,33 +228,37 @@ class _FrameGraphs:
         being computed on the side stream when this returns - rank() waits for it."""
         key = (tuple(pts.shape), pts.dtype)
         ent = self._a.get(key)
-        cur = torch.cuda.current_stream(pts.device)
         if ent is None:
-            buf = pts.clone()
-            grouping, _, _ = self._score_body(buf)  # warm-up outside capture: workspaces, kernel attributes
-            self._energy_body(buf, grouping)
-            torch.cuda.synchronize()
-            # the replays write into encoder workspaces that were allocated outside the captures (by the warm-up above): pinned - BEFORE the
-            # captures, so that none of them can be re-allocated inside one - for as long as these graphs live
-            n, N = int(buf.shape[0]), int(buf.shape[1])
-            pinned = [self.snet.pts_encoder.pin_workspaces(n, N, self.SLOT), self.enet.pts_encoder.pin_workspaces(n, N, self.SLOT)]
-            ga = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga):
-                grouping, centre, cvec_s = self._score_body(buf)
-            ge = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ge, stream=self.side):
-                cvec_e = self._energy_body(buf, grouping)
-            ent = self._a[key] = (ga, ge, buf, (centre, cvec_s, cvec_e), pinned)
-        ga, ge, buf, outs, _ = ent
+            ent = self._a[key] = self._capture_embed(pts.clone())
+        if self.enet is None:
+            return ent.replay(pts)
+        cur = torch.cuda.current_stream(pts.device)
         cur.wait_event(self.ev_e)  # the previous frame's A' (side stream) has finished reading `buf`, which is about to change
-        buf.copy_(pts)
-        ga.replay()
+        ent.replay(pts)
         self.ev_a.record(cur)
         with torch.cuda.stream(self.side):
             self.side.wait_event(self.ev_a)
-            ge.replay()
+            ent.extra["side"].replay()
             self.ev_e.record(self.side)
-        return outs
+        return ent.outs
+
+    def _capture_embed(self, buf):
+        """One entry for A and A': `outs` = (centre, cvec_s, cvec_e or None), A' as extra['side']."""
+        n, N, two = int(buf.shape[0]), int(buf.shape[1]), self.enet is not None
+
+        def warm():  # outside capture: workspaces, kernel attributes
+            grouping = self._score_body(buf)[0]
+            if two:
+                self._energy_body(buf, grouping)
+        # the replays write into encoder workspaces that were allocated outside the captures: pinned - around BOTH captures and before the
+        # first, so that none of them can be re-allocated inside one and a failure in either gives every pin back - for as long as these
+        # graphs live
+        with holding([lambda net=net: net.pts_encoder.pin_workspaces(n, N, self.SLOT) for net in self.nets]) as pinned:
+            ent = capture(lambda: self._score_body(buf), bufs=(buf,), warmup=warm)
+            grouping, centre, cvec_s = ent.outs
+            side = capture(lambda: self._energy_body(buf, grouping), stream=self.side) if two else None
+        ent.outs, ent.pinned, ent.extra["side"] = (centre, cvec_s, side.outs if two else None), pinned, side
+        return ent
 
     def _rank_body(self, pred, centre, cvec_e):
         n, K = pred.shape[0], self.K
@@ -267,17 +275,8 @@ class _FrameGraphs:
         torch.cuda.current_stream(pred.device).wait_event(self.ev_e)  # the energy model's embedding (side stream, under the solve)
         if ent is None:
             bufs = (pred.clone(), centre.clone(), cvec_e.clone())
-            self._rank_body(*bufs)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                outs = self._rank_body(*bufs)
-            ent = self._b[key] = (g, bufs, outs)
-        g, bufs, outs = ent
-        for b, v in zip(bufs, (pred, centre, cvec_e)):
-            b.copy_(v)
-        g.replay()
-        return outs
+            ent = self._b[key] = capture(lambda: self._rank_body(*bufs), bufs=bufs, warmup=True)
+        return ent.replay(pred, centre, cvec_e)
 
 
 class TrackingRunner:
@@ -475,49 +474,6 @@ class MultiSequenceTracker:
                       "nfev": int(smp.group_stats[q]["nfev"])}
         self._prev = (live, average_sRT)
         return out
-
-
-def _unpin_score_embed(key, ent):
-    for ws in ent[3]:
-        ws["_pins"] -= 1
-
-
-class _ScoreEmbedGraph:
-    """Graph A of _FrameGraphs for a tracker that has no energy agent: clouds [n,1024,3] -> centres and the score model's per-cloud
-    embedding, one hipGraph per cloud shape (static input, static outputs that the next frame of the shape overwrites)."""
-
-    SLOT = "fixed-step-tracker"
-
-    def __init__(self, snet, T_energy=None):
-        self.snet = snet
-        self.enc = snet.pointnet2_encoder("FixedStepTracker")
-        self._a = ShapeCache(_FrameGraphs.MAX_SHAPES, on_evict=_unpin_score_embed)
-        self.ev_e = None
-        if T_energy is not None:  # `snet` is an ENERGY network that also ranks (FixedStepTracker(sample_from='energy')): as _FrameGraphs.__init__
-            from .sde import SIGMA_MAX, SIGMA_MIN
-            t = torch.full((1,), float(T_energy), device=snet.device)
-            self.tvec_e = snet.pose_score_net.time_embed(t)[0].contiguous()
-            self.sigma_e = (SIGMA_MIN * (SIGMA_MAX / SIGMA_MIN) ** t).contiguous()
-
-    def _body(self, pts):
-        return pts.mean(dim=1), self.snet.pose_score_net.cloud_embed(self.enc.forward(pts, slot=self.SLOT))
-
-    def embed(self, pts):
-        key = (tuple(pts.shape), pts.dtype)
-        ent = self._a.get(key)
-        if ent is None:
-            buf = pts.clone()
-            self._body(buf)  # warm-up outside capture: workspaces, kernel attributes
-            torch.cuda.synchronize()
-            pinned = [self.enc.pin_workspaces(int(buf.shape[0]), int(buf.shape[1]), self.SLOT)]
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                centre, cvec_s = self._body(buf)
-            ent = self._a[key] = (g, buf, (centre, cvec_s, None), pinned)
-        g, buf, outs, _ = ent
-        buf.copy_(pts)
-        g.replay()
-        return outs
 
 
 class FixedStepTracker:
@@ -760,15 +716,14 @@ class FixedStepTracker:
             lk.cvec = a_outs[1]
             lk._write_schedule(net.sampling_eps, 1.0)
         keep = self._prev.clone()
-        self._body(ent)  # warm-up outside capture: kernel attributes, the allocator's blocks
-        torch.cuda.synchronize()
-        self._prev.copy_(keep)  # (the warm-up ran on placeholders and wrote its poses into the slots)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            ent["outs"] = self._body(ent)
-        ent["graph"] = g
+
+        def warm():  # outside capture: kernel attributes, the allocator's blocks
+            self._body(ent)
+            self._prev.copy_(keep)  # (the warm-up ran on placeholders and wrote its poses into the slots)
+        # (no `bufs`: step() fills the static inputs itself - the clouds ahead of the pinned uploads, the tables only when they change)
+        captured = capture(lambda: self._body(ent), warmup=warm, extra=ent)
         self.captures += 1
-        return ent
+        return captured
 
     def step(self, frames):
         net = self.sampling_agent.net
@@ -786,16 +741,17 @@ class FixedStepTracker:
         if self._embed is None:
             if self._two_nets:
                 self.energy_agent.net._need_weights()
-                self._embed = _FrameGraphs(net, self.energy_agent.net, K, max(1, int(self.ratio * K)))
-            else:  # one network: the score model's, or (sample_from 'energy') the energy model's, which then ranks on the same embedding
-                self._embed = _ScoreEmbedGraph(net, T_energy=1e-5 if self.sample_from == "energy" and self.ranker == "energy" else None)
+            # one network: the score model's, or (sample_from 'energy') the energy model's, which then ranks on the same embedding
+            self._embed = _FrameGraphs(net, self.energy_agent.net if self._two_nets else None, K, max(1, int(self.ratio * K)),
+                                       T_energy=1e-5 if self.ranker == "energy" else None)
         key = tuple((i, int(frames[i][0].shape[0])) for i in live)
         pts = torch.cat([frames[i][0].float() for i in live], dim=0)
         a_outs = self._embed.embed(pts)
         replays = 2 if self._two_nets else 1
-        ent = self._b.get(key)
-        if ent is None or ent["a_outs"][1] is not a_outs[1]:  # (graph A of this cloud count was dropped and captured again: new static tensors)
-            ent = self._b[key] = self._capture(key, a_outs, pts)
+        captured = self._b.get(key)
+        if captured is None or captured.extra["a_outs"][1] is not a_outs[1]:  # (graph A of this cloud count was dropped and captured again: new static tensors)
+            captured = self._b[key] = self._capture(key, a_outs, pts)
+        ent = captured.extra  # the sampler, the static tables, their host mirrors and the ring of pinned blocks
         # ---- warm-start table: where every object continues from
         src, fresh = [], False
         for i in live:
@@ -834,9 +790,8 @@ class FixedStepTracker:
         ent["ev"][slot].record(cur)
         if self._two_nets:
             cur.wait_event(self._embed.ev_e)  # the energy model's embedding (side stream)
-        ent["graph"].replay()
         replays += 1
-        init_x, pred, energy, sorted_RTs, average_sRT = (t.clone() for t in ent["outs"])
+        init_x, pred, energy, sorted_RTs, average_sRT = (t.clone() for t in captured.replay())
         smp = ent["smp"]
         self.last_stats = {"replays": replays, "captures": self.captures, "launches": smp.launches, "kernel": smp.kernel_name, "plan": smp.plan,
                            "nfev": smp.nlaunch - 1, "rows": pts.shape[0] * K, "uploaded_src": uploaded, "uploaded_fallback": fresh}

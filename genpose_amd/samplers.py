@@ -7,6 +7,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr, stream_ptr
+from .graphs import PinnedBlock, capture
 from .sde import EPS, SIGMA_MAX, SIGMA_MIN, ve_sde
 
 
@@ -120,8 +121,7 @@ class PCSampler:
         else:
             self.z1 = self.z2 = None
             self.seed_state = torch.zeros(4, dtype=torch.int64, device=self.dev)  # gp_philox::SEED_WORDS uint32: seed, run index, row base, 0
-            self._seed_host = torch.zeros(4, dtype=torch.int64).pin_memory()
-            self._seed_ev = None
+            self._seed_host = PinnedBlock(4, torch.int64)
             self.next_run_index = 0
             self.last_run_index = None
         self.cvec, self.centre = f(B, 768), f(B, 3)
@@ -160,15 +160,11 @@ class PCSampler:
         if not 0 <= base < (1 << 63):
             raise ValueError(f"row_base {base}")
         self.last_run_index = int(run_index)
-        if self._seed_ev is not None:
-            self._seed_ev.synchronize()  # the previous copy out of the pinned words has completed
-        else:
-            self._seed_ev = torch.cuda.Event()
-        h = self._seed_host
-        h[0] = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
-        h[1], h[2], h[3] = int(run_index), base, 0
-        self.seed_state.copy_(h, non_blocking=True)
-        self._seed_ev.record(torch.cuda.current_stream(self.dev))
+
+        def fill(h):
+            h[0] = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
+            h[1], h[2], h[3] = int(run_index), base, 0
+        self._seed_host.send(self.seed_state, fill)
 
     def launch_step(self, i):
         """Launch i of the chain (0 <= i <= n) on the current stream: finishes step i-1 and, for i < n, evaluates the score at t_i."""
@@ -236,18 +232,11 @@ def _replay_captured(smp, restore, graph_events=None):
     """The graph path of a sampler's run().  First run: a warm-up chain outside capture (it sets the kernels' attributes), smp.x put back
     from `restore`, the whole chain captured once.  Every run: the replay, between graph_events' two events where given."""
     if smp.graph is None:
-        smp._launch_all()
-        torch.cuda.synchronize()
-        smp.x.copy_(restore)
-        smp.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(smp.graph):
-            smp._launch_all()
+        # (no `bufs`: run() has filled the sampler's own buffers, which the launch-by-launch path reads as well)
+        smp._captured = capture(smp._launch_all, warmup=lambda: (smp._launch_all(), smp.x.copy_(restore)))
+        smp.graph = smp._captured.graph
         smp.captures += 1
-    if graph_events is not None:
-        graph_events[0].record(torch.cuda.current_stream())
-    smp.graph.replay()
-    if graph_events is not None:
-        graph_events[1].record(torch.cuda.current_stream())
+    smp._captured.replay(events=graph_events)
 
 
 class _ScheduleTable:
@@ -260,8 +249,7 @@ class _ScheduleTable:
         self._sched_len = classes * nlaunch * row
         ntimes = classes * ntimes
         self._table = torch.zeros(self._sched_len + ntimes, device=device)
-        self._host = torch.zeros(self._sched_len + ntimes).pin_memory()
-        self._ev = None
+        self._host = PinnedBlock(self._sched_len + ntimes)
         self._key = None
         self.sched = self._table[: self._sched_len]
         self.t_dev = self._table[self._sched_len:]
@@ -273,15 +261,12 @@ class _ScheduleTable:
         if key == self._key:
             return
         t, sched = schedule()
-        if self._ev is not None:
-            self._ev.synchronize()  # the previous copy out of the pinned block has completed
-        else:
-            self._ev = torch.cuda.Event()
-        h = self._host.numpy()
-        h[: self._sched_len] = sched.reshape(-1)
-        h[self._sched_len:] = t.astype(np.float32).reshape(-1)
-        self._table.copy_(self._host, non_blocking=True)
-        self._ev.record(torch.cuda.current_stream(self.dev))
+
+        def fill(host):
+            h = host.numpy()
+            h[: self._sched_len] = sched.reshape(-1)
+            h[self._sched_len:] = t.astype(np.float32).reshape(-1)
+        self._host.send(self._table, fill)
         self.net.time_embed(self.t_dev, out=self.tvec_all)
         self._key = key
 
@@ -1014,11 +999,7 @@ class ODESampler:
                     if not graphs:
                         self._attempt(traj)  # warm-up outside capture
                         n_done += 1
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        for _ in range(chunk):
-                            self._attempt(traj)
-                    graphs[chunk] = g
+                    graphs[chunk] = capture(lambda: [self._attempt(traj) for _ in range(chunk)]).graph
                     if len(graphs) > self.MAX_GRAPHS:  # bounded cache: drop the least recently captured size that is not in use now
                         for c in list(graphs):
                             if c not in (chunk, self.poll):

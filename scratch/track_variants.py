@@ -39,19 +39,18 @@ def patch(mode):
         key = (tuple(pts.shape), pts.dtype)
         if self._a.get(key) is None:
             return FG._embed_orig(self, pts)  # capture through the shipped path
-        ga, ge, buf, outs, _ = self._a.get(key)
+        ent = self._a.get(key)
         cur = torch.cuda.current_stream(pts.device)
-        buf.copy_(pts)
-        ga.replay()
+        ent.replay(pts)
         if mode == "before":
-            ge.replay()
+            ent.extra["side"].replay()
         self.ev_e.record(cur)
-        return outs
+        return ent.outs
 
     def rank(self, pred, centre, cvec_e):
         if mode == "after":
             key = next(iter(self._a.keys()))
-            self._a.get(key)[1].replay()
+            self._a.get(key).extra["side"].replay()
             self.ev_e.record(torch.cuda.current_stream(pred.device))
         return FG._rank_orig(self, pred, centre, cvec_e)
     FG.embed, FG.rank = embed, rank

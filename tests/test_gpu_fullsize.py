@@ -378,8 +378,8 @@ def test_drop_in_eval_single_as_timed():
         runs.append((pred.clone(), energy.clone(), r["order"].clone(), r["avg_pose"].clone(), data["pts_feat"].clone(),
                      int(sa.net.last_sampler.last_stats["nfev"])))
     torch.cuda.synchronize()
-    assert all(ent.get("graph") is not None for ent in sa.net.pts_encoder._pass_graphs.values())  # the passes are graph replays by now
-    assert all(ent.get("graph") is not None for ent in ea.net.pts_encoder._pass_graphs.values())
+    assert all(ent.graph is not None for ent in sa.net.pts_encoder._pass_graphs.values())  # the passes are graph replays by now
+    assert all(ent.graph is not None for ent in ea.net.pts_encoder._pass_graphs.values())
     for later in runs[1:]:
         for a, b in zip(runs[0][:5], later[:5]):
             assert torch.equal(a, b)

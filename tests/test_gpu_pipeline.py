@@ -287,7 +287,7 @@ def test_tracking_frame_graphs_equal_the_agent_calls():
                 #         stream, which rank() has already ordered after the side stream: no host synchronisation between frames)
                 key = (tuple(pts.shape), pts.dtype)
                 levels = [[f.clone() for f in a.net.pts_encoder._workspace(pts.shape[0], pts.shape[1], tr._graphs.SLOT)["feat"]] for a in (sa, ea)]
-                snaps.append(([t.clone() for t in tr._graphs._a[key][3]], levels))
+                snaps.append(([t.clone() for t in tr._graphs._a[key].outs], levels))
         outs[graphs] = res
         torch.cuda.synchronize()
         if graphs:
