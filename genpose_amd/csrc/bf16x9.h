@@ -4,13 +4,26 @@
 // eight bits of a value that has at most 24).  A product a_i . b_j of two bf16 terms has at most 16 significand bits, so it is exact in
 // fp32; v_mfma_f32_16x16x32_bf16 forms all of them exactly and only its fp32 accumulation rounds - the error class of the fp32 MFMA path,
 // at 16 / 9 of its work rate (the BF16 pipe runs at 16x the fp32 one).  Unlike bf16x3.h (three of the nine products, hi / lo pairs),
-// nothing is dropped.
+// nothing is dropped - in the score trunks (trunk_bf16x9.h, rk45.hip, heun_solve.hip), which form all nine (NPROD = 9, the default).
+// The encoder kernels (sa_bf16x9.hip, sa_lds_bf16x9.hip, sa_groupall_bf16x9.hip) form EIGHT (NPROD = 8): the split is the same nine-term
+// one and each product formed is exact, but lo.lo is not issued.  |mid| <= 2^-8 |x| and |lo| <= 2^-16 |x|, so what is not formed is at
+// most 2^-32 |a b| per multiply - 1 / 256 of an fp32 unit roundoff (2^-24) of that product, and over a K = 512 reduction at most
+// 2^-23 max|a||b| with all signs equal against the 512 x 2^-24 = 2^-15 bound on the fp32 accumulation's own rounding - for 8 / 9 of the
+// matrix-pipe cycles.
 #pragma once
 #include <type_traits>
 
 #include "bf16_split_common.h"
 
+// Products per multiply in the encoder kernels (the score trunks always form nine).  A build-time choice only: -DGP_SA_X9_PRODUCTS=9
+// rebuilds the three kernels with lo.lo issued, for measurements against the full nine.
+#ifndef GP_SA_X9_PRODUCTS
+#define GP_SA_X9_PRODUCTS 8
+#endif
+
 namespace gp_bf16x9 {
+
+constexpr int SA_NPROD = GP_SA_X9_PRODUCTS;
 
 // the three terms of eight values: t[0] = hi, t[1] = mid, t[2] = lo
 struct Split8 {
@@ -44,17 +57,22 @@ __device__ __forceinline__ Split8 split8(const f32x4 a, const f32x4 b) {
 // acc[p] += W . X[p] for NT B tiles sharing one A operand W = (hi, mid, lo): the nine exact products of each tile, SMALLEST TERMS FIRST
 // (lo.lo; lo.mid, mid.lo; lo.hi, mid.mid, hi.lo; mid.hi, hi.mid; hi.hi), so the small terms meet the accumulator before the large
 // ones; the tiles are interleaved product by product (independent accumulation chains for the pipe).
-// TRANSPOSED: acc[p] += X[p] . W, the activations as the A operand - the same nine products in the same order.
-// `first`: acc[p] = W . X[p] - the first product starts from a literal-zero C operand (the bits of 0 + product), no zeroed registers.
-template <int NT, bool TRANSPOSED = false>
+// NPROD = 8: the first of them, lo.lo (q == 0, at most 2^-32 |a b| per multiply: see the top of the file), is not issued; the other eight
+// in the same order.
+// TRANSPOSED: acc[p] += X[p] . W, the activations as the A operand - the same products in the same order.
+// `first`: acc[p] = W . X[p] - the first product issued starts from a literal-zero C operand (the bits of 0 + product), no zeroed
+// registers.
+template <int NT, bool TRANSPOSED = false, int NPROD = 9>
 __device__ __forceinline__ void mma9(const bf16x8 (&w)[3], const Split8 (&x)[NT], f32x4 (&acc)[NT], bool first = false) {
+    static_assert(NPROD == 9 || NPROD == 8, "all nine products, or all but lo.lo");
     constexpr int WA[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0};  // term of W
     constexpr int XB[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0};  // term of X
+    constexpr int Q0 = 9 - NPROD;                       // the first product issued
 #pragma unroll
-    for (int q = 0; q < 9; ++q)
+    for (int q = Q0; q < 9; ++q)
 #pragma unroll
         for (int p = 0; p < NT; ++p) {
-            const f32x4 c = first && q == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[p];
+            const f32x4 c = first && q == Q0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[p];
             if constexpr (TRANSPOSED) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[p].t[XB[q]], w[WA[q]], c, 0, 0, 0);
             else acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[WA[q]], x[p].t[XB[q]], c, 0, 0, 0);
         }
@@ -75,15 +93,15 @@ struct RingNoSide {
 
 // One step of the two-slot LDS ring every bf16x9 kernel streams its weights through (slice = chunks x (hi, mid, lo) x 64 lanes of
 // bf16x8; NTH threads, PER_T slice elements per thread), over the slice in `slot`: for chunk n < NCH of the slice (output chunk N0 + n
-// of acc), the three weight terms (read one chunk ahead) x the two row tiles' split k-block = 18 MFMAs; beside chunk n < PER_T, element
+// of acc), the three weight terms (read one chunk ahead) x the two row tiles' split k-block = 2 NPROD MFMAs; beside chunk n < PER_T, element
 // n of the next slice goes from the registers (`hold`, requested a step ago) to the other slot `dst` (last read one step ago) and
 // element n of the slice after it, `src`, is requested; one barrier.  The caller keeps the ring's position and names the three slices.
 // `first`: the step opens its accumulators (acc = W . X, mma9).
 // `side(n)`: the caller's piece of other work for chunk n - values that are already final (the split of the NEXT k-block, an epilogue of
-// chunks < n of a layer's last step); it must not touch acc[.][N0 + n].  With a side, the chunk's 18 MFMAs take at most two other
+// chunks < n of a layer's last step); it must not touch acc[.][N0 + n].  With a side, the chunk's 2 NPROD MFMAs take at most two other
 // instructions behind each (ring_half_step's placement), so the piece goes BETWEEN them; without one the region is left to the scheduler
 // as before (sa_bf16x9.hip's kernels: several waves per SIMD fill each other's bursts).
-template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NA, class Side = RingNoSide>
+template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NPROD = 9, int NA, class Side = RingNoSide>
 __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], const Split8 (&xs)[2],
                                           f32x4 (&acc)[2][NA], int tid, int lane, bool first = false, Side side = Side()) {
     static_assert(NCH >= PER_T && N0 + NCH <= NA, "every slice element moves beside a chunk");
@@ -103,11 +121,11 @@ __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const
         }
         if constexpr (SIDE) side(n);
         f32x4 an[2] = {acc[0][N0 + n], acc[1][N0 + n]};
-        mma9<2, TRANSPOSED>(wf[n & 1], xs, an, first);
+        mma9<2, TRANSPOSED, NPROD>(wf[n & 1], xs, an, first);
         acc[0][N0 + n] = an[0], acc[1][N0 + n] = an[1];
         if constexpr (SIDE) {
 #pragma unroll
-            for (int i = 0; i < 18; ++i) {
+            for (int i = 0; i < 2 * NPROD; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
                 __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);  // VALU | SALU | VMEM | DS
             }
@@ -121,10 +139,10 @@ __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const
 // `slot` against the KB split k-blocks of the whole input, acc[p] = sum over kb ascending of W[C][kb] . X[kb][p] - each accumulator takes
 // its k-blocks in the order of the k-major step, from a literal zero.  Sub-block u = C KB + kb: the weight terms of u + 1 are read, element
 // u < PER_T of the next slice moves and the slice after it is requested as in ring_step, and `side(kb)` is the caller's piece of other
-// work for this sub-block (an epilogue of accumulators that are already final); the sub-block's 18 MFMAs take at most two other
+// work for this sub-block (an epilogue of accumulators that are already final); the sub-block's 2 NPROD MFMAs take at most two other
 // instructions behind each, so what side() adds goes BETWEEN them (trunk_chain.h's placement: one wave per SIMD, nothing else fills a
 // burst).  Chunk 0 reads chunk 1's first weight terms ahead into `w1`; the barrier follows chunk 1.
-template <int NTH, int PER_T, int KB, int C, class Side>
+template <int NTH, int PER_T, int KB, int C, int NPROD = 9, class Side>
 __device__ __forceinline__ void ring_half_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], bf16x8 (&w1)[3],
                                                const Split8 (&xs)[KB][2], f32x4 (&acc)[2], int tid, int lane, Side side) {
     static_assert(C == 0 || C == 1, "two chunks per slice");
@@ -146,9 +164,9 @@ __device__ __forceinline__ void ring_half_step(const bf16x8 *slot, bf16x8 *dst, 
             hold[u] = src[tid + u * NTH];
         }
         side(kb);
-        mma9<2>(wf[kb & 1], xs[kb], acc, kb == 0);
+        mma9<2, false, NPROD>(wf[kb & 1], xs[kb], acc, kb == 0);
 #pragma unroll
-        for (int i = 0; i < 18; ++i) {
+        for (int i = 0; i < 2 * NPROD; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
             __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);  // VALU | SALU | VMEM | DS
         }

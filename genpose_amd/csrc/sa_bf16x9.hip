@@ -1,7 +1,9 @@
 // Grouping level 2 of the light / dense / lighter encoders (hoisted first layer -> 128 -> 196 -> 256 -> max over the neighbourhood) with the two
-// dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h): every fp32 operand is hi + mid + lo, all nine cross products are
-// exact in fp32 and only the fp32 accumulation rounds - the error class of sa_chain_ring_kernel<128, 196, 256, NS> (sa_mlp.hip), whose job,
-// inputs and [B, 128, 256] output per scale this kernel takes over (encoder precision 'bf16x9'; the fp32 kernel stays selectable as 'f32').
+// dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h): every fp32 operand is hi + mid + lo, EIGHT of the nine cross
+// products are formed (NPROD = SA_NPROD = 8: all but lo.lo, which is at most 2^-32 |a b| per multiply, 1 / 256 of an fp32 roundoff of that
+// product), each exact in fp32, and only the fp32 accumulation rounds - the error class of sa_chain_ring_kernel<128, 196, 256, NS>
+// (sa_mlp.hip), whose job, inputs and [B, 128, 256] output per scale this kernel takes over (encoder precision 'bf16x9'; the fp32 kernel
+// stays selectable as 'f32').  The K tail below is fp32 and whole.
 // Furthest point sampling and the ball queries see coordinates only: centres and neighbourhoods are bit-identical either way.
 //
 // Form: sa_bf16x3.hip's (the row front and back end is sa_rows.h's, shared with that kernel; the ring step is bf16x9.h's, shared with the
@@ -21,8 +23,8 @@
 // its 22 slices (weights.py: pack_sa_bf16x9); the ring consumes 20: of slices 14 and 21 (layer 3's seventh k-block of either half) only the
 // tail's 256 x 4 x 3 terms are read, once - nothing of layer-3 columns >= 196.
 // Budget per workgroup iteration (256 rows; MI355X: v_mfma_f32_16x16x32_bf16 16 cycles, v_mfma_f32_16x16x4_f32 32, LDS 128 B/clk/CU):
-//   MFMA                (4 x 13 + 6 x 16) chunks x 9 products x 2 tiles = 2 664 per wave x 16 cycles + 16 chunks x 2 tiles x 32 cycles
-//                       = 43.6 k cycles per wave (47.2 k with the tail as a seventh k-block) x 2 waves per SIMD = 87 k cycles
+//   MFMA                (4 x 13 + 6 x 16) chunks x 8 products x 2 tiles = 2 368 per wave x 16 cycles + 16 chunks x 2 tiles x 32 cycles
+//                       = 38.9 k cycles per wave (43.6 k with all nine products) x 2 waves per SIMD = 78 k cycles
 //   LDS fragment reads  (52 + 96) KB x 3 terms x 8 waves = 3.5 MB -> 28 k cycles;  ring writes 480 KB
 // so the matrix pipe bounds it.
 #include "bf16x9.h"
@@ -85,7 +87,7 @@ __device__ __forceinline__ void sx_step(SXRing &r, bf16x8 (&hold)[SX_PER_T], con
     const bf16x8 *src = r.w + (size_t)r.snext * SX_SLICE;
     r.par ^= 1;
     r.snext = sx_next_slice(r.snext);
-    ring_step<SX_NTH, SX_PER_T, TRANSPOSED, N0, NCH>(slot, dst, src, hold, xs, acc, tid, lane);
+    ring_step<SX_NTH, SX_PER_T, TRANSPOSED, N0, NCH, SA_NPROD>(slot, dst, src, hold, xs, acc, tid, lane);
 }
 
 template <int NS>

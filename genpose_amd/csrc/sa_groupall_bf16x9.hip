@@ -1,11 +1,12 @@
 // GroupAll level of the light encoder (128 points x [512 features + xyz] -> 256 -> 256 | 384 -> 512 -> max over the cloud, per scale) with ALL
-// THREE dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h), in ONE launch for both scales: the job of
+// THREE dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h; EIGHT of the nine cross products are formed, NPROD =
+// SA_NPROD = 8 - all but lo.lo, at most 2^-32 |a b| per multiply - each exact in fp32), in ONE launch for both scales: the job of
 // gp_point_linear (hoisted feature half of layer 1, both scales) + sa_groupall_ring_kernel<256, 256 | 384, 512> / the 32-row tile kernel
 // (sa_mlp.hip), without the [B, 128, 512] hoisted rows in memory, without a zeroed output and without atomics.
 //
 // Work item = (cloud, scale) = 128 rows.  Form: the score trunk's (trunk_bf16x9.h) - 4 waves per workgroup, one wave per SIMD, two 16-row
-// tiles per wave, so that every weight fragment read from LDS feeds 18 MFMAs and a wave has the 256 + 256 registers of its SIMD for the
-// layer-2 accumulators (192 at C2 = 384) beside half of h1 (64); 8 waves x 16 rows would read each fragment for 9 MFMAs (83 B/clk of the
+// tiles per wave, so that every weight fragment read from LDS feeds 16 MFMAs and a wave has the 256 + 256 registers of its SIMD for the
+// layer-2 accumulators (192 at C2 = 384) beside half of h1 (64); 8 waves x 16 rows would read each fragment for 8 MFMAs (94 B/clk of the
 // LDS's 128) with 256 registers per wave for 160 + operands.  Persistent workgroups, one per CU: workgroup w serves the contiguous items
 // [w I / G, (w + 1) I / G) in ascending order (item = cloud x scales + scale: a workgroup alternates between the scales, whose costs
 // differ by 30 %), and the weight stream runs on from item to item through the 2-slot LDS ring (ring_step): slices of 24 KB = 8 output
@@ -14,13 +15,14 @@
 //                     layer 2 (k-block 4 half + j, j < 4) x (8 chunks h < C2 / 128)          8 | 12
 //   layer 3           (chunk group q < 4) x (k-block kb < C2 / 32)                           32 | 48     transposed (lane = channel)
 // (layer 1 in two halves, each consumed at once as four k-blocks of layer 2: see ga_item)
-// Every accumulator takes its k-blocks in ascending order, nine products smallest first (mma9).  The xyz half of layer 1 and b1 are
+// Every accumulator takes its k-blocks in ascending order, eight products smallest first (mma9).  The xyz half of layer 1 and b1 are
 // added on the VALU in sa_rows.h's order, z + (dot + b1), absolute coordinates (GroupAll: no centring); max over the rows before
 // bias + ReLU (pooling of sa_groupall_ring_kernel: a wave pools its 32 rows in registers, the four waves meet in LDS once per item).
 // A cloud's output depends on nothing but that cloud: an item's arithmetic is the same whichever workgroup serves it, and in whatever
 // position.  With one wave per SIMD nothing hides VALU work, so the splits of the NEXT k-block ride beside the MFMAs of a step
 // (ring_step's side).
-// Per item: (256 + 128 | 192 + 256 | 384) chunk-k-blocks x 18 MFMAs x 16 cycles = 184 k | 240 k cycles per SIMD.
+// Per item: (256 + 128 | 192 + 256 | 384) chunk-k-blocks x 16 MFMAs x 16 cycles = 164 k | 213 k cycles per SIMD (all nine products:
+// 18 MFMAs, 184 k | 240 k).
 #include "bf16x9.h"
 #include "sa_rows.h"
 
@@ -81,7 +83,7 @@ __device__ __forceinline__ void ga_step(GARing &r, bf16x8 (&hold)[GA_PER_T], con
     bf16x8 *dst = r.ring + (r.par ^ 1) * GA_SLICE;
     const bf16x8 *src = r.next();
     r.par ^= 1;
-    ring_step<GA_NTH, GA_PER_T, TRANSPOSED, N0, GA_NCS>(slot, dst, src, hold, xs, acc, tid, lane, first, side);
+    ring_step<GA_NTH, GA_PER_T, TRANSPOSED, N0, GA_NCS, SA_NPROD>(slot, dst, src, hold, xs, acc, tid, lane, first, side);
 }
 
 // Piece q < 8 of the split of a k-block held as two fp32 D fragments per tile (v[p][0], v[p][1]): values 2 (q & 3), + 1 of tile q >> 2.

@@ -1,6 +1,7 @@
 // Grouping level 1 of the light / dense encoders (hoisted first layer -> 64 -> 64 | 96 -> 128 -> max over the neighbourhood) with the two dense
-// layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h: every fp32 operand is hi + mid + lo, all nine cross products are exact
-// in fp32 and only the fp32 accumulation rounds) - the error class of sa_chain_lds_kernel<C1, C2, C3, NS> (sa_mlp.hip), whose job, inputs and
+// layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h: every fp32 operand is hi + mid + lo; EIGHT of the nine cross products
+// are formed, NPROD = SA_NPROD = 8 - all but lo.lo, at most 2^-32 |a b| per multiply, 1 / 256 of an fp32 roundoff of that product - each
+// exact in fp32, and only the fp32 accumulation rounds) - the error class of sa_chain_lds_kernel<C1, C2, C3, NS> (sa_mlp.hip), whose job, inputs and
 // [B, np, C3] output columns per scale this kernel takes over (Pointnet2EncoderHIP(level1 = 'bf16x9'); the fp32 kernel stays the default of the
 // class).  Furthest point sampling and the ball queries see coordinates only: centres and neighbourhoods are bit-identical either way.
 //
@@ -8,14 +9,14 @@
 // that BOTH layers' weights stay LDS-resident as hi / mid / lo (64-64-128: 24 + 48 KB, 64-96-128: 36 + 72 KB), copied once per workgroup
 // before ONE __syncthreads(); the persistent loop over 32-row units has no barrier, so the waves of a SIMD drift apart and fill each other's
 // gaps.  32 rows per wave and iteration (one neighbourhood of 32 or two of 16): every weight fragment read from LDS feeds two B tiles =
-// 18 MFMAs.  Activations stay in registers from the gather to the pooled output; layer 1 on the fp32 VALU with the fp32 kernel's arithmetic,
+// 16 MFMAs.  Activations stay in registers from the gather to the pooled output; layer 1 on the fp32 VALU with the fp32 kernel's arithmetic,
 // z + (dot + b1); the D fragment of a layer IS the next layer's operand (two chunks = one k-block, weights.py: pack_bf16x9's k order); layer
 // 3 transposed (activations as the A operand, lane = channel), max over the points before bias + ReLU.  The hoisted feature rows of k-block
 // kb + 1 are requested while kb is multiplied, those of the NEXT unit's first k-block while layer 3 is.
 // C2 = 64 | 96 and C3 = 128 are whole chunks and whole k-blocks: no padding anywhere, no skipped or zero MFMAs.
-// Budget per 32-row unit (MI355X: v_mfma_f32_16x16x32_bf16 16 cycles): (KB1 NC2 + KB2 8) x 18 MFMAs = 432 (64-64-128) | 648 (64-96-128)
-// = 6.9 k | 10.4 k cycles; LDS fragment reads 3 KB per 18 MFMAs and wave: 8-12 waves x 3 KB / 128 B/clk = 190-290 cycles beside
-// 2-3 x 288 cycles of MFMA per SIMD - the matrix pipe bounds it.
+// Budget per 32-row unit (MI355X: v_mfma_f32_16x16x32_bf16 16 cycles): (KB1 NC2 + KB2 8) x 16 MFMAs = 384 (64-64-128) | 576 (64-96-128)
+// = 6.1 k | 9.2 k cycles (all nine products: 432 | 648 = 6.9 k | 10.4 k); LDS fragment reads 3 KB per 16 MFMAs and wave: 8-12 waves x
+// 3 KB / 128 B/clk = 190-290 cycles beside 2-3 x 256 cycles of MFMA per SIMD - the matrix pipe bounds it.
 #include "bf16x9.h"
 #include "sa_rows.h"
 
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(WPE, W
             for (int n = 0; n < NC2; ++n) {
                 if (!AHEAD) salx_frag(wf[n & 1], w2l + kb * NC2 * 3 * 64, n, lo_);
                 else if (n + 1 < NC2) salx_frag(wf[(n + 1) & 1], w2l + kb * NC2 * 3 * 64, n + 1, lo_);
-                mma9<2>(wf[n & 1], xs, acc2[n], kb == 0);
+                mma9<2, false, SA_NPROD>(wf[n & 1], xs, acc2[n], kb == 0);
                 __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the layer
             }
         }
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(WPE, W
             for (int n = 0; n < NC3; ++n) {
                 if (!AHEAD) salx_frag(wf[n & 1], w3l + kb * NC3 * 3 * 64, n, lo_);
                 else if (n + 1 < NC3) salx_frag(wf[(n + 1) & 1], w3l + kb * NC3 * 3 * 64, n + 1, lo_);
-                mma9<2, true>(wf[n & 1], xs, acc3[n], kb == 0);
+                mma9<2, true, SA_NPROD>(wf[n & 1], xs, acc3[n], kb == 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
