@@ -83,6 +83,8 @@ SIGNATURES = {
     "gp_pc_step_bf16x9": [c_int] * 5 + [NETP] + [P] * 12 + [c_int] + [P] * 3 + [P],
     "gp_pc_step_plan_seeded": [c_int] * 6 + [NETP] + [P] * 11 + [c_int, P],
     "gp_pc_step_bf16x9_seeded": [c_int] * 5 + [NETP] + [P] * 11 + [c_int] + [P] * 3 + [P],
+    "gp_pc_step_bf16x6": [c_int] * 5 + [NETP] + [P] * 12 + [c_int] + [P] * 3 + [P],
+    "gp_pc_step_bf16x6_seeded": [c_int] * 5 + [NETP] + [P] * 11 + [c_int] + [P] * 3 + [P],
     "gp_pc_noise_fill": [P, c_int, c_int, c_int64, c_int64, P, P, P],
     "gp_philox_raw": [c_int64, P, P, P, P],
     "gp_track_warm_start": [c_int, c_int] + [P] * 7 + [P],

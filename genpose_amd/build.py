@@ -18,7 +18,12 @@ SO = os.path.join(LIBDIR, f"libgenpose_hip_{TAG}.so" if TAG else "libgenpose_hip
 OBJDIR = os.path.join(LIBDIR, f"obj_{TAG}") if TAG else LIBDIR
 SOURCES = ["misc.hip", "pn2_ops.hip", "sa_mlp.hip", "scorenet.hip", "rk45.hip", "rank.hip", "preprocess.hip", "score_div.hip", "sa_bf16x3.hip", "sa_bf16x9.hip", "sa_lds_bf16x9.hip", "sa_groupall_bf16x9.hip", "trunk_bf16x3.hip", "trunk_bf16x9.hip", "noise.hip", "pointnet.hip", "heun_likelihood.hip", "heun_solve.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]
-FLAGS += [f for f in os.environ.get("GP_EXTRA_FLAGS", "").split() if f]
+EXTRA = [f for f in os.environ.get("GP_EXTRA_FLAGS", "").split() if f]
+# The encoder's split-bf16 kernels issue six of the nine products of a multiply (csrc/bf16x9.h).  The count is this build's choice: the
+# header's own fallback stays the eight-product form, and GP_EXTRA_FLAGS=-DGP_SA_X9_PRODUCTS=8 (or =9) rebuilds an earlier instruction stream.
+if not any(f.startswith("-DGP_SA_X9_PRODUCTS") for f in EXTRA):
+    FLAGS.append("-DGP_SA_X9_PRODUCTS=6")
+FLAGS += EXTRA
 
 
 def _hipcc():

@@ -34,11 +34,12 @@ DEFAULTS = dict(
     likelihood_grid="geometric",  # (ours) sigma grid of likelihood_solver 'heun': 'geometric' or 'edm' (heun_grid's two)
     heun_grid="geometric",  # (ours) sampler_mode ['heun'] (the fixed-step Heun solver of the probability-flow ODE, samplers.HeunSampler; sampling_steps = its N) and ['dpm2m'] (the DPM-Solver++(2M) solver on the same grid, samplers.Dpm2mSampler: one evaluation per step): the sigma grid - 'geometric' (t uniform) or 'edm' (cond_edm_sampler's rho = 7 discretisation)
     fixed_step_energy=False,  # (ours) True: opt-in - sampler_mode ['heun'] / ['dpm2m'] serve a posenet_mode='energy' agent too: the fixed-step solvers driven by the energy model's score, the gradient of its inner-product energy evaluated inside the kernels (samplers.HeunSampler / Dpm2mSampler(model='energy')); False: such an agent refuses both samplers, as before
+    sampler_products="auto",  # (ours) products per multiply of the PC sampler's split-bf16 chain kernel (PCSampler(products=), csrc/bf16x9.h), read where that kernel applies (score model, 128-row chain plan): 6 = lo.lo, lo.mid and mid.lo are not issued (at most (2^-23 + 2^-32) |a b| per multiply, below the fp32 accumulation's own rounding: still the fp32 kernels' error class, 6 / 9 of the matrix-pipe work), 9 = all nine, bit for bit as before, 'auto' = 6 for a score-model agent of the PC sampler
     ode_trunk=None,  # (ours) 'bf16x9': opt-in exact-product split-bf16 trunk in the ODE sampler's chain-plan stage kernels (ODESampler(trunk=)); None / 'f32mfma': the fp32 MFMA kernels
     encoder_precision="f32",  # (ours) 'bf16x3': opt-in, exploratory split-bf16 products on the 128-196-256 grouping level (csrc/sa_bf16x3.hip)
-    encoder_level2="auto",  # (ours) under encoder_precision 'f32', the arithmetic of grouping level 2 (128-196-256): 'bf16x9' = exact-product split bf16 on the BF16 matrix pipe (csrc/sa_bf16x9.hip, the fp32 kernels' error class; the kernel forms eight of the nine products of the split, each exact - lo.lo, at most 2^-32 |a b| per multiply, is not issued (csrc/bf16x9.h)), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the adaptive ODE sampler (its goldens pin RK45 attempt counts that move with the last bits of the features); encoder_precision='bf16x9' forces it
-    encoder_level1="auto",  # (ours) the arithmetic of grouping level 1 (64-64/96-128): 'bf16x9' = layers 2-3 as exact-product split bf16 with LDS-resident weights (csrc/sa_lds_bf16x9.hip, the fp32 kernels' error class; the kernel forms eight of the nine products of the split, each exact - lo.lo, at most 2^-32 |a b| per multiply, is not issued (csrc/bf16x9.h); batches below Pointnet2EncoderHIP.LEVEL1_BF16X9_MIN_CLOUDS keep the fp32 kernels), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the ODE, Heun and DPM samplers (their goldens pin fp32 bits)
-    encoder_level3="auto",  # (ours) the arithmetic of the GroupAll level (128 points x 512 -> 256 -> 256 | 384 -> 512): 'bf16x9' = all three layers of both scales as exact-product split bf16 in one launch (csrc/sa_groupall_bf16x9.hip, the fp32 kernels' error class; the kernel forms eight of the nine products of the split, each exact - lo.lo, at most 2^-32 |a b| per multiply, is not issued (csrc/bf16x9.h); batches below Pointnet2EncoderHIP.LEVEL3_BF16X9_MIN_CLOUDS keep the fp32 kernels), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the ODE, Heun and DPM samplers (their goldens pin fp32 bits)
+    encoder_level2="auto",  # (ours) under encoder_precision 'f32', the arithmetic of grouping level 2 (128-196-256): 'bf16x9' = exact-product split bf16 on the BF16 matrix pipe (csrc/sa_bf16x9.hip, the fp32 kernels' error class; the kernel forms six of the nine products of the split, each exact - lo.lo, lo.mid and mid.lo, together at most (2^-23 + 2^-32) |a b| per multiply, are not issued (csrc/bf16x9.h)), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the adaptive ODE sampler (its goldens pin RK45 attempt counts that move with the last bits of the features); encoder_precision='bf16x9' forces it
+    encoder_level1="auto",  # (ours) the arithmetic of grouping level 1 (64-64/96-128): 'bf16x9' = layers 2-3 as exact-product split bf16 with LDS-resident weights (csrc/sa_lds_bf16x9.hip, the fp32 kernels' error class; the kernel forms six of the nine products of the split, each exact - lo.lo, lo.mid and mid.lo, together at most (2^-23 + 2^-32) |a b| per multiply, are not issued (csrc/bf16x9.h); batches below Pointnet2EncoderHIP.LEVEL1_BF16X9_MIN_CLOUDS keep the fp32 kernels), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the ODE, Heun and DPM samplers (their goldens pin fp32 bits)
+    encoder_level3="auto",  # (ours) the arithmetic of the GroupAll level (128 points x 512 -> 256 -> 256 | 384 -> 512): 'bf16x9' = all three layers of both scales as exact-product split bf16 in one launch (csrc/sa_groupall_bf16x9.hip, the fp32 kernels' error class; the kernel forms six of the nine products of the split, each exact - lo.lo, lo.mid and mid.lo, together at most (2^-23 + 2^-32) |a b| per multiply, are not issued (csrc/bf16x9.h); batches below Pointnet2EncoderHIP.LEVEL3_BF16X9_MIN_CLOUDS keep the fp32 kernels), 'f32mfma' = the fp32 MFMA kernels, bit for bit as before, 'auto' = 'bf16x9' for an agent of the fixed-step PC sampler, 'f32mfma' for the ODE, Heun and DPM samplers (their goldens pin fp32 bits)
     dist_arith=DEFAULT_DIST_ARITH,  # (ours) contraction convention of the grouping operators' distances, see above
     synset_names=["bottle", "bowl", "camera", "can", "laptop", "mug"], img_size=256, max_eval_num=10000000, results_path="",
 )
@@ -53,6 +54,18 @@ def _pipe_of(cfg, field):
     if v == "auto":
         mode = getattr(cfg, "sampler_mode", None) or ["ode"]
         v = "bf16x9" if mode[0] == "pc" else "f32mfma"
+    return v
+
+
+def sampler_products_of(cfg):
+    """The `products` of PCSampler a namespace asks for: sampler_products 9 | 6, 'auto' = 6 for a score-model agent of the PC sampler and 9
+    for every other (where the sampler ignores it)."""
+    v = getattr(cfg, "sampler_products", "auto")
+    if v not in ("auto", 9, 6):
+        raise ValueError(f"sampler_products {v!r}: 'auto', 9 or 6")
+    if v == "auto":
+        mode = getattr(cfg, "sampler_mode", None) or ["ode"]
+        v = 6 if mode[0] == "pc" and getattr(cfg, "posenet_mode", "score") == "score" else 9
     return v
 
 

@@ -4,19 +4,26 @@
 // eight bits of a value that has at most 24).  A product a_i . b_j of two bf16 terms has at most 16 significand bits, so it is exact in
 // fp32; v_mfma_f32_16x16x32_bf16 forms all of them exactly and only its fp32 accumulation rounds - the error class of the fp32 MFMA path,
 // at 16 / 9 of its work rate (the BF16 pipe runs at 16x the fp32 one).  Unlike bf16x3.h (three of the nine products, hi / lo pairs),
-// nothing is dropped - in the score trunks (trunk_bf16x9.h, rk45.hip, heun_solve.hip), which form all nine (NPROD = 9, the default).
-// The encoder kernels (sa_bf16x9.hip, sa_lds_bf16x9.hip, sa_groupall_bf16x9.hip) form EIGHT (NPROD = 8): the split is the same nine-term
-// one and each product formed is exact, but lo.lo is not issued.  |mid| <= 2^-8 |x| and |lo| <= 2^-16 |x|, so what is not formed is at
-// most 2^-32 |a b| per multiply - 1 / 256 of an fp32 unit roundoff (2^-24) of that product, and over a K = 512 reduction at most
-// 2^-23 max|a||b| with all signs equal against the 512 x 2^-24 = 2^-15 bound on the fp32 accumulation's own rounding - for 8 / 9 of the
-// matrix-pipe cycles.
+// nothing is dropped in the score trunks that pin fp32 bits (trunk_bf16x9.h's nine-product kernels, rk45.hip, heun_solve.hip): they form
+// all nine (NPROD = 9, the default).
+// Fewer products - the split is the same nine-term one and each product formed is exact; with |mid| <= 2^-8 |x| and |lo| <= 2^-16 |x|:
+//   NPROD = 8  lo.lo is not issued: at most 2^-32 |a b| per multiply - 1 / 256 of an fp32 unit roundoff (2^-24) of that product.
+//   NPROD = 6  lo.lo, lo.mid and mid.lo are not issued (the encoder kernels sa_bf16x9.hip, sa_lds_bf16x9.hip, sa_groupall_bf16x9.hip as
+//              the project builds them, and the PC step's six-product kernels of trunk_bf16x9.hip): lo.mid and mid.lo are each at most
+//              2^-24 |a b|, so the three together are at most (2^-23 + 2^-32) |a b| per multiply - K 2^-23 max|a||b| over a reduction
+//              with all signs equal.  The classical bound on the fp32 accumulation's own rounding, K 2^-24 sum |a_i b_i| <= K^2 2^-24
+//              max|a||b|, is K / 2 times that; on random data what is dropped is a random walk of steps ~2^-24 |a b|, two orders of
+//              magnitude below the accumulated rounding (tests/test_x6_products_host.py: against float64 six products stay within
+//              1.1x of nine, and FIVE - lo.hi dropped as well - are ten times worse: six is the boundary).  6 / 9 of the matrix-pipe
+//              cycles.
 #pragma once
 #include <type_traits>
 
 #include "bf16_split_common.h"
 
-// Products per multiply in the encoder kernels (the score trunks always form nine).  A build-time choice only: -DGP_SA_X9_PRODUCTS=9
-// rebuilds the three kernels with lo.lo issued, for measurements against the full nine.
+// Products per multiply in the encoder kernels: 9, 8 or 6.  A build-time choice only.  The project's build (build.py) passes
+// -DGP_SA_X9_PRODUCTS=6; a translation unit compiled without the flag gets the eight-product kernels, and -DGP_SA_X9_PRODUCTS=8 / =9
+// rebuild the earlier instruction streams for measurements against them.  (The score trunks name their count per kernel.)
 #ifndef GP_SA_X9_PRODUCTS
 #define GP_SA_X9_PRODUCTS 8
 #endif
@@ -58,13 +65,14 @@ __device__ __forceinline__ Split8 split8(const f32x4 a, const f32x4 b) {
 // (lo.lo; lo.mid, mid.lo; lo.hi, mid.mid, hi.lo; mid.hi, hi.mid; hi.hi), so the small terms meet the accumulator before the large
 // ones; the tiles are interleaved product by product (independent accumulation chains for the pipe).
 // NPROD = 8: the first of them, lo.lo (q == 0, at most 2^-32 |a b| per multiply: see the top of the file), is not issued; the other eight
-// in the same order.
+// in the same order.  NPROD = 6: neither are lo.mid and mid.lo (q == 1, 2); the other six in the same order - lo.hi, mid.mid, hi.lo,
+// mid.hi, hi.mid, hi.hi.
 // TRANSPOSED: acc[p] += X[p] . W, the activations as the A operand - the same products in the same order.
 // `first`: acc[p] = W . X[p] - the first product issued starts from a literal-zero C operand (the bits of 0 + product), no zeroed
 // registers.
 template <int NT, bool TRANSPOSED = false, int NPROD = 9>
 __device__ __forceinline__ void mma9(const bf16x8 (&w)[3], const Split8 (&x)[NT], f32x4 (&acc)[NT], bool first = false) {
-    static_assert(NPROD == 9 || NPROD == 8, "all nine products, or all but lo.lo");
+    static_assert(NPROD == 9 || NPROD == 8 || NPROD == 6, "all nine products, all but lo.lo, or all but lo.lo, lo.mid and mid.lo");
     constexpr int WA[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0};  // term of W
     constexpr int XB[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0};  // term of X
     constexpr int Q0 = 9 - NPROD;                       // the first product issued
@@ -101,7 +109,9 @@ struct RingNoSide {
 // chunks < n of a layer's last step); it must not touch acc[.][N0 + n].  With a side, the chunk's 2 NPROD MFMAs take at most two other
 // instructions behind each (ring_half_step's placement), so the piece goes BETWEEN them; without one the region is left to the scheduler
 // as before (sa_bf16x9.hip's kernels: several waves per SIMD fill each other's bursts).
-template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NPROD = 9, int NA, class Side = RingNoSide>
+// OTHERS: how many other instructions a side's placement takes behind each MFMA - two; a six-product caller whose side pieces were cut
+// for 18 MFMAs asks for three (12 x 3 = 18 x 2 places per chunk).
+template <int NTH, int PER_T, bool TRANSPOSED, int N0, int NCH, int NPROD = 9, int OTHERS = 2, int NA, class Side = RingNoSide>
 __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], const Split8 (&xs)[2],
                                           f32x4 (&acc)[2][NA], int tid, int lane, bool first = false, Side side = Side()) {
     static_assert(NCH >= PER_T && N0 + NCH <= NA, "every slice element moves beside a chunk");
@@ -127,7 +137,7 @@ __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const
 #pragma unroll
             for (int i = 0; i < 2 * NPROD; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);  // VALU | SALU | VMEM | DS
+                __builtin_amdgcn_sched_group_barrier(0x096, OTHERS, 0);  // VALU | SALU | VMEM | DS
             }
         }
         __builtin_amdgcn_sched_barrier(0);  // one chunk per region: the optimiser would hoist every fragment read of the step
@@ -141,8 +151,8 @@ __device__ __forceinline__ void ring_step(const bf16x8 *slot, bf16x8 *dst, const
 // u < PER_T of the next slice moves and the slice after it is requested as in ring_step, and `side(kb)` is the caller's piece of other
 // work for this sub-block (an epilogue of accumulators that are already final); the sub-block's 2 NPROD MFMAs take at most two other
 // instructions behind each, so what side() adds goes BETWEEN them (trunk_chain.h's placement: one wave per SIMD, nothing else fills a
-// burst).  Chunk 0 reads chunk 1's first weight terms ahead into `w1`; the barrier follows chunk 1.
-template <int NTH, int PER_T, int KB, int C, int NPROD = 9, class Side>
+// burst).  Chunk 0 reads chunk 1's first weight terms ahead into `w1`; the barrier follows chunk 1.  OTHERS: as in ring_step.
+template <int NTH, int PER_T, int KB, int C, int NPROD = 9, int OTHERS = 2, class Side>
 __device__ __forceinline__ void ring_half_step(const bf16x8 *slot, bf16x8 *dst, const bf16x8 *src, bf16x8 (&hold)[PER_T], bf16x8 (&w1)[3],
                                                const Split8 (&xs)[KB][2], f32x4 (&acc)[2], int tid, int lane, Side side) {
     static_assert(C == 0 || C == 1, "two chunks per slice");
@@ -168,7 +178,7 @@ __device__ __forceinline__ void ring_half_step(const bf16x8 *slot, bf16x8 *dst, 
 #pragma unroll
         for (int i = 0; i < 2 * NPROD; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-            __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);  // VALU | SALU | VMEM | DS
+            __builtin_amdgcn_sched_group_barrier(0x096, OTHERS, 0);  // VALU | SALU | VMEM | DS
         }
         __builtin_amdgcn_sched_barrier(0);
     }

@@ -1,7 +1,7 @@
 // Grouping level 2 of the light / dense / lighter encoders (hoisted first layer -> 128 -> 196 -> 256 -> max over the neighbourhood) with the two
-// dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h): every fp32 operand is hi + mid + lo, EIGHT of the nine cross
-// products are formed (NPROD = SA_NPROD = 8: all but lo.lo, which is at most 2^-32 |a b| per multiply, 1 / 256 of an fp32 roundoff of that
-// product), each exact in fp32, and only the fp32 accumulation rounds - the error class of sa_chain_ring_kernel<128, 196, 256, NS>
+// dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h): every fp32 operand is hi + mid + lo, SIX of the nine cross
+// products are formed as the project builds it (NPROD = SA_NPROD = GP_SA_X9_PRODUCTS = 6: all but lo.lo, lo.mid and mid.lo, together at
+// most (2^-23 + 2^-32) |a b| per multiply, below the fp32 accumulation's own rounding; 8 and 9 are measurement builds), each exact in fp32, and only the fp32 accumulation rounds - the error class of sa_chain_ring_kernel<128, 196, 256, NS>
 // (sa_mlp.hip), whose job, inputs and [B, 128, 256] output per scale this kernel takes over (encoder precision 'bf16x9'; the fp32 kernel
 // stays selectable as 'f32').  The K tail below is fp32 and whole.
 // Furthest point sampling and the ball queries see coordinates only: centres and neighbourhoods are bit-identical either way.

@@ -1,6 +1,7 @@
 // GroupAll level of the light encoder (128 points x [512 features + xyz] -> 256 -> 256 | 384 -> 512 -> max over the cloud, per scale) with ALL
-// THREE dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h; EIGHT of the nine cross products are formed, NPROD =
-// SA_NPROD = 8 - all but lo.lo, at most 2^-32 |a b| per multiply - each exact in fp32), in ONE launch for both scales: the job of
+// THREE dense layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h; SIX of the nine cross products are formed as the project builds it, NPROD =
+// SA_NPROD = GP_SA_X9_PRODUCTS = 6 - all but lo.lo, lo.mid and mid.lo, at most (2^-23 + 2^-32) |a b| per multiply - each exact in fp32;
+// with six the kernel keeps 156 B of scratch against 140 B with eight and is still 8 % faster, profiles/x6_products.txt), in ONE launch for both scales: the job of
 // gp_point_linear (hoisted feature half of layer 1, both scales) + sa_groupall_ring_kernel<256, 256 | 384, 512> / the 32-row tile kernel
 // (sa_mlp.hip), without the [B, 128, 512] hoisted rows in memory, without a zeroed output and without atomics.
 //
@@ -15,7 +16,7 @@
 //                     layer 2 (k-block 4 half + j, j < 4) x (8 chunks h < C2 / 128)          8 | 12
 //   layer 3           (chunk group q < 4) x (k-block kb < C2 / 32)                           32 | 48     transposed (lane = channel)
 // (layer 1 in two halves, each consumed at once as four k-blocks of layer 2: see ga_item)
-// Every accumulator takes its k-blocks in ascending order, eight products smallest first (mma9).  The xyz half of layer 1 and b1 are
+// Every accumulator takes its k-blocks in ascending order, the products formed smallest first (mma9).  The xyz half of layer 1 and b1 are
 // added on the VALU in sa_rows.h's order, z + (dot + b1), absolute coordinates (GroupAll: no centring); max over the rows before
 // bias + ReLU (pooling of sa_groupall_ring_kernel: a wave pools its 32 rows in registers, the four waves meet in LDS once per item).
 // A cloud's output depends on nothing but that cloud: an item's arithmetic is the same whichever workgroup serves it, and in whatever

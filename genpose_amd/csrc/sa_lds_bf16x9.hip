@@ -1,6 +1,7 @@
 // Grouping level 1 of the light / dense encoders (hoisted first layer -> 64 -> 64 | 96 -> 128 -> max over the neighbourhood) with the two dense
-// layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h: every fp32 operand is hi + mid + lo; EIGHT of the nine cross products
-// are formed, NPROD = SA_NPROD = 8 - all but lo.lo, at most 2^-32 |a b| per multiply, 1 / 256 of an fp32 roundoff of that product - each
+// layers as EXACT-PRODUCT split bf16 on the BF16 matrix pipe (bf16x9.h: every fp32 operand is hi + mid + lo; SIX of the nine cross products
+// are formed as the project builds it, NPROD = SA_NPROD = GP_SA_X9_PRODUCTS = 6 - all but lo.lo, lo.mid and mid.lo, together at most
+// (2^-23 + 2^-32) |a b| per multiply, below the fp32 accumulation's own rounding; 8 and 9 are measurement builds - each
 // exact in fp32, and only the fp32 accumulation rounds) - the error class of sa_chain_lds_kernel<C1, C2, C3, NS> (sa_mlp.hip), whose job, inputs and
 // [B, np, C3] output columns per scale this kernel takes over (Pointnet2EncoderHIP(level1 = 'bf16x9'); the fp32 kernel stays the default of the
 // class).  Furthest point sampling and the ball queries see coordinates only: centres and neighbourhoods are bit-identical either way.

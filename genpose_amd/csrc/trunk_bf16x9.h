@@ -15,6 +15,8 @@
 // prologue up to the first MFMA (sampler update, slot 0), the part of the tail that does not fit two-per-MFMA (14 runs of 39-49
 // instructions at the chunk ends of pose_encoder.2's last step, 124 before the first head chunk), the head loop's short runs, the last
 // head's last chunk.
+// run<KSIDE, NPROD>: NPROD = 9 is all of the above; NPROD = 6 (the PC step's six-product kernels, trunk_bf16x9.hip) issues six of the nine
+// products of every multiply (bf16x9.h) - 6 336 MFMAs per wave instead of 9 504, the same ring, packs, orders and side pieces.
 //   request : slices 0 and 1 into registers - the caller places it among its own loads (memory returns in order)
 //   stage_request : the staged fp32 operands (w_out, b0, b2, cvec[cloud] + tvec) into registers, for a caller that has work of its own
 //             before run() - issued BEFORE request, they arrive under that work instead of behind the 24 weight loads
@@ -77,13 +79,17 @@ __device__ __forceinline__ void stage_request(X9Staged &sg, const SplitNet &w, c
 // plain form - their f64 stage state leaves no room for the second live split (stages 6 and 7 would take 12-36 B more scratch).
 // 1 (the Heun step): all but pose_encoder.2's tail - with it that kernel parks 117 values in AGPRs instead of 76 and loses what the
 // rest gains.  2 (the PC kernels): all of it.  (profiles/x9_kmajor_under_mfma.txt)
-template <int KSIDE = 0, class Emit, class Staged = std::nullptr_t>
+// NPROD: the products per multiply (bf16x9.h), forwarded to both ring functions - 9 (the default: every kernel whose bits are recorded) or
+// 6 (the PC step's six-product kernels).  With six, a chunk's or sub-block's 12 MFMAs take THREE other instructions behind each: the side
+// pieces above were cut for 18 MFMAs x 2 and find the same 36 places.
+template <int KSIDE = 0, int NPROD = 9, class Emit, class Staged = std::nullptr_t>
 __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *cvec, const float *tvec, int wg_row0, int nrows, int kcand,
                                     const bf16x8 (&first)[X9_PER_T], bf16x8 (&hold)[X9_PER_T], const float (&xv)[X9_RT][POSE],
                                     const int (&row)[X9_RT], Emit emit, const Staged &sg = nullptr) {
     bf16x8 *ring = reinterpret_cast<bf16x8 *>(lds);
     const float *woutl = lds + X9Lds::OFF_WOUT, *b0l = lds + X9Lds::OFF_B0, *b2l = lds + X9Lds::OFF_B2, *cvtl = lds + X9Lds::OFF_CVT;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
+    constexpr int OTHERS = NPROD == 6 ? 3 : 2;
     // ---- staged epilogue operands and slot 0
     if constexpr (std::is_same<Staged, X9Staged>::value) split_stage_store<X9_NT, X9Lds>(lds, sg);
     else split_stage<X9_NT, X9Lds>(lds, w, cvec, tvec, wg_row0, nrows, kcand);
@@ -97,7 +103,7 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
         // the plain form (the text rk45.hip's resource table was taken with): bias + ReLU between the layers, each k-block split before its step
         auto step = [&](const Split8 (&xs)[X9_RT], bool first) {
             const int gs = gstep++;
-            ring_step<X9_NT, X9_PER_T, false, 0, 16>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
+            ring_step<X9_NT, X9_PER_T, false, 0, 16, NPROD, OTHERS>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
                                                      tid, lane, first);
         };
         auto hidden = [&](const float *bias) {
@@ -158,7 +164,7 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
         // the accumulators (no zeroing pass)
         auto step = [&](const Split8 (&xs)[X9_RT], bool first, auto side) {
             const int gs = gstep++;
-            ring_step<X9_NT, X9_PER_T, false, 0, 16>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
+            ring_step<X9_NT, X9_PER_T, false, 0, 16, NPROD, OTHERS>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
                                                      tid, lane, first, side);
         };
         // The k-major layers keep their 256-wide input in fp32 (act) and split it one k-block at a time.  Nothing of that is issued between two
@@ -266,7 +272,7 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
         if (C == 1) ++gstep;
 #pragma unroll
         for (int p = 0; p < X9_RT; ++p) pend[p] = fin[p];
-        ring_half_step<X9_NT, X9_PER_T, 8, C>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, w1, xs_all,
+        ring_half_step<X9_NT, X9_PER_T, 8, C, NPROD, OTHERS>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, w1, xs_all,
                                               fin, tid, lane, side);
     };
     constexpr std::integral_constant<int, 0> c0{};

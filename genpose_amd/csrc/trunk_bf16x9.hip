@@ -32,6 +32,17 @@
 // What is left of the gap to the floor - 80 us at a sustained 1.9 GHz (the clock inside the kernel has not been measured) - is the
 // prologue up to the first MFMA (~1 800 static instructions, both branch arms), barrier drains (one wave per SIMD), the half of the tail
 // that does not fit two-per-MFMA, the head loop's short runs and the last head's last chunk.
+//
+// SIX PRODUCTS (pc_step_chain_kernel_bf16x6 and its seeded twin; gp_pc_step_bf16x6, PCSampler(products=6), what a score-model PC agent
+// runs): the same text with NPROD = 6 - lo.lo, lo.mid and mid.lo are not issued (bf16x9.h: at most (2^-23 + 2^-32) |a b| per multiply,
+// below the fp32 accumulation's own rounding); the weight packs are unchanged (the lo terms are still read for lo.hi and hi.lo).
+//   MFMA                33 x 16 chunks x 6 products x 2 tiles = 6 336 per wave x 16 cycles = 101 k cycles per SIMD (42 us at 2.4 GHz, 53 us
+//                       at 1.9 GHz); SQ_VALU_MFMA_BUSY_CYCLES 101 376 000 per launch against 152 064 000
+// The side pieces keep their places: a chunk's 12 MFMAs take three other instructions behind each where 18 took two (36 places either
+// way).  256 + 255 registers, 22 (seeded: 26) values parked in AGPRs, 0 B of scratch.  Measured (profiles/x6_products.txt): 75.0-75.2 us
+// per launch against 95.6-95.7 us in one alternating session (HIP events around the PC-100 graph, 32 000 rows); MFMA-busy over
+// 4 x busy-CU cycles 0.57 against 0.65 - more of the launch is now the exposed part listed above, which did not shrink.  The Heun, DPM-Solver
+// and RK45 kernels and the nine-product PC kernels keep nine products and their device code: their bits are recorded.
 #include "pc_rows.h"
 #include "trunk_bf16x9.h"
 #include "trunk_chain.h"
@@ -45,10 +56,13 @@ using namespace gp_x9trunk;
 // HEUN (heun_step_chain_kernel_bf16x9; Args = HeunArgs): a launch of the fixed-step Heun solver of the probability-flow ODE
 // (cond_edm_sampler's method, samplers.py:230-290) - PcRows runs the row-local update, the score is stored, there is no partial sum.
 // SOLVER_DPM2M (dpm2m_step_chain_kernel_bf16x9): a launch of the DPM-Solver++(2M) solver (pc_rows.h), the same through PcRows' other update.
-template <bool SEEDED, int SOLVER = SOLVER_PC, class Args = PcArgs>
+// NPROD = 6 (pc_step_chain_kernel_bf16x6, the PC step only): lo.lo, lo.mid and mid.lo are not issued (bf16x9.h) - the same text, weight
+// packs and ring, 6 336 MFMAs per wave instead of 9 504.
+template <bool SEEDED, int SOLVER = SOLVER_PC, class Args = PcArgs, int NPROD = 9>
 __device__ __forceinline__ void pc_step_chain_bf16x9(const Args &a, const SplitNet &w) {
     constexpr bool HEUN = SOLVER != SOLVER_PC;
     static_assert(HEUN == std::is_same<Args, HeunArgs>::value && !(HEUN && SEEDED), "HeunArgs drive the HEUN instantiation");
+    static_assert(NPROD == 9 || !HEUN, "the fixed-step solvers pin fp32 bits: nine products");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), i = a.step;
     const int wg_row0 = blockIdx.x * X9_ROWS;
@@ -66,7 +80,7 @@ __device__ __forceinline__ void pc_step_chain_bf16x9(const Args &a, const SplitN
     // each head's three score components are final once its epilogue is done: stored there, their squares summed in component order
     const float sden = rs.sigma + 1e-7f;
     float q[X9_RT] = {};
-    run<HEUN ? 1 : 2>(lds, w, a.cvec, tvec, wg_row0, a.nrows, a.kcand, first, hold, rs.xv, rs.row,
+    run<HEUN ? 1 : 2, NPROD>(lds, w, a.cvec, tvec, wg_row0, a.nrows, a.kcand, first, hold, rs.xv, rs.row,
         [&](int h, int p, const float (&out)[3]) __attribute__((always_inline)) {
             const float sc[3] = {out[0] / sden, out[1] / sden, out[2] / sden};
             pc_store_score(a, rs.row[p], lane, 3 * h, sc, q[p]);
@@ -78,6 +92,9 @@ __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x9(PcArgs a
 __global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_seeded_kernel_bf16x9(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<true>(a, w); }
 __global__ __launch_bounds__(X9_NT, 1) void heun_step_chain_kernel_bf16x9(HeunArgs a, SplitNet w) { pc_step_chain_bf16x9<false, SOLVER_HEUN>(a, w); }
 __global__ __launch_bounds__(X9_NT, 1) void dpm2m_step_chain_kernel_bf16x9(HeunArgs a, SplitNet w) { pc_step_chain_bf16x9<false, SOLVER_DPM2M>(a, w); }
+// the PC step with six of the nine products (after the nine-product kernels: their device code keeps its place in the file)
+__global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_kernel_bf16x6(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<false, SOLVER_PC, PcArgs, 6>(a, w); }
+__global__ __launch_bounds__(X9_NT, 1) void pc_step_chain_seeded_kernel_bf16x6(PcArgs a, SplitNet w) { pc_step_chain_bf16x9<true, SOLVER_PC, PcArgs, 6>(a, w); }
 
 // stage_request reads the staged fp32 operands with 16-byte loads
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -143,6 +160,25 @@ int gp_pc_step_bf16x9_seeded(int ngroups, int nclouds_per_group, int k, int step
                              const void *w_headx_x9, gp_stream_t s) {
     if ((uint32_t)nsteps >= gp_philox::MAX_STEPS) return GP_EINVAL;
     return launch_pc_bf16x9<pc_step_chain_seeded_kernel_bf16x9>(ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched,
+                                                                reinterpret_cast<const float *>(seed_state), nullptr, centre, x, mean_x, score, partials, traj,
+                                                                gn_ext, gn_rows_total, w_pose0_x9, w_pose2_x9, w_headx_x9, s);
+}
+
+int gp_pc_step_bf16x6(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec, const float *tvec_all,
+                      const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score,
+                      float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
+                      const void *w_headx_x9, gp_stream_t s) {
+    if (!z_predictor) return GP_EINVAL;
+    return launch_pc_bf16x9<pc_step_chain_kernel_bf16x6>(ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched, z_langevin, z_predictor, centre, x,
+                                                         mean_x, score, partials, traj, gn_ext, gn_rows_total, w_pose0_x9, w_pose2_x9, w_headx_x9, s);
+}
+
+int gp_pc_step_bf16x6_seeded(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
+                             const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
+                             float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
+                             const void *w_headx_x9, gp_stream_t s) {
+    if ((uint32_t)nsteps >= gp_philox::MAX_STEPS) return GP_EINVAL;
+    return launch_pc_bf16x9<pc_step_chain_seeded_kernel_bf16x6>(ngroups, nclouds_per_group, k, step, nsteps, net, cvec, tvec_all, sched,
                                                                 reinterpret_cast<const float *>(seed_state), nullptr, centre, x, mean_x, score, partials, traj,
                                                                 gn_ext, gn_rows_total, w_pose0_x9, w_pose2_x9, w_headx_x9, s);
 }

@@ -60,7 +60,7 @@ class PipelinedPCPredictor:
         self.seed = getattr(self.net.cfg, "sampler_seed", None)
         self.runs = 0
         self.smp = [{self.G: PCSampler(self.net.pose_score_net, B, K, num_steps, self.dev, use_graph=True, record_traj=False, groups=self.G,
-                                       precision=self.net._pc_precision(B, K, groups=self.G), seed=self.seed)}
+                                       precision=self.net._pc_precision(B, K, groups=self.G), seed=self.seed, products=self.net._pc_products())}
                     for _ in range(sampler_streams)]
         # furthest point sampling of the NEXT launch group runs on a side stream while the MFMA stages of the current group
         # own the chip: it is a latency-bound chain of 893 block-wide argmax steps per cloud (one workgroup per cloud, tiny
@@ -85,7 +85,7 @@ class PipelinedPCPredictor:
     def _sampler(self, j, g):
         if g not in self.smp[j]:  # ragged tail of a run: fewer batches in the last launch
             self.smp[j][g] = PCSampler(self.net.pose_score_net, self.B1 * g, self.K, self.n, self.dev, use_graph=True, record_traj=False, groups=g,
-                                       precision=self.net._pc_precision(self.B1 * g, self.K, groups=g), seed=self.seed)
+                                       precision=self.net._pc_precision(self.B1 * g, self.K, groups=g), seed=self.seed, products=self.net._pc_products())
         return self.smp[j][g]
 
     def run(self, batches, prior_noise=None, noise=None, out=None):
@@ -301,7 +301,7 @@ class FullPipelinePredictor:
             # cfg.sampler_seed of the score agent (opt-in): noise drawn inside the step kernels; batch i of call number c draws as global
             # rows i * B*K .. with run index c, whatever launch it shares (as PipelinedPCPredictor)
             self._smp[g] = PCSampler(self.snet.pose_score_net, g * self.B, self.K, self.n, self.dev, use_graph=True, record_traj=False, groups=g,
-                                     seed=getattr(self.snet.cfg, "sampler_seed", None))
+                                     seed=getattr(self.snet.cfg, "sampler_seed", None), products=self.snet._pc_products())
         return self._smp[g]
 
     def run(self, pts, prior_noise=None, noise=None):

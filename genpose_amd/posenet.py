@@ -14,7 +14,7 @@ and every cloud owns K consecutive pose rows - this is how PoseNet.pred_func avo
 """
 import torch
 
-from .config import encoder_kwargs_of
+from .config import encoder_kwargs_of, sampler_products_of
 from .encoder import Pointnet2EncoderHIP
 from .graphs import PinnedBlock
 from .lru import ShapeCache
@@ -153,6 +153,11 @@ class GFObjectPose:
             return "f32"
         return "bf16x3" if groups == 1 or ((B // groups) * K) % 128 == 0 else "f32"
 
+    def _pc_products(self):
+        """cfg.sampler_products resolved (config.sampler_products_of): the `products` of every PCSampler built for this agent - here, by the
+        pipelined predictor and by the full pipeline, which therefore agree bit for bit."""
+        return sampler_products_of(self.cfg)
+
     def sample(self, data, sampler, init_x=None, T0=None, noise=None, return_process=True):
         if sampler == "dpm2m":
             # (ours) the fixed-step DPM-Solver++(2M) solve of the same ODE (samplers.Dpm2mSampler): the 'heun' branch's rules
@@ -195,7 +200,8 @@ class GFObjectPose:
                 # self.coupling_group (optional, set by the caller): the batch is sharded over the ranks of that process group and
                 # the Langevin step size is taken over ALL of its rows (PCSampler, "faithful" multi-GPU mode)
                 smp = self._samplers[key] = PCSampler(self.pose_score_net, B, K, n, self.device, record_traj=return_process,
-                                                      coupling_group=coupling, precision=self._pc_precision(B, K, coupling), seed=seed)
+                                                      coupling_group=coupling, precision=self._pc_precision(B, K, coupling), seed=seed,
+                                                      products=self._pc_products())
             z1, z2 = noise if noise is not None else (None, None)
             self.last_sampler = smp  # statistics / timing of the sampler that served the last call
             xs, res = smp.run(cvec, centre, x0, z1, z2)

@@ -27,7 +27,7 @@ class PCSampler:
     """Predictor-corrector sampler state for a fixed (B, K, num_steps): buffers + optional hipGraph of the whole loop."""
 
     def __init__(self, net, B, K, num_steps, device, use_graph=True, record_traj=False, groups=1, coupling_group=None, tile=0, model="score",
-                 precision="f32", trunk=None, seed=None, row_base=None):
+                 precision="f32", trunk=None, seed=None, row_base=None, products=None):
         """B clouds in `groups` independent batches of B/groups clouds laid out back to back: one launch chain serves all of
         them, the batch-mean gradient norm (samplers.py:130-132) stays per batch (gp_pc_step_grouped).
 
@@ -95,15 +95,23 @@ class PCSampler:
         # 'f32mfma' (pc_step_chain_kernel<2>: fp32 MFMA; A/B runs and tests).  Every other plan, model and precision ignores it.
         if trunk not in (None, "bf16x9", "f32mfma"):
             raise ValueError(f"trunk {trunk!r}: 'bf16x9' or 'f32mfma'")
+        # products: how many of the nine cross products the bf16x9 trunk issues - None / 9 (the class default: all nine, the kernels whose
+        # bits are recorded) or 6 (lo.lo, lo.mid and mid.lo are not issued, csrc/bf16x9.h: at most (2^-23 + 2^-32) |a b| per multiply, below
+        # the fp32 accumulation's own rounding; gp_pc_step_bf16x6 and its seeded twin).  Read only where trunk == 'bf16x9' applies; every
+        # other plan, model, precision and trunk ignores it, as they ignore `trunk` (self.products is then None).
+        if products not in (None, 9, 6):
+            raise ValueError(f"products {products!r}: 9 or 6")
         self.trunk = None
         if precision == "f32" and self.model == 0 and self.tile == 128:
             self.trunk = trunk or "bf16x9"
             if self.trunk == "bf16x9":
                 self._x9 = net.w.bf16x9_packs()
+        self.products = (products or 9) if self.trunk == "bf16x9" else None
+        self._x9_entry = "gp_pc_step_bf16x6" if self.products == 6 else "gp_pc_step_bf16x9"
         if precision == "bf16x3":
             self.kernel_name = "pc_step_bf16x3_kernel"
         elif self.trunk == "bf16x9":
-            self.kernel_name = "pc_step_chain_kernel<bf16x9>"
+            self.kernel_name = "pc_step_chain_kernel<bf16x9,6>" if self.products == 6 else "pc_step_chain_kernel<bf16x9>"
         elif self.tile in (16, 32, 64):
             self.kernel_name = ("pc_step_kernel<16,0,split>" if self.hsplit == 3 else f"pc_step_kernel<{self.tile}>" if self.model == 0
                                 else f"pc_step_kernel<{self.tile},energy>")
@@ -174,7 +182,7 @@ class PCSampler:
             bufs = (ptr(self.cvec), ptr(self.tvec_all), ptr(self.sched), ptr(self.seed_state), ptr(self.centre), ptr(self.x), ptr(self.mean_x),
                     ptr(self.score), ptr(self.partials), ptr(self.traj))
             if self.trunk == "bf16x9":
-                _lib.call("gp_pc_step_bf16x9_seeded", *shape, self.net.w.ref(), *bufs, *gn, *(ptr(w) for w in self._x9), stream_ptr())
+                _lib.call(self._x9_entry + "_seeded", *shape, self.net.w.ref(), *bufs, *gn, *(ptr(w) for w in self._x9), stream_ptr())
             else:
                 _lib.call("gp_pc_step_plan_seeded", self.plan, *shape, self.net.w.ref(), *bufs, *gn, stream_ptr())
             return
@@ -185,7 +193,7 @@ class PCSampler:
             _lib.call("gp_pc_step_bf16x3", *shape, *bufs, *(ptr(w) for w in self._bf), ptr(t["b_pose0"]), ptr(t["b_pose2"]), ptr(t["w_out"]),
                       ptr(t["b_out"]), stream_ptr())
         elif self.trunk == "bf16x9":
-            _lib.call("gp_pc_step_bf16x9", *shape, self.net.w.ref(), *bufs, *gn, *(ptr(w) for w in self._x9), stream_ptr())
+            _lib.call(self._x9_entry, *shape, self.net.w.ref(), *bufs, *gn, *(ptr(w) for w in self._x9), stream_ptr())
         else:
             _lib.call("gp_pc_step_plan", self.model, self.plan, *shape, self.net.w.ref(), *bufs, *gn, stream_ptr())
 

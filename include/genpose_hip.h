@@ -382,6 +382,14 @@ int gp_pc_step_bf16x9(int ngroups, int nclouds_per_group, int k, int step, int n
                       const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score,
                       float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
                       const void *w_headx_x9, gp_stream_t s);
+/* gp_pc_step_bf16x9 with SIX of the nine products of every multiply (csrc/bf16x9.h: lo.lo, lo.mid and mid.lo are not issued - at most
+ * (2^-23 + 2^-32) |a b| per multiply, below the fp32 accumulation's own rounding; still the fp32 error class, 6 / 9 of the matrix-pipe
+ * work).  Arguments, weight packs (the lo terms are still read), plan, alignment rule and results contract are gp_pc_step_bf16x9's; the bits
+ * are its own.  What a score-model PC agent takes by default (config.sampler_products). */
+int gp_pc_step_bf16x6(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec, const float *tvec_all,
+                      const float *sched, const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score,
+                      float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
+                      const void *w_headx_x9, gp_stream_t s);
 int gp_pc_step_bf16x3(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const float *cvec, const float *tvec_all, const float *sched,
                       const float *z_langevin, const float *z_predictor, const float *centre, float *x, float *mean_x, float *score, float *partials,
                       float *traj, const void *w_pose0_split, const void *w_pose2_split, const void *w_headx_split, const float *b_pose0, const float *b_pose2,
@@ -423,6 +431,11 @@ int gp_pc_step_plan_seeded(int tile, int ngroups, int nclouds_per_group, int k, 
                            const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
                            float *partials, float *traj, const float *gn_ext, int gn_rows_total, gp_stream_t s);
 int gp_pc_step_bf16x9_seeded(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
+                             const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
+                             float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
+                             const void *w_headx_x9, gp_stream_t s);
+/* gp_pc_step_bf16x6 with seed_state in place of the noise buffers, as gp_pc_step_bf16x9_seeded is to gp_pc_step_bf16x9. */
+int gp_pc_step_bf16x6_seeded(int ngroups, int nclouds_per_group, int k, int step, int nsteps, const gp_scorenet *net, const float *cvec,
                              const float *tvec_all, const float *sched, const void *seed_state, const float *centre, float *x, float *mean_x, float *score,
                              float *partials, float *traj, const float *gn_ext, int gn_rows_total, const void *w_pose0_x9, const void *w_pose2_x9,
                              const void *w_headx_x9, gp_stream_t s);

@@ -8,7 +8,9 @@ built with GP_BUILD_TAG, genpose_amd/build.py); arms are compared by running thi
   RK45     wall clock around ODESampler(trunk='bf16x9').run() from T0 = 0.15 (host polling included)
   --pmc N  instead of all that: N full PC launches at this shape, one by one, no graph (for a rocprofv3 --pmc pass)
 
-    python scratch/x9_kmajor_measure.py [--reps 11] [--warmup 2] [--pmc N] [--label NAME]
+  --products 6   the PC arms on the six-product kernel (PCSampler(products=6)); --only-pc skips the Heun and RK45 arms
+
+    python scratch/x9_kmajor_measure.py [--reps 11] [--warmup 2] [--pmc N] [--label NAME] [--products 9|6] [--only-pc]
 """
 import argparse
 import os
@@ -46,6 +48,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pmc", type=int, default=0)
     ap.add_argument("--label", default=os.path.basename(os.environ.get("GENPOSE_HIP_LIB", "libgenpose_hip.so")))
+    ap.add_argument("--products", type=int, default=9, choices=(9, 6))
+    ap.add_argument("--only-pc", action="store_true")
     args = ap.parse_args()
     from genpose_amd.samplers import HeunSampler, ODESampler, PCSampler
     from genpose_amd.scorenet import ScoreNetHIP
@@ -60,7 +64,7 @@ def main():
     tag = f"[{args.label}]"
 
     if args.pmc:
-        pc = PCSampler(net, B, K, N_PC, "cuda", groups=G, tile=128, trunk="bf16x9", use_graph=False)
+        pc = PCSampler(net, B, K, N_PC, "cuda", groups=G, tile=128, trunk="bf16x9", use_graph=False, products=args.products)
         pc.cvec.copy_(cvec), pc.centre.copy_(centre), pc.x.copy_(x0), pc.z1.copy_(z1), pc.z2.copy_(z2)
         for i in range(args.pmc):
             pc.launch_step(i)
@@ -69,8 +73,8 @@ def main():
         return
 
     # ---- PC-100
-    pc = PCSampler(net, B, K, N_PC, "cuda", groups=G, tile=128, trunk="bf16x9")
-    assert pc.kernel_name == "pc_step_chain_kernel<bf16x9>"
+    pc = PCSampler(net, B, K, N_PC, "cuda", groups=G, tile=128, trunk="bf16x9", products=args.products)
+    assert pc.kernel_name == ("pc_step_chain_kernel<bf16x9,6>" if args.products == 6 else "pc_step_chain_kernel<bf16x9>")
     pc.run(cvec, centre, x0, z1, z2)  # captures
     torch.cuda.synchronize()
     chk = pc.mean_x.double().abs().sum().item()
@@ -86,6 +90,8 @@ def main():
     f = statistics.median(fin)
     print(f"{tag} PC-{N_PC} chain ({N_PC + 1} launches) {_fmt(chain)}   finish launch {_fmt(fin, 1e3, 'us')}")
     print(f"{tag}   per full launch (chain - finish) / {N_PC}: {_fmt([(t - f) / N_PC for t in chain], 1e3, 'us')}   sum |mean_x| {chk!r}")
+    if args.only_pc:
+        return
     # ---- Heun, 18 steps
     hs = HeunSampler(net, B, K, N_HEUN, "cuda", groups=G, tile=128)
     assert hs.kernel_name == "heun_step_chain_kernel<bf16x9>"
