@@ -71,6 +71,7 @@ SIGNATURES = {
     "gp_pc_step": [c_int, c_int, c_int, c_int, NETP] + [P] * 11 + [P],
     "gp_roi_to_cloud": [c_int, c_int, c_int, c_int, P, P, P, c_float, c_float, c_float, c_float, P, P, P, P],
     "gp_cloud_sample": [c_int, c_int, c_int, P, P, P, P, P],
+    "gp_roi_sample_seeded": [c_int] * 5 + [P, P, P] + [c_float] * 4 + [P] * 5 + [P],
     "gp_score_div": [c_int, c_int, NETP, P, P, P, P, P, P, P, P],
     "gp_energy_score": [c_int, c_int, NETP, P, P, P, P, P, P, P],
     "gp_score_div_exact": [c_int, c_int, NETP, P, P, P, P, P, P, P],

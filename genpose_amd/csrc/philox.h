@@ -13,6 +13,13 @@
 // the same layout with the step field RESERVED: step = PRIOR_STEP = 2^29 - 1, stream 0, run index = the FRAME index, global row =
 // (sequence * objects per frame + object) * K + candidate.  The seeded PC samplers take nsteps < 2^29, so their steps end at 2^29 - 2:
 // no PC draw of a sampler shares a (counter, key) with the prior.
+// THE DEPTH FRONT END'S DRAW (gp_roi_sample_seeded, preprocess.hip: which n_pts of a detection's c valid pixels form its cloud;
+// genpose_amd.preprocess.seeded_ranks restates it) takes the reserved step with STREAM 1, block 0.  It uses the generator as the round
+// function F(u, r) of a Feistel network, not as a source of normals: F = output word 0 of the block with
+//     ctr[0] = u (the half of the Feistel state that is read)      ctr[1] = (slot & 0xFFFFFF) | r << 24      (round r < 8)
+//     ctr[2] = run index (the FRAME index)                         ctr[3] = PRIOR_STEP << 3 | 1 << 2 | 0
+// slot = the detection's global slot = seed state word [4] + instance of the launch (a tracker: sequence * objects per frame + object).
+// The prior draws on stream 0 of that step and no PC step reaches it, so the stream bit alone keeps these (counter, key) apart from both.
 // One row, stream and step take three blocks = 12 words w[0..11]; pair k = (w[2k], w[2k+1]) gives
 //     u1 = ((w[2k] >> 8) + 1) * 2^-24,  u2 = ((w[2k+1] >> 8) + 1) * 2^-24        both in (0, 1]
 //     z[2k] = sqrt(-2 log u1) * cos(2 pi u2),  z[2k+1] = sqrt(-2 log u1) * sin(2 pi u2)
@@ -29,6 +36,7 @@ constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0x
 constexpr int STREAM_LANGEVIN = 0, STREAM_PREDICTOR = 1;
 constexpr uint32_t MAX_STEPS = 1u << 29;
 constexpr uint32_t PRIOR_STEP = MAX_STEPS - 1;  // the tracker's prior (header comment)
+constexpr int STREAM_PRIOR = 0, STREAM_FRONT_END = 1;  // the two users of the reserved step
 
 // The seed state in device memory (8 words, written by the host in stream order before a replay; the kernels only read it):
 //     [0], [1] seed lo / hi   [2] run index   [3] 0   [4], [5] row base lo / hi (global row = row base + row of the launch)   [6], [7] 0

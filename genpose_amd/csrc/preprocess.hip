@@ -4,6 +4,7 @@
 // pixels (depth_to_pcl, :107-118) in raster order, then sample_points (:120-133).  Byte-sized work: one workgroup per
 // detection, compaction in raster order of the crop so that the points come out in the reference's order.
 #include "gp_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -50,6 +51,13 @@ __device__ __forceinline__ RoiPixel roi_pixel(const RoiArgs &a, int inst, long l
     return p;
 }
 
+// depth_to_pcl, all float32: (x - cx) * d / fx, (y - cy) * d / fy, d; then / 1000
+__device__ __forceinline__ void roi_point(const RoiArgs &a, const RoiPixel &p, float *o) {
+    o[0] = (((float)p.sx - a.cx) * p.d / a.fx) / 1000.0f;
+    o[1] = (((float)p.sy - a.cy) * p.d / a.fy) / 1000.0f;
+    o[2] = p.d / 1000.0f;
+}
+
 __global__ __launch_bounds__(64 * ROI_WAVES) void roi_cloud_kernel(RoiArgs a) {
     __shared__ int wave_tot[ROI_WAVES], wave_dep[ROI_WAVES];
     const int inst = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -77,13 +85,7 @@ __global__ __launch_bounds__(64 * ROI_WAVES) void roi_cloud_kernel(RoiArgs a) {
                     cnt += __popcll(bal);
                     dep += __popcll(__ballot(p.has_depth));
                 } else {
-                    if (p.valid) {
-                        // depth_to_pcl, all float32: (x - cx) * d / fx, (y - cy) * d / fy, d; then / 1000
-                        float *o = out + (size_t)(off + __popcll(bal & ((1ull << lane) - 1))) * 3;
-                        o[0] = (((float)p.sx - a.cx) * p.d / a.fx) / 1000.0f;
-                        o[1] = (((float)p.sy - a.cy) * p.d / a.fy) / 1000.0f;
-                        o[2] = p.d / 1000.0f;
-                    }
+                    if (p.valid) roi_point(a, p, out + (size_t)(off + __popcll(bal & ((1ull << lane) - 1))) * 3);
                     off += __popcll(bal);
                 }
             }
@@ -111,6 +113,116 @@ __global__ void cloud_sample_kernel(int cap, int npts, const float *__restrict__
     o[0] = s[0], o[1] = s[1], o[2] = s[2];
 }
 
+// ---- gp_roi_sample_seeded: depth + masks -> the SAMPLED [n_pts, 3] clouds in one launch, no [img*img, 3] buffer in between.
+// Pass 1 is roi_cloud_kernel's counting pass on the same roi_pixel, except that every (crop row, 64-column segment) keeps its ballot of
+// valid pixels in LDS; an exclusive scan of the segments' popcounts in raster order gives every segment its base rank and the workgroup
+// c (valid pixels) and d (pixels with depth).  Pass 2: output row k takes the valid pixel of rank
+//     c < n: k % c (sample_points' tiling)     c == n: k     c > n: sigma(k)
+// sigma: a keyed bijection of [0, c) - cycle walking over an alternating Feistel network of b = max(2, bit_length(c - 1)) bits whose
+// round function is word 0 of a Philox block (philox.h, "THE DEPTH FRONT END'S DRAW") - so the n ranks are distinct by construction.
+// The rank's segment is found by binary search in the scanned table, its column is the (rank - base)-th set bit of the ballot, the pixel
+// is recomputed and written with roi_cloud_kernel's float expressions (roi_point): row k is bit for bit row `rank` of gp_roi_to_cloud.
+constexpr int SAMPLE_MAX_IMG = 512;  // 512 rows x 8 segments: 32 KB of ballots + 16 KB of base ranks in LDS
+constexpr int FEISTEL_ROUNDS = 8;
+
+__device__ __forceinline__ uint32_t feistel_f(const gp_philox::Seed &sd, uint32_t slot, uint32_t u, uint32_t r) {
+    uint32_t w[4] = {u, (slot & 0xFFFFFFu) | r << 24, sd.run, gp_philox::PRIOR_STEP << 3 | (uint32_t)gp_philox::STREAM_FRONT_END << 2};
+    gp_philox::philox4x32_10(w, sd.k0, sd.k1);
+    return w[0];
+}
+
+__device__ __forceinline__ uint32_t seeded_rank(const gp_philox::Seed &sd, uint32_t slot, uint32_t c, uint32_t k) {  // c > n > k
+    const int b = max(2, 32 - __clz((int)(c - 1))), ha = b / 2, hb = b - ha;
+    const uint32_t ma = (1u << ha) - 1, mb = (1u << hb) - 1;
+    uint32_t x = k;
+    do {  // (the walk stays on the cycle of a permutation of [0, 2^b) that holds k < c, so it ends; 2^b <= 2 c)
+        uint32_t a = x >> hb, v = x & mb;
+#pragma unroll 1
+        for (uint32_t r = 0; r < FEISTEL_ROUNDS; r += 2) {
+            a ^= feistel_f(sd, slot, v, r) & ma;
+            v ^= feistel_f(sd, slot, a, r + 1) & mb;
+        }
+        x = a << hb | v;
+    } while (x >= c);
+    return x;
+}
+
+__global__ __launch_bounds__(64 * ROI_WAVES) void roi_sample_kernel(RoiArgs a, const uint32_t *__restrict__ seed, int npts, uint8_t *__restrict__ valid) {
+    extern __shared__ unsigned long long seg_bal[];  // [nseg] ballots, then [nseg] int base ranks
+    __shared__ int wave_tot[ROI_WAVES], wave_dep[ROI_WAVES];
+    const int inst = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int segs = (a.img + 63) >> 6, nseg = a.img * segs;
+    int *seg_base = reinterpret_cast<int *>(seg_bal + nseg);
+    const double *M = a.minv + (size_t)inst * 6;
+    const double m00 = M[0], m01 = M[1], m02 = M[2], m10 = M[3], m11 = M[4], m12 = M[5];
+    // ---- pass 1: the segments go round the waves
+    int dep = 0;
+    for (int s = wave; s < nseg; s += ROI_WAVES) {
+        const int y = s / segs, x0 = (s - y * segs) << 6;
+        const long long X0 = llrint((m01 * y + m02) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
+        const long long Y0 = llrint((m11 * y + m12) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
+        const RoiPixel p = roi_pixel(a, inst, X0, Y0, m00, m10, x0 + lane);
+        const unsigned long long bal = __ballot(p.valid);
+        dep += __popcll(__ballot(p.has_depth));
+        if (lane == 0) seg_bal[s] = bal;
+    }
+    if (lane == 0) wave_dep[wave] = dep;
+    __syncthreads();
+    // ---- exclusive scan of the popcounts in raster order: a thread owns `per` consecutive segments
+    const int per = (nseg + 64 * ROI_WAVES - 1) / (64 * ROI_WAVES), s0 = tid * per;
+    int local = 0;
+    for (int j = 0; j < per; ++j)
+        if (s0 + j < nseg) local += __popcll(seg_bal[s0 + j]);
+    int inc = local;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    int run = inc - local, c = 0, d = 0;
+    for (int w = 0; w < ROI_WAVES; ++w) {
+        if (w < wave) run += wave_tot[w];
+        c += wave_tot[w], d += wave_dep[w];
+    }
+    for (int j = 0; j < per; ++j)
+        if (s0 + j < nseg) {
+            seg_base[s0 + j] = run;
+            run += __popcll(seg_bal[s0 + j]);
+        }
+    __syncthreads();
+    const bool ok = c > 1 && d > 1;  // evaluation_single.py:201-208
+    if (tid == 0) a.count[inst] = c, a.depth_count[inst] = d, valid[inst] = ok;
+    // ---- pass 2
+    float *out = a.pcl + (size_t)inst * npts * 3;
+    const gp_philox::Seed sd = gp_philox::load_seed(seed);
+    const uint32_t slot = (uint32_t)sd.row_base + (uint32_t)inst;
+    for (int k = tid; k < npts; k += 64 * ROI_WAVES) {
+        float *o = out + (size_t)k * 3;
+        if (!ok) {
+            o[0] = o[1] = o[2] = 0.f;
+            continue;
+        }
+        const int rank = c < npts ? k % c : (c == npts ? k : (int)seeded_rank(sd, slot, (uint32_t)c, (uint32_t)k));
+        int lo = 0, hi = nseg - 1;  // the last segment whose base rank is <= rank (it holds the rank: the next base is above it)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (seg_base[mid] <= rank) lo = mid; else hi = mid - 1;
+        }
+        unsigned long long m = seg_bal[lo];
+        int j = rank - seg_base[lo], pos = 0;  // the j-th set bit of the ballot
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1) {
+            const int below = __popcll(m & ((1ull << w) - 1));
+            if (j >= below) j -= below, m >>= w, pos += w;
+        }
+        const int y = lo / segs, x = ((lo - y * segs) << 6) + pos;
+        const long long X0 = llrint((m01 * y + m02) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
+        const long long Y0 = llrint((m11 * y + m12) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
+        roi_point(a, roi_pixel(a, inst, X0, Y0, m00, m10, x), o);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -129,6 +241,19 @@ int gp_cloud_sample(int ninst, int cap, int npts, const float *pcl, const int32_
     if (ninst < 0 || cap <= 0 || npts <= 0 || !pcl || !count || !out) return GP_EINVAL;
     if (ninst == 0) return GP_OK;
     hipLaunchKernelGGL(cloud_sample_kernel, dim3((npts + 255) / 256, ninst), dim3(256), 0, (hipStream_t)s, cap, npts, pcl, count, ids, out);
+    return gp_launch_status();
+}
+
+int gp_roi_sample_seeded(int h, int w, int ninst, int img, int npts, const uint16_t *depth, const uint8_t *masks, const double *minv, float fx,
+                         float fy, float cx, float cy, const uint32_t *seed_state, float *out, int32_t *count, int32_t *depth_count, uint8_t *valid,
+                         gp_stream_t s) {
+    if (h <= 0 || w <= 0 || ninst < 0 || img <= 0 || npts <= 0 || !depth || !masks || !minv || !seed_state || !out || !count || !depth_count || !valid)
+        return GP_EINVAL;
+    if (h > 32767 || w > 32767 || img > SAMPLE_MAX_IMG) return GP_EINVAL;
+    if (ninst == 0) return GP_OK;
+    RoiArgs a{h, w, ninst, img, depth, masks, minv, fx, fy, cx, cy, out, count, depth_count};
+    const size_t lds = (size_t)img * ((img + 63) / 64) * (sizeof(unsigned long long) + sizeof(int));
+    hipLaunchKernelGGL(roi_sample_kernel, dim3(ninst), dim3(64 * ROI_WAVES), lds, (hipStream_t)s, a, seed_state, npts, valid);
     return gp_launch_status();
 }
 

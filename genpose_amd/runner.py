@@ -67,6 +67,7 @@ class SingleFrameRunner:
                                  + ("" if energy_agent is None else f", got {energy_agent.cfg.posenet_mode!r}"))
         self.score_agent, self.energy_agent, self.ranker, self.sample_from = score_agent, energy_agent, ranker, sample_from
         self.repeat_num, self.T0, self.batch_size, self.ratio = repeat_num, T0, batch_size, ratio
+        self.depth_front_end = None  # infer_depth's preprocess.DepthToClouds (assign one for other intrinsics / crop size / cloud size)
 
     def infer_tensors(self, clouds, sym=None):
         """clouds: device tensor [n,1024,3] -> dict of device tensors with leading dim n (usable under ShardedInference).
@@ -111,6 +112,23 @@ class SingleFrameRunner:
         clouds = torch.as_tensor(np.asarray(clouds), dtype=torch.float32).to(device)
         return {k: v.cpu().numpy() for k, v in (self.infer_tensors(clouds) if sym is None else self.infer_tensors(clouds, sym)).items()}
 
+    def infer_depth(self, depth, masks, rois, class_ids, seed=0, frame=0):
+        """A depth frame and its detections (the inputs of preprocess.DepthToClouds) -> infer_tensors' dict on ALL n detections, plus
+        `valid` [n] uint8, `cat_id` [n] (class_ids - 1), `count` and `depth_count` [n]; device tensors throughout.  The clouds come from
+        DepthToClouds.device_clouds (self.depth_front_end; a default one on first use): one launch, the sampled pixels a function of
+        (seed, frame, detection index), no count read back.  A detection the reference skips (valid = 0: its cloud is all zeros) runs through
+        the networks with the rest and gets the identity as average_sRT, the reference's f_sRT[i] = identity - by a device-side select."""
+        from .preprocess import DepthToClouds
+        if self.depth_front_end is None:
+            self.depth_front_end = DepthToClouds()
+        fe = self.depth_front_end.device_clouds(depth, masks, rois, seed, frame)
+        out = self.infer_tensors(fe["points"])
+        if "average_sRT" in out:
+            avg = out["average_sRT"]
+            out["average_sRT"] = torch.where(fe["valid"].bool().view(-1, 1, 1), avg, torch.eye(4, dtype=avg.dtype, device=avg.device))
+        out["valid"], out["count"], out["depth_count"] = fe["valid"], fe["count"], fe["depth_count"]
+        out["cat_id"] = torch.as_tensor(np.asarray(class_ids), dtype=torch.int64).to(fe["valid"].device) - 1
+        return out
 
     def evaluate(self, detect_result, out_dir=None, degree_thresholds=tuple(range(0, 46)), shift_thresholds=tuple(i / 2 for i in range(21)),
                  iou_thresholds=tuple(i / 100 for i in range(101)), pooling_mode="average", ranker="energy_ranker"):

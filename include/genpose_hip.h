@@ -66,6 +66,22 @@ int gp_arith_default(void); /* the GP_ARITH_DEFAULT this library was built with 
 int gp_roi_to_cloud(int h, int w, int ninst, int img, const uint16_t *depth, const uint8_t *masks, const double *minv, float fx, float fy,
                     float cx, float cy, float *pcl, int32_t *count, int32_t *depth_count, gp_stream_t s);
 int gp_cloud_sample(int ninst, int cap, int npts, const float *pcl, const int32_t *count, const int32_t *ids, float *out, gp_stream_t s);
+/* gp_roi_sample_seeded (ours): the two above in ONE launch with the draw made on the device - depth + masks -> out [ninst][npts][3], no
+ *   [ninst][img*img][3] buffer, no count read back, no host permutation.  depth, masks, minv, the intrinsics, count and depth_count as in
+ *   gp_roi_to_cloud; valid [ninst] uint8 = count > 1 && depth_count > 1 (the reference's skip, :201-208, as a device flag); a detection
+ *   with valid = 0 gets all-zero rows.  Row k of a valid detection with c = count is, bit for bit, row rank(k) of what gp_roi_to_cloud
+ *   writes for it:  c < npts: rank = k % c (sample_points' tiling);  c == npts: rank = k;  c > npts: rank = sigma(k), a keyed bijection of
+ *   [0, c) (cycle walking over an 8-round alternating Feistel network on max(2, bit_length(c - 1)) bits whose round function is a
+ *   Philox4x32-10 block: genpose_amd/csrc/philox.h, "the depth front end's draw"; genpose_amd.preprocess.seeded_ranks restates it in
+ *   numpy), so the npts pixels are distinct by construction.  NO random-number parity with numpy's permutation is claimed.
+ *   seed_state: the 8 uint32 words of the seeded samplers in device memory ([0], [1] seed lo / hi, [2] run = the frame index, [4] the
+ *   slot of detection 0: detection i draws as global slot [4] + i, whatever shares its launch); only read.
+ *   img <= 512 (the per-segment ballots and base ranks live in LDS: 12 bytes per 64 crop pixels of a row, 48 KB at 512).  NULL pointers,
+ *   npts <= 0, img outside [1, 512] or h, w outside [1, 32767]: GP_EINVAL, nothing written; ninst == 0: GP_OK.  One 16-wave workgroup per
+ *   detection; no allocation, no synchronisation, no host read: capturable. */
+int gp_roi_sample_seeded(int h, int w, int ninst, int img, int npts, const uint16_t *depth, const uint8_t *masks, const double *minv, float fx,
+                         float fy, float cx, float cy, const uint32_t *seed_state, float *out, int32_t *count, int32_t *depth_count, uint8_t *valid,
+                         gp_stream_t s);
 
 /* Library / device identification: returns ABI version; writes gcnArchName of the current device. */
 int gp_version(void);
