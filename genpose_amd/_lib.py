@@ -72,6 +72,7 @@ SIGNATURES = {
     "gp_roi_to_cloud": [c_int, c_int, c_int, c_int, P, P, P, c_float, c_float, c_float, c_float, P, P, P, P],
     "gp_cloud_sample": [c_int, c_int, c_int, P, P, P, P, P],
     "gp_roi_sample_seeded": [c_int] * 5 + [P, P, P] + [c_float] * 4 + [P] * 5 + [P],
+    "gp_roi_sample_frames": [c_int] * 6 + [P, P, c_int64] + [P] * 4 + [c_float] * 4 + [P] * 5 + [P],
     "gp_score_div": [c_int, c_int, NETP, P, P, P, P, P, P, P, P],
     "gp_energy_score": [c_int, c_int, NETP, P, P, P, P, P, P, P],
     "gp_score_div_exact": [c_int, c_int, NETP, P, P, P, P, P, P, P],

@@ -32,7 +32,15 @@ struct RoiPixel {
     float d;
 };
 
-__device__ __forceinline__ RoiPixel roi_pixel(const RoiArgs &a, int inst, long long X0, long long Y0, double m00, double m10, int x) {
+// Where a detection's pixels and its draw come from: the addressing argument of roi_pixel and of roi_sample_body.
+struct RoiSrc {
+    const uint16_t *depth;  // the detection's depth image [H,W]
+    const uint8_t *mask;    // pixel 0 of the detection's channel = its mask block + the channel
+    int stride;             // channels of that block = bytes from a pixel's entry to the next pixel's
+    uint32_t run, slot;     // the draw's (run, slot) of philox.h (roi_sample_body alone)
+};
+
+__device__ __forceinline__ RoiPixel roi_pixel(const RoiArgs &a, const RoiSrc &src, long long X0, long long Y0, double m00, double m10, int x) {
     RoiPixel p{false, false, 0, 0, 0.f};
     if (x >= a.img) return p;
     // adelta[x] = cvRound(M00 * x * 1024), source = (X0 + adelta[x]) >> 10 (arithmetic shift), saturate_cast<short>
@@ -43,10 +51,10 @@ __device__ __forceinline__ RoiPixel roi_pixel(const RoiArgs &a, int inst, long l
     if (sxl >= 0 && sxl < a.W && syl >= 0 && syl < a.H) {
         p.sx = (int)sxl, p.sy = (int)syl;
         const size_t q = (size_t)p.sy * a.W + p.sx;
-        const uint16_t dv = a.depth[q];
+        const uint16_t dv = src.depth[q];
         p.has_depth = dv > 0;
         p.d = (float)dv;
-        p.valid = p.has_depth && a.masks[q * a.ninst + inst] != 0;
+        p.valid = p.has_depth && src.mask[q * src.stride] != 0;
     }
     return p;
 }
@@ -64,6 +72,7 @@ __global__ __launch_bounds__(64 * ROI_WAVES) void roi_cloud_kernel(RoiArgs a) {
     const double *M = a.minv + (size_t)inst * 6;
     const double m00 = M[0], m01 = M[1], m02 = M[2], m10 = M[3], m11 = M[4], m12 = M[5];
     float *out = a.pcl + (size_t)inst * a.img * a.img * 3;
+    const RoiSrc src{a.depth, a.masks + inst, a.ninst, 0, 0};
     const int rpw = (a.img + ROI_WAVES - 1) / ROI_WAVES;
     const int r0 = wave * rpw, r1 = (r0 + rpw < a.img) ? r0 + rpw : a.img;
     int cnt = 0, dep = 0;
@@ -79,7 +88,7 @@ __global__ __launch_bounds__(64 * ROI_WAVES) void roi_cloud_kernel(RoiArgs a) {
             const long long X0 = llrint((m01 * y + m02) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
             const long long Y0 = llrint((m11 * y + m12) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
             for (int x0 = 0; x0 < a.img; x0 += 64) {
-                const RoiPixel p = roi_pixel(a, inst, X0, Y0, m00, m10, x0 + lane);
+                const RoiPixel p = roi_pixel(a, src, X0, Y0, m00, m10, x0 + lane);
                 const unsigned long long bal = __ballot(p.valid);
                 if (pass == 0) {
                     cnt += __popcll(bal);
@@ -147,10 +156,13 @@ __device__ __forceinline__ uint32_t seeded_rank(const gp_philox::Seed &sd, uint3
     return x;
 }
 
-__global__ __launch_bounds__(64 * ROI_WAVES) void roi_sample_kernel(RoiArgs a, const uint32_t *__restrict__ seed, int npts, uint8_t *__restrict__ valid) {
+// Pass 1, the scan and pass 2 for detection `inst` of the launch (its minv row, its output rows), written once: roi_sample_kernel and
+// roi_sample_frames_kernel differ in `src` alone.  a.depth, a.masks and a.ninst are not read here.
+__device__ __forceinline__ void roi_sample_body(const RoiArgs &a, const RoiSrc &src, int inst, const uint32_t *__restrict__ seed, int npts,
+                                                uint8_t *__restrict__ valid) {
     extern __shared__ unsigned long long seg_bal[];  // [nseg] ballots, then [nseg] int base ranks
     __shared__ int wave_tot[ROI_WAVES], wave_dep[ROI_WAVES];
-    const int inst = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int segs = (a.img + 63) >> 6, nseg = a.img * segs;
     int *seg_base = reinterpret_cast<int *>(seg_bal + nseg);
     const double *M = a.minv + (size_t)inst * 6;
@@ -161,7 +173,7 @@ __global__ __launch_bounds__(64 * ROI_WAVES) void roi_sample_kernel(RoiArgs a, c
         const int y = s / segs, x0 = (s - y * segs) << 6;
         const long long X0 = llrint((m01 * y + m02) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
         const long long Y0 = llrint((m11 * y + m12) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
-        const RoiPixel p = roi_pixel(a, inst, X0, Y0, m00, m10, x0 + lane);
+        const RoiPixel p = roi_pixel(a, src, X0, Y0, m00, m10, x0 + lane);
         const unsigned long long bal = __ballot(p.valid);
         dep += __popcll(__ballot(p.has_depth));
         if (lane == 0) seg_bal[s] = bal;
@@ -195,8 +207,9 @@ __global__ __launch_bounds__(64 * ROI_WAVES) void roi_sample_kernel(RoiArgs a, c
     if (tid == 0) a.count[inst] = c, a.depth_count[inst] = d, valid[inst] = ok;
     // ---- pass 2
     float *out = a.pcl + (size_t)inst * npts * 3;
-    const gp_philox::Seed sd = gp_philox::load_seed(seed);
-    const uint32_t slot = (uint32_t)sd.row_base + (uint32_t)inst;
+    gp_philox::Seed sd = gp_philox::load_seed(seed);  // (the key; run and slot are the source's)
+    sd.run = src.run;
+    const uint32_t slot = src.slot;
     for (int k = tid; k < npts; k += 64 * ROI_WAVES) {
         float *o = out + (size_t)k * 3;
         if (!ok) {
@@ -219,8 +232,46 @@ __global__ __launch_bounds__(64 * ROI_WAVES) void roi_sample_kernel(RoiArgs a, c
         const int y = lo / segs, x = ((lo - y * segs) << 6) + pos;
         const long long X0 = llrint((m01 * y + m02) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
         const long long Y0 = llrint((m11 * y + m12) * (double)(1 << AB_BITS)) + (1 << (AB_BITS - 1));
-        roi_point(a, roi_pixel(a, inst, X0, Y0, m00, m10, x), o);
+        roi_point(a, roi_pixel(a, src, X0, Y0, m00, m10, x), o);
     }
+}
+
+// One frame: the launch's detections are the channels of its one mask block; run and the slot of detection 0 from the seed state.
+__global__ __launch_bounds__(64 * ROI_WAVES) void roi_sample_kernel(RoiArgs a, const uint32_t *__restrict__ seed, int npts, uint8_t *__restrict__ valid) {
+    const int inst = blockIdx.x;
+    const RoiSrc src{a.depth, a.masks + inst, a.ninst, seed[2], seed[4] + (uint32_t)inst};
+    roi_sample_body(a, src, inst, seed, npts, valid);
+}
+
+// Many frames of one size: detection i's frame, channel, block and (run, slot) from the tables (genpose_hip.h, gp_roi_sample_frames).  An
+// entry that does not name a channel of a block inside `masks` is a detection without a cloud - zero rows, zero counts, valid = 0 - decided
+// by the whole workgroup before anything is read through it.
+struct FrameTables {
+    int nframes;
+    long long mask_bytes;
+    const long long *mask_off;  // [nframes]
+    const int32_t *det;         // [ndet][3] frame, channel, channels of the frame's block
+    const uint32_t *draw;       // [ndet][2] run, slot
+};
+
+__global__ __launch_bounds__(64 * ROI_WAVES) void roi_sample_frames_kernel(RoiArgs a, FrameTables t, const uint32_t *__restrict__ seed, int npts,
+                                                                           uint8_t *__restrict__ valid) {
+    const int inst = blockIdx.x;
+    const int f = t.det[3 * inst], ch = t.det[3 * inst + 1], nf = t.det[3 * inst + 2];
+    bool ok = f >= 0 && f < t.nframes && nf > 0 && ch >= 0 && ch < nf;
+    long long off = 0;
+    if (ok) {  // (H, W <= 32767 and nf < 2^31: the block's size stays below 2^61)
+        off = t.mask_off[f];
+        ok = off >= 0 && off <= t.mask_bytes && (long long)a.H * a.W * nf <= t.mask_bytes - off;
+    }
+    if (!ok) {
+        float *out = a.pcl + (size_t)inst * npts * 3;
+        for (int k = threadIdx.x; k < npts; k += 64 * ROI_WAVES) out[(size_t)k * 3] = out[(size_t)k * 3 + 1] = out[(size_t)k * 3 + 2] = 0.f;
+        if (threadIdx.x == 0) a.count[inst] = 0, a.depth_count[inst] = 0, valid[inst] = 0;
+        return;
+    }
+    const RoiSrc src{a.depth + (size_t)f * a.H * a.W, a.masks + off + ch, nf, t.draw[2 * inst], t.draw[2 * inst + 1]};
+    roi_sample_body(a, src, inst, seed, npts, valid);
 }
 
 }  // namespace
@@ -254,6 +305,22 @@ int gp_roi_sample_seeded(int h, int w, int ninst, int img, int npts, const uint1
     RoiArgs a{h, w, ninst, img, depth, masks, minv, fx, fy, cx, cy, out, count, depth_count};
     const size_t lds = (size_t)img * ((img + 63) / 64) * (sizeof(unsigned long long) + sizeof(int));
     hipLaunchKernelGGL(roi_sample_kernel, dim3(ninst), dim3(64 * ROI_WAVES), lds, (hipStream_t)s, a, seed_state, npts, valid);
+    return gp_launch_status();
+}
+
+int gp_roi_sample_frames(int h, int w, int nframes, int ndet, int img, int npts, const uint16_t *depth, const uint8_t *masks, int64_t mask_bytes,
+                         const int64_t *mask_off, const int32_t *det, const uint32_t *draw, const double *minv, float fx, float fy, float cx, float cy,
+                         const uint32_t *seed_state, float *out, int32_t *count, int32_t *depth_count, uint8_t *valid, gp_stream_t s) {
+    if (h <= 0 || w <= 0 || ndet < 0 || img <= 0 || npts <= 0 || mask_bytes < 0 || !depth || !masks || !mask_off || !det || !draw || !minv || !seed_state ||
+        !out || !count || !depth_count || !valid)
+        return GP_EINVAL;
+    if (h > 32767 || w > 32767 || img > SAMPLE_MAX_IMG) return GP_EINVAL;
+    if (ndet == 0) return GP_OK;
+    if (nframes <= 0) return GP_EINVAL;
+    RoiArgs a{h, w, ndet, img, depth, masks, minv, fx, fy, cx, cy, out, count, depth_count};
+    FrameTables t{nframes, (long long)mask_bytes, (const long long *)mask_off, det, draw};
+    const size_t lds = (size_t)img * ((img + 63) / 64) * (sizeof(unsigned long long) + sizeof(int));
+    hipLaunchKernelGGL(roi_sample_frames_kernel, dim3(ndet), dim3(64 * ROI_WAVES), lds, (hipStream_t)s, a, t, seed_state, npts, valid);
     return gp_launch_status();
 }
 

@@ -126,14 +126,16 @@ class PinnedBlock:
         self.host = torch.zeros(shape, dtype=dtype).pin_memory()
         self._ev = torch.cuda.Event()  # (never recorded so far: the first synchronize() returns at once)
 
-    def send(self, dst, fill):
+    def send(self, dst, fill, rows=None):
         """fill(block) writes the host block.  dst: the device tensor to overwrite, or a device - then a fresh tensor there.  The copy
-        is in stream order on the current stream of dst's device; returns the device tensor."""
+        is in stream order on the current stream of dst's device; returns the device tensor.  rows: only the block's first `rows`
+        entries along dim 0 travel (a block sized by capacity, a dst at least as long: its rest keeps what it held)."""
         self._ev.synchronize()  # the previous copy out of the pinned block has completed
         fill(self.host)
+        src = self.host if rows is None else self.host[:rows]
         if torch.is_tensor(dst):
-            dst.copy_(self.host, non_blocking=True)
+            (dst if rows is None else dst[:rows]).copy_(src, non_blocking=True)
         else:
-            dst = self.host.to(dst, non_blocking=True)
+            dst = src.to(dst, non_blocking=True)
         self._ev.record(torch.cuda.current_stream(dst.device))
         return dst

@@ -112,8 +112,166 @@ def seeded_ranks(count, n_pts, seed, run, slot):
     return x[0] if scalar else x
 
 
+# ------------------------------------------------------------------ many frames in one launch (gp_roi_sample_frames): the host tables
+def _depth_hw(depth, f):
+    """(H, W) of a depth image - a host array or a tensor on any device - after device_clouds' dtype check; nothing is copied."""
+    if isinstance(depth, torch.Tensor):
+        ok = depth.dtype in (torch.uint16, torch.int16)
+    else:
+        depth = np.asarray(depth)
+        ok = depth.dtype.kind in "ui" and depth.dtype.itemsize == 2
+    if not ok:
+        raise RuntimeError(f"frame {f}: depth must be uint16 millimetres")
+    shape = tuple(depth.shape)
+    if len(shape) != 2:
+        raise ValueError(f"frame {f}: depth must be [H, W], got {shape}")
+    return int(shape[0]), int(shape[1])
+
+
+def inverse_crop_maps(rois, img_size, im_h, im_w):
+    """inverse_crop_map(get_bbox(roi, im_h, im_w), img_size, im_h, im_w).reshape(6) for every row of rois [n,4] at once -> [n,6] float64,
+    the same integer and float64 operations in the same order (equal bit for bit; tests/test_depth_frames_host.py): a batch of 258
+    detections costs 1.5 ms through the per-detection functions."""
+    if len(rois) < 16:  # (a frame or two: the per-detection functions are quicker than some forty array operations)
+        return np.array([inverse_crop_map(get_bbox(b, im_h, im_w), img_size, im_h, im_w) for b in rois], dtype=np.float64).reshape(len(rois), 6)
+    r = np.trunc(np.asarray(rois, dtype=np.float64)).astype(np.int64).reshape(-1, 4)  # (int(v): towards zero)
+    y1, x1, y2, x2 = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+    half = np.minimum((np.maximum(y2 - y1, x2 - x1) // 40 + 1) * 40, 440) // 2  # (a multiple of 40 halved: exact)
+    cy, cx = (y1 + y2) // 2, (x1 + x2) // 2
+    rmin, rmax, cmin, cmax = cy - half, cy + half, cx - half, cx + half
+    rmax, rmin = np.where(rmin < 0, rmax - rmin, rmax), np.maximum(rmin, 0)
+    cmax, cmin = np.where(cmin < 0, cmax - cmin, cmax), np.maximum(cmin, 0)
+    rmin, rmax = np.where(rmax > im_h, rmin - (rmax - im_h), rmin), np.minimum(rmax, im_h)
+    cmin, cmax = np.where(cmax > im_w, cmin - (cmax - im_w), cmin), np.minimum(cmax, im_w)
+    scale = np.minimum(np.maximum(rmax - rmin, cmax - cmin), max(im_h, im_w)).astype(np.float64)
+    out = np.zeros((len(r), 6), dtype=np.float64)
+    out[:, 0] = out[:, 4] = scale / float(img_size)
+    out[:, 2] = 0.5 * (cmin + cmax) - 0.5 * scale
+    out[:, 5] = 0.5 * (rmin + rmax) - 0.5 * scale
+    return out
+
+
+def frame_tables(frames, img_size, first_run=0, slot_base=0, runs=None, slots=None):
+    """The tables of gp_roi_sample_frames (include/genpose_hip.h) for a list of frames (depth [H,W] uint16, masks [H,W,n_f], rois [n_f,4],
+    ...) of ONE image size; device-free: host arrays out, the images are only asked for their shapes and dtypes.  The n = sum n_f detections
+    are in frame order, instance order inside a frame.  -> dict
+        H, W, nframes, ndet, mask_bytes (= sum H * W * n_f: the packed mask buffer)
+        mask_off [F] int64      byte offset of each frame's [H,W,n_f] uint8 block in that buffer (the running sum of H * W * n_f)
+        det      [n,3] int32    frame index, mask channel inside the frame's block, n_f
+        draw     [n,2] uint32   (run, slot) of the detection's draw: run = first_run + frame index, slot = slot_base + instance, so that
+                                frame f's block of the launch equals device_clouds(*frame, seed, run=first_run + f, slot_base=slot_base);
+                                runs [F] (one per FRAME) / slots [n] (one per DETECTION, in frame order) replace them
+        minv     [n,6] float64  inverse_crop_map(get_bbox(roi)) per detection
+        frame, inst [n] int64   which frame, which instance of it
+    ValueError: frames of different H x W, a mask block that is not [H,W,len(rois)], img_size > MAX_IMG_SEEDED, runs / slots of the wrong
+    length; RuntimeError: depth that is not uint16 (as device_clouds)."""
+    if img_size > MAX_IMG_SEEDED:
+        raise ValueError(f"frame_tables: img_size {img_size} > {MAX_IMG_SEEDED} (the kernel keeps the crop's ballots in LDS); use __call__")
+    F = len(frames)
+    H = W = total = 0
+    # (plain lists, converted once at the end: array calls per frame were most of a 43-frame table's cost)
+    mask_off, frame, inst, chans, rois = [], [], [], [], []
+    for f, fr in enumerate(frames):
+        h, w = _depth_hw(fr[0], f)
+        if f == 0:
+            H, W = h, w
+        elif (h, w) != (H, W):
+            raise ValueError(f"frame {f} is {h} x {w}, frame 0 is {H} x {W}: one launch serves one image size (group the frames by size)")
+        mshape = tuple(fr[1].shape) if hasattr(fr[1], "shape") else np.shape(fr[1])
+        nf = int(mshape[2]) if len(mshape) == 3 else 0
+        if nf != len(fr[2]):
+            raise ValueError(f"frame {f}: {nf} masks for {len(fr[2])} rois")
+        if nf and tuple(mshape[:2]) != (H, W):
+            raise ValueError(f"frame {f}: masks {mshape} for a {H} x {W} depth image")
+        mask_off.append(total)
+        total += H * W * nf
+        if nf:
+            frame += [f] * nf
+            inst += range(nf)
+            chans += [nf] * nf
+            rois.append(np.asarray(fr[2]).reshape(nf, 4))
+    n = len(frame)
+    if runs is None:
+        runs = [int(first_run) + f for f in range(F)]
+    elif np.shape(runs) != (F,):
+        raise ValueError(f"runs: one per frame ([{F}]), got {np.shape(runs)}")
+    if slots is None:
+        slots = [int(slot_base) + i for i in inst]
+    elif np.shape(slots) != (n,):
+        raise ValueError(f"slots: one per detection ([{n}]), got {np.shape(slots)}")
+    draw = np.array([(int(runs[f]) & 0xFFFFFFFF, int(s) & 0xFFFFFFFF) for f, s in zip(frame, slots)], dtype=np.uint32).reshape(n, 2)
+    return {"H": H, "W": W, "nframes": F, "ndet": n, "mask_bytes": total, "mask_off": np.array(mask_off, dtype=np.int64).reshape(F),
+            "det": np.array([frame, inst, chans], dtype=np.int32).reshape(3, n).T.copy(), "draw": draw,
+            "minv": inverse_crop_maps(np.concatenate(rois) if rois else np.zeros((0, 4)), img_size, H, W), "frame": np.array(frame, dtype=np.int64).reshape(n),
+            "inst": np.array(inst, dtype=np.int64).reshape(n)}
+
+
+def check_frame_tables(t):
+    """Refuses, before any launch, tables whose entries the kernel would have to guard against (there such a detection silently gets no
+    cloud): a frame outside [0, nframes), n_f <= 0, a channel outside [0, n_f), a block outside the packed mask buffer.  ValueError."""
+    F, n, H, W = t["nframes"], t["ndet"], t["H"], t["W"]
+    det, off = np.asarray(t["det"]).reshape(-1, 3), np.asarray(t["mask_off"]).reshape(-1)
+    if len(det) != n or len(off) != F or np.asarray(t["draw"]).shape != (n, 2) or np.asarray(t["minv"]).shape != (n, 6):
+        raise ValueError(f"frame tables: {n} detections of {F} frames, got det {det.shape}, mask_off {off.shape}")
+    if n == 0:
+        return t
+    if F <= 0 or not (1 <= H <= 32767 and 1 <= W <= 32767):
+        raise ValueError(f"frame tables: {n} detections of {F} frames of {H} x {W}")
+    f, ch, nf = det[:, 0].astype(np.int64), det[:, 1].astype(np.int64), det[:, 2].astype(np.int64)
+    bad = (f < 0) | (f >= F) | (nf <= 0) | (ch < 0) | (ch >= nf)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"frame tables: detection {i} names frame {f[i]} of {F}, channel {ch[i]} of {nf[i]}")
+    o = off[f]
+    bad = (o < 0) | (o + H * W * nf > int(t["mask_bytes"]))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"frame tables: detection {i}'s mask block [{o[i]}, {o[i] + H * W * nf[i]}) leaves the {t['mask_bytes']} packed bytes")
+    return t
+
+
+def assemble_detect_result(keys, results, class_ids, frame, inst, valid, points):
+    """Host arrays of a batched front end -> the reference's `detect_result` dict (evaluation_single.py:241-253):
+    keys[f] -> {'result': results[f], 'valid_pts': [n_pts,3] float32 per kept instance, 'cat_id': class_id - 1 per kept instance,
+    'valid_inst': the kept instance indices}, kept = valid != 0, in instance order.  frame / inst / valid [n], points [n,n_pts,3]: the
+    detections in frame order; class_ids[f]: frame f's [n_f].  A frame with nothing kept has its key with empty lists.  results[f] gets the
+    reference's placeholders pred_RTs (identities) and pred_scales (ones) where it has none (:162-163, :238-239)."""
+    if not (len(keys) == len(results) == len(class_ids)):
+        raise ValueError(f"{len(keys)} keys, {len(results)} results, {len(class_ids)} class_ids: one of each per frame")
+    frame, inst, valid = np.asarray(frame).reshape(-1), np.asarray(inst).reshape(-1), np.asarray(valid).reshape(-1)
+    points = np.asarray(points, dtype=np.float32)
+    if not (len(frame) == len(inst) == len(valid) == len(points)):
+        raise ValueError(f"frame {frame.shape}, inst {inst.shape}, valid {valid.shape}, points {points.shape}: one row per detection")
+    out = {}
+    for f, key in enumerate(keys):
+        n_f = len(class_ids[f])
+        res = results[f]
+        res.setdefault("pred_RTs", np.tile(np.identity(4, dtype=float), (n_f, 1, 1)))
+        res.setdefault("pred_scales", np.ones((n_f, 3), dtype=float))
+        out[key] = {"result": res, "valid_pts": [], "cat_id": [], "valid_inst": []}
+    for i in np.flatnonzero(valid != 0):
+        f, k = int(frame[i]), int(inst[i])
+        e = out[keys[f]]
+        e["valid_pts"].append(points[i])
+        e["cat_id"].append(int(class_ids[f][k]) - 1)
+        e["valid_inst"].append(k)
+    return out
+
+
+def _as_one_block(ts, H, W):
+    """Device images [H,W] that already are the consecutive slices of one contiguous tensor -> that [F,H,W] tensor, no copy; else None."""
+    t0 = ts[0]
+    step = H * W * t0.element_size()
+    for f, t in enumerate(ts):
+        if not (t.is_contiguous() and t.dtype == t0.dtype and t.device == t0.device and t.data_ptr() == t0.data_ptr() + f * step
+                and t.untyped_storage().data_ptr() == t0.untyped_storage().data_ptr()):
+            return None
+    return t0.as_strided((len(ts), H, W), (H * W, W, 1))
+
+
 class DepthToClouds:
     RING = 4  # pinned blocks in rotation (device_clouds): the host rewrites one only after the copy issued four calls earlier has completed
+    FRAMES_RING = 2  # device_clouds_frames' blocks hold many frames each: two in rotation (a third call waits for the first one's copy)
 
     def __init__(self, intrinsics=REAL_INTRINSICS, n_pts=1024, img_size=256, device="cuda"):
         _lib.check_device()
@@ -121,6 +279,7 @@ class DepthToClouds:
         self.fx, self.fy, self.cx, self.cy = float(K[0]), float(K[4]), float(K[2]), float(K[5])
         self.n_pts, self.img, self.dev = n_pts, img_size, torch.device(device)
         self._staging = {}  # device_clouds: (H, W, n) -> static device inputs and their pinned blocks
+        self._staging_frames = {}  # device_clouds_frames: (H, W) -> device buffers sized by capacity and their pinned blocks
 
     def full_clouds(self, depth, masks, rois):
         """All valid points of every detection, raster order of the crop: (pcl [n,img*img,3] f32, count [n], depth_count [n])."""
@@ -244,3 +403,179 @@ class DepthToClouds:
         st["pin_minv"][slot].send(st["minv"], lambda h: h.copy_(torch.from_numpy(minv_h)))
         st["pin_seed"][slot].send(st["seed"], lambda h: h.copy_(torch.from_numpy(words.view(np.int32))))
         return self.launch_seeded(depth.contiguous(), masks.contiguous(), st["minv"], st["seed"], out)
+
+    # ------------------------------------------------------------------ many frames in one launch
+    def empty_outputs_frames(self, n):
+        """The output dict of device_clouds_frames for n detections: empty_outputs(n) plus frame and inst [n] int64."""
+        out = self.empty_outputs(n)
+        out["frame"], out["inst"] = torch.zeros(2, n, dtype=torch.int64, device=self.dev)  # (one block: one copy fills both)
+        return out
+
+    def launch_frames(self, depth, masks, mask_off, det, draw, minv, seed_state, out):
+        """gp_roi_sample_frames on device tensors alone: depth [F,H,W] uint16 / int16, masks [bytes] uint8 (the frames' [H,W,n_f] blocks one
+        after the other), mask_off [F] int64, det [n,3] int32, draw [n,2] int32 (the uint32 words), minv [n,6] float64 - frame_tables' arrays -
+        seed_state [8] int32 (words 0, 1 alone are read), out as empty_outputs(n) (frame / inst, if present, are not touched).  One launch,
+        nothing else: capturable.  The table ENTRIES are not looked at here (that would be a read-back; check_frame_tables does it on the
+        host): the kernel gives an out-of-range entry no cloud."""
+        if depth.dim() != 3 or det.dim() != 2:
+            raise ValueError("launch_frames: depth [F,H,W], det [n,3]")
+        F, H, W = depth.shape
+        n = det.shape[0]
+        for name, shape, dtype in (("points", (n, self.n_pts, 3), torch.float32), ("count", (n,), torch.int32),
+                                   ("depth_count", (n,), torch.int32), ("valid", (n,), torch.uint8)):
+            if tuple(out[name].shape) != shape or out[name].dtype != dtype or out[name].device.type != "cuda":
+                raise ValueError(f"out[{name!r}]: a device tensor {shape} {dtype}, got {tuple(out[name].shape)} {out[name].dtype} on {out[name].device}")
+        if depth.dtype not in (torch.uint16, torch.int16) or masks.dtype != torch.uint8 or masks.dim() != 1 or mask_off.dtype != torch.int64 \
+                or tuple(mask_off.shape) != (F,) or det.dtype != torch.int32 or tuple(det.shape) != (n, 3) or draw.dtype != torch.int32 \
+                or tuple(draw.shape) != (n, 2) or minv.dtype != torch.float64 or tuple(minv.shape) != (n, 6) or seed_state.dtype != torch.int32 \
+                or seed_state.numel() != 8:
+            raise ValueError("launch_frames: depth uint16 [F,H,W], masks uint8 [bytes], mask_off int64 [F], det int32 [n,3], draw int32 [n,2], "
+                             "minv float64 [n,6], seed_state int32 [8]")
+        if any(t.device.type != "cuda" for t in (depth, masks, mask_off, det, draw, minv, seed_state)):
+            raise ValueError("launch_frames: device tensors only")
+        if n == 0:
+            return out
+        _lib.call("gp_roi_sample_frames", H, W, F, n, self.img, self.n_pts, ptr(depth), ptr(masks), masks.numel(), ptr(mask_off), ptr(det), ptr(draw),
+                  ptr(minv), self.fx, self.fy, self.cx, self.cy, ptr(seed_state), ptr(out["points"]), ptr(out["count"]), ptr(out["depth_count"]),
+                  ptr(out["valid"]), stream_ptr())
+        return out
+
+    def _reserve(self, st, name, need, tail, dtype):
+        """st[name]: a device buffer [capacity, *tail] with capacity >= need - sized by capacity, it only grows (by half at least), so a
+        ragged sequence of batches does not reallocate on every call; its pinned blocks are rebuilt with it."""
+        cap = st["cap"].get(name, 0)
+        if cap < need:
+            cap = max(need, cap + cap // 2)
+            st[name] = torch.empty((cap,) + tail, dtype=dtype, device=self.dev)
+            for blk in st["pin"].pop(name, ()):
+                blk._ev.synchronize()  # (the last copy out of a block that goes away has completed)
+            st["cap"][name] = cap
+        return st[name]
+
+    def _pinned(self, st, name, slot):
+        from .graphs import PinnedBlock
+        ring = st["pin"].get(name)
+        if ring is None:
+            ring = st["pin"][name] = [PinnedBlock(tuple(st[name].shape), st[name].dtype) for _ in range(self.FRAMES_RING)]
+        return ring[slot]
+
+    def _clouds_frames(self, frames, seed, first_run, slot_base, runs, slots, out):
+        """device_clouds_frames -> (its dict, the host tables)."""
+        frames = [tuple(fr[:3]) for fr in frames]
+        t = check_frame_tables(frame_tables(frames, self.img, first_run, slot_base, runs, slots))
+        F, n, H, W = t["nframes"], t["ndet"], t["H"], t["W"]
+        if out is None:
+            out = self.empty_outputs_frames(n)
+        if n == 0:
+            return out, t
+        st = self._staging_frames.get((H, W))
+        if st is None:
+            if len(self._staging_frames) >= 4:
+                self._staging_frames.pop(next(iter(self._staging_frames)))
+            st = self._staging_frames[(H, W)] = {"cap": {}, "pin": {}, "ring": 0}
+        slot = st["ring"] = (st["ring"] + 1) % self.FRAMES_RING
+        # ---- depth: device images that are one block already are used as they are; others are gathered by device copies; host images go up
+        # through one pinned block, the frames side by side
+        depths = [torch.as_tensor(np.ascontiguousarray(fr[0])) if not torch.is_tensor(fr[0]) else fr[0] for fr in frames]
+        on_dev = [d.device.type == "cuda" for d in depths]
+        depth = _as_one_block(depths, H, W) if all(on_dev) else None
+        if depth is None:
+            buf = self._reserve(st, "depth", F, (H, W), torch.int16)
+            i16 = [d.view(torch.int16) if d.dtype == torch.uint16 else d for d in depths]
+            if all(on_dev):
+                for f in range(F):
+                    buf[f].copy_(i16[f])
+            elif not any(on_dev):
+                def fill_depth(h):
+                    for f in range(F):
+                        h[f].copy_(i16[f])
+                self._pinned(st, "depth", slot).send(buf, fill_depth, rows=F)
+            else:
+                raise ValueError("device_clouds_frames: the frames' depth images are all host arrays or all device tensors")
+            depth = buf[:F]
+        # ---- masks: packed at mask_off - on the host into one pinned block (bool -> 0 / 1 there), from the device by one copy per frame
+        blocks = [(f, int(t["mask_off"][f]), torch.as_tensor(np.ascontiguousarray(fr[1])) if not torch.is_tensor(fr[1]) else fr[1])
+                  for f, fr in enumerate(frames) if len(fr[2])]
+        on_dev = [m.device.type == "cuda" for _, _, m in blocks]
+        nbytes = t["mask_bytes"]
+        if len(blocks) == 1 and on_dev[0] and blocks[0][2].dtype == torch.uint8 and blocks[0][2].is_contiguous():
+            masks = blocks[0][2].view(-1)  # (one frame's uint8 block on the device: as it is)
+        else:
+            buf = self._reserve(st, "masks", nbytes, (), torch.uint8)
+            if all(on_dev):
+                for f, off, m in blocks:
+                    buf[off:off + m.numel()].view(m.shape).copy_(m)
+            elif not any(on_dev):
+                def fill_masks(h):
+                    for f, off, m in blocks:
+                        h[off:off + m.numel()].view(m.shape).copy_(m)
+                self._pinned(st, "masks", slot).send(buf, fill_masks, rows=nbytes)
+            else:
+                raise ValueError("device_clouds_frames: the frames' masks are all host arrays or all device tensors")
+            masks = buf[:nbytes]
+        # ---- the tables and the seed: ONE pinned block, one copy - int64 mask_off [F] | float64 minv [n,6] | int64 frame, inst [2,n] |
+        # int32 det [n,3] | uint32 draw [n,2] | the 8 seed words (run and slot words unused: they come from draw)
+        seed = int(seed) % (1 << 64)
+        words = np.array([seed & 0xFFFFFFFF, seed >> 32, 0, 0, 0, 0, 0, 0], dtype=np.uint32)
+        parts = [("mask_off", t["mask_off"]), ("minv", t["minv"]), ("fi", np.stack([t["frame"], t["inst"]])), ("det", t["det"]),
+                 ("draw", t["draw"]), ("seed", words)]
+        total = sum(a.nbytes for _, a in parts)
+        buf = self._reserve(st, "tables", total, (), torch.uint8)
+
+        def fill_tables(h):
+            hn, o = h.numpy(), 0
+            for _, a in parts:
+                hn[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+                o += a.nbytes
+        self._pinned(st, "tables", slot).send(buf, fill_tables, rows=total)
+        as_torch = {"int64": torch.int64, "float64": torch.float64, "int32": torch.int32, "uint32": torch.int32}
+        dev, o = {}, 0
+        for name, a in parts:  # (8-byte entries first: every view starts at a multiple of its item size)
+            dev[name] = buf[o:o + a.nbytes].view(as_torch[a.dtype.name]).view(a.shape)
+            o += a.nbytes
+        self.launch_frames(depth, masks, dev["mask_off"], dev["det"], dev["draw"], dev["minv"], dev["seed"], out)
+        # (the staging is the next call's: the indices leave it - in one copy where the two tensors are empty_outputs_frames' one block)
+        fr_o, in_o = out.get("frame"), out.get("inst")
+        if fr_o is None or in_o is None:
+            out["frame"], out["inst"] = dev["fi"].clone()
+        elif fr_o.is_contiguous() and in_o.is_contiguous() and in_o.data_ptr() == fr_o.data_ptr() + 8 * n \
+                and in_o.untyped_storage().data_ptr() == fr_o.untyped_storage().data_ptr():
+            fr_o.as_strided((2, n), (n, 1)).copy_(dev["fi"])
+        else:
+            fr_o.copy_(dev["fi"][0])
+            in_o.copy_(dev["fi"][1])
+        return out, t
+
+    def device_clouds_frames(self, frames, seed, first_run=0, slot_base=0, runs=None, slots=None, out=None):
+        """device_clouds over MANY frames in ONE launch (gp_roi_sample_frames).  frames: a sequence of (depth [H,W] uint16, masks [H,W,n_f],
+        rois [n_f,4]) of one image size (this object's intrinsics and crop size serve them all; n_f may be 0).  -> device_clouds' dict over
+        all n = sum n_f detections in frame order - points [n,n_pts,3], count, depth_count, valid [n] - plus frame and inst [n] int64 (which
+        frame, which instance of it), all on the device, nothing read back.  Detection (f, i) draws as (seed, run = first_run + f,
+        slot = slot_base + i): frame f's block equals device_clouds(*frames[f], seed, run=first_run + f, slot_base=slot_base) bit for bit,
+        whatever shares the launch and in whatever order; runs [F] / slots [n] replace the defaults (frame_tables).
+        Host depth, masks and the tables go up through pinned blocks in stream order (three copies for the whole batch); device depth images
+        that are consecutive slices of one [F,H,W] tensor are used as they are, others and per-frame device masks are gathered by device
+        copies.  The staging is sized by capacity and only grows.  out: empty_outputs_frames(n) of an earlier call - then nothing is
+        allocated for the outputs.  No detection at all: the empty dict, no launch."""
+        return self._clouds_frames(frames, seed, first_run, slot_base, runs, slots, out)[0]
+
+    def detect(self, frames, keys, results, class_ids, seed=0, first_run=0, chunk=64):
+        """The reference's `detect_result` dict (what detect_mrcnn_genpose pickles, evaluation_single.py:241-253: key -> {'result',
+        'valid_pts', 'cat_id', 'valid_inst'}) for a list of frames (depth, masks, rois), built from batched launches of at most `chunk`
+        frames with ONE read-back per chunk (the clouds and their valid flags in one copy).  keys[f], results[f] (the per-image record
+        carried along as 'result'), class_ids[f] [n_f] belong to frames[f]; frame f draws as run first_run + f.  The kept instances are
+        exactly those __call__ keeps; SingleFrameRunner.evaluate and evaluation.DetectionResults take the dict as it is."""
+        if not (len(frames) == len(keys) == len(results) == len(class_ids)):
+            raise ValueError(f"{len(frames)} frames, {len(keys)} keys, {len(results)} results, {len(class_ids)} class_ids: one of each per frame")
+        if chunk < 1:
+            raise ValueError(f"detect(chunk={chunk}): at least one frame per launch")
+        out = {}
+        for c0 in range(0, len(frames), chunk):
+            sl = slice(c0, c0 + chunk)
+            fe, t = self._clouds_frames(frames[sl], seed, first_run + c0, 0, None, None, None)
+            n = t["ndet"]
+            # (valid travels as one more column of the float rows: one device -> host copy, one synchronisation per chunk)
+            both = torch.cat([fe["points"].reshape(n, -1), fe["valid"].float().unsqueeze(1)], dim=1).cpu().numpy() if n else np.zeros((0, 3 * self.n_pts + 1), np.float32)
+            out.update(assemble_detect_result(keys[sl], results[sl], class_ids[sl], t["frame"], t["inst"], both[:, -1],
+                                              both[:, :-1].reshape(n, self.n_pts, 3)))
+        return out

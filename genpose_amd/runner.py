@@ -130,6 +130,29 @@ class SingleFrameRunner:
         out["cat_id"] = torch.as_tensor(np.asarray(class_ids), dtype=torch.int64).to(fe["valid"].device) - 1
         return out
 
+    def infer_depth_frames(self, frames, seed=0, first_frame=0):
+        """infer_depth over MANY frames: frames, a sequence of (depth, masks, rois, class_ids) of one image size -> infer_depth's dict over
+        all n = sum n_f detections in frame order, plus `frame` and `inst` [n] int64 (which frame, which instance of it).  ONE front-end
+        launch (DepthToClouds.device_clouds_frames; frame f draws as (seed, first_frame + f, instance), so its rows are what
+        infer_depth(*frames[f], seed, frame=first_frame + f) feeds the networks), then infer_tensors on all n clouds - sliced by batch_size,
+        so the networks see full batches instead of one frame's five clouds - and the identity for the detections without a cloud."""
+        from .preprocess import DepthToClouds
+        if self.depth_front_end is None:
+            self.depth_front_end = DepthToClouds()
+        frames = list(frames)
+        fe = self.depth_front_end.device_clouds_frames([fr[:3] for fr in frames], seed, first_run=first_frame)
+        out = self.infer_tensors(fe["points"])
+        if "average_sRT" in out:
+            avg = out["average_sRT"]
+            out["average_sRT"] = torch.where(fe["valid"].bool().view(-1, 1, 1), avg, torch.eye(4, dtype=avg.dtype, device=avg.device))
+        for k in ("valid", "count", "depth_count", "frame", "inst"):
+            out[k] = fe[k]
+        cls = np.concatenate([np.asarray(fr[3], dtype=np.int64).reshape(-1) for fr in frames]) if frames else np.zeros(0, dtype=np.int64)
+        if len(cls) != fe["valid"].shape[0]:
+            raise ValueError(f"{len(cls)} class_ids for {fe['valid'].shape[0]} detections")
+        out["cat_id"] = torch.from_numpy(cls).to(fe["valid"].device) - 1
+        return out
+
     def evaluate(self, detect_result, out_dir=None, degree_thresholds=tuple(range(0, 46)), shift_thresholds=tuple(i / 2 for i in range(21)),
                  iou_thresholds=tuple(i / 100 for i in range(101)), pooling_mode="average", ranker="energy_ranker"):
         """inference_pose -> inference_energy -> evaluate (evaluation_single.py:356-544) on the reference's `detect_result` dict

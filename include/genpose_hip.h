@@ -82,6 +82,24 @@ int gp_cloud_sample(int ninst, int cap, int npts, const float *pcl, const int32_
 int gp_roi_sample_seeded(int h, int w, int ninst, int img, int npts, const uint16_t *depth, const uint8_t *masks, const double *minv, float fx,
                          float fy, float cx, float cy, const uint32_t *seed_state, float *out, int32_t *count, int32_t *depth_count, uint8_t *valid,
                          gp_stream_t s);
+/* gp_roi_sample_frames (ours): gp_roi_sample_seeded over the detections of MANY depth images in ONE launch - ndet detections that belong
+ *   to nframes images of one size h x w and one set of intrinsics; one 16-wave workgroup per detection, the same device code (the body of
+ *   pass 1, the scan and pass 2 exists once; the two kernels differ in the addressing they hand it).
+ *   depth [nframes][h][w] uint16 mm; masks: the frames' [h][w][n_f] uint8 blocks one after the other (n_f differs from frame to frame
+ *   and may be 0), mask_bytes the size of the whole packed buffer; mask_off [nframes] int64 = the byte offset of each frame's block;
+ *   det [ndet][3] int32 = {frame index, mask channel inside that frame's block, n_f = the block's channel count};
+ *   draw [ndet][2] uint32 = {run, slot} of the detection's draw; minv [ndet][6] as above (row i = detection i);
+ *   seed_state: the 8 words as above, of which ONLY [0], [1] (the seed) are read - run and slot come from `draw`.
+ *   out [ndet][npts][3], count, depth_count, valid [ndet] as gp_roi_sample_seeded.  Detection i's four outputs are, bit for bit, what
+ *   gp_roi_sample_seeded writes for it given depth + det[i][0] * h * w, masks + mask_off[det[i][0]] with ninst = det[i][2], instance
+ *   det[i][1], seed_state[2] = draw[i][0] and seed_state[4] + instance = draw[i][1] - whatever shares its launch, in any order.
+ *   A table entry that is out of range - frame outside [0, nframes), n_f <= 0, channel outside [0, n_f), or a block that does not lie
+ *   inside [0, mask_bytes) - is a detection without a cloud: zero rows, count = depth_count = 0, valid = 0; nothing is read through it.
+ *   NULL pointers, npts <= 0, img outside [1, 512], h or w outside [1, 32767], ndet < 0, mask_bytes < 0, nframes <= 0 with ndet > 0:
+ *   GP_EINVAL, nothing written; ndet == 0: GP_OK.  No allocation, no synchronisation, no host read: capturable. */
+int gp_roi_sample_frames(int h, int w, int nframes, int ndet, int img, int npts, const uint16_t *depth, const uint8_t *masks, int64_t mask_bytes,
+                         const int64_t *mask_off, const int32_t *det, const uint32_t *draw, const double *minv, float fx, float fy, float cx, float cy,
+                         const uint32_t *seed_state, float *out, int32_t *count, int32_t *depth_count, uint8_t *valid, gp_stream_t s);
 
 /* Library / device identification: returns ABI version; writes gcnArchName of the current device. */
 int gp_version(void);
