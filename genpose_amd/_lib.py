@@ -16,6 +16,7 @@ PLAN_SHARED = 0x200     # GP_PLAN_SHARED: the RK45 driver's shared-chunk plan (1
 PLAN_FLAGS = 0x300
 RK45_MODEL_LIKELIHOOD_EXACT = 4  # GP_RK45_MODEL_LIKELIHOOD_EXACT: the likelihood ODE with the exact divergence (3 stays an unknown model)
 CONSENSUS_MAX_K = 512   # GP_CONSENSUS_MAX_K: the largest candidate count the consensus ranker's LDS layout serves
+MODE_MAX_ITERS = 64     # GP_MODE_MAX_ITERS: the most mean-shift iterations gp_mode_aggregate runs
 PLAN_HEADSPLIT = 0x100  # GP_PLAN_HEADSPLIT (include/genpose_hip.h): OR-ed onto a 16-row tile plan = three workgroups per tile, one head each
 
 
@@ -137,6 +138,7 @@ SIGNATURES = {
     "gp_quat_trans_to_rt": [c_int, P, P, P],
     "gp_consensus_energy": [c_int, c_int, c_int, P, P, P, P],
     "gp_consensus_rank_aggregate_rt": [c_int, c_int, c_int, c_int] + [P] * 9 + [P],
+    "gp_mode_aggregate": [c_int, c_int, c_int, P, P, P, ctypes.c_double, ctypes.c_double, c_int] + [P] * 5 + [P],
 }
 OPTIONAL = set()
 

@@ -352,6 +352,251 @@ __global__ __launch_bounds__(64) void consensus_rank_aggregate_kernel(int k, int
     rank_aggregate_cloud<T>(b, k, sel, poses, e, ord, quat, sorted_poses, sorted_energy, order, avg_pose, sorted_rt, avg_rt);
 }
 
+// ---------------------------------------------------------------------------------------------- mode-seeking aggregation
+// Kernel density over a cloud's candidates and a mean shift from the densest one (ours; include/genpose_hip.h, section D), the rotation
+// (column 0) and the translation (column 1) independently.  LDS per candidate: consensus_stage's matrix, translation and flag, and its
+// two effective weights: 108 bytes, 55 296 at k = GP_CONSENSUS_MAX_K.  The quaternions are NOT staged (32 bytes more per candidate would
+// pass the 64 KB default at k = 512): every mean-shift iteration recomputes them from the matrices.
+constexpr size_t MODE_LDS_PER_K = CONS_LDS_PER_K + 2 * sizeof(float);
+
+// consensus_score's distances between two staged poses a and q (the same expressions in the same order: bitwise symmetric)
+template <bool SYM>
+__device__ __forceinline__ double mode_rot_dist(const double *a, const double *q) {
+    double x;
+    if (SYM) {
+        const double d0 = a[1] - q[1], d1 = a[4] - q[4], d2 = a[7] - q[7];
+        x = sqrt((d0 * d0 + d1 * d1) + d2 * d2) / 2.0;
+    } else {
+        double ss = 0.0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            const double d = a[c] - q[c];
+            ss += d * d;
+        }
+        x = sqrt(ss) / 2.8284271247461903;  // 2 sqrt 2
+    }
+    return 2.0 * asin(x < 1.0 ? x : 1.0);
+}
+
+__device__ __forceinline__ double mode_trans_dist(const double *a, const double *q) {
+    const double t0 = a[9] - q[9], t1 = a[10] - q[10], t2 = a[11] - q[11];
+    return sqrt((t0 * t0 + t1 * t1) + t2 * t2);
+}
+
+__device__ __forceinline__ double mode_kernel(double d, double h) { return exp(-(d * d) / (2.0 * h * h)); }
+
+// the sum over the wave, the same bits in every lane (a + b == b + a at every level of the butterfly)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// (w, x, y, z) -> row-major 3x3 in float64 (pytorch3d quaternion_to_matrix: two_s = 2 / |q|^2)
+__device__ __forceinline__ void quat_to_matrix(const double q[4], double *o) {
+    const double r = q[0], a = q[1], b = q[2], c = q[3];
+    const double two_s = 2.0 / (((r * r + a * a) + b * b) + c * c);
+    o[0] = 1.0 - two_s * (b * b + c * c), o[1] = two_s * (a * b - c * r), o[2] = two_s * (a * c + b * r);
+    o[3] = two_s * (a * b + c * r), o[4] = 1.0 - two_s * (a * a + c * c), o[5] = two_s * (b * c - a * r);
+    o[6] = two_s * (a * c - b * r), o[7] = two_s * (b * c + a * r), o[8] = 1.0 - two_s * (a * a + b * b);
+}
+
+// row-major 3x3 -> (w, x, y, z) with w >= 0
+__device__ __forceinline__ void matrix_to_quat_pos(const double *m9, double q[4]) {
+    double R[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r][c] = m9[3 * r + c];
+    matrix_to_quat(R, q);
+    const double sgn = q[0] < 0 ? -1.0 : 1.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i] *= sgn;
+}
+
+// One cloud by one wave.  Sums over j that decide a ranking (the density) run serially and ascending in the lane that owns i; sums that
+// feed the centre (mean shift, mass, W) are lane partials over j = lane, lane + 64, ... folded by wave_sum - every lane then holds the same
+// centre and carries it on redundantly, as rank_aggregate_cloud does with its Jacobi iteration.
+template <bool SYM>
+__device__ __forceinline__ void mode_cloud(int b, int k, const double *rt, const int *fin, const float *w, double hr, double ht,
+                                           int iters, float *__restrict__ density, float *__restrict__ mode_pose, float *__restrict__ mode_rt,
+                                           float *__restrict__ mass, int32_t *__restrict__ start) {
+    const int tid = threadIdx.x;
+    double Wr = 0.0, Wt = 0.0;
+    for (int j = tid; j < k; j += 64) Wr += (double)w[2 * j], Wt += (double)w[2 * j + 1];
+    Wr = wave_sum(Wr), Wt = wave_sum(Wt);
+    // density, and the lane's best candidate per column (strict >: the lowest index of a lane's ascending i wins its ties)
+    double best_r = -1.0, best_t = -1.0;
+    int ir = -1, it = -1;
+    for (int i = tid; i < k; i += 64) {
+        double d0 = -__builtin_inf(), d1 = -__builtin_inf();
+        if (fin[i]) {
+            double a[CONS_F64];
+#pragma unroll
+            for (int c = 0; c < CONS_F64; ++c) a[c] = rt[CONS_F64 * i + c];
+            double sr = 0.0, st = 0.0;
+            for (int j = 0; j < k; ++j) {
+                const double wr = (double)w[2 * j], wt = (double)w[2 * j + 1];
+                if (wr == 0.0 && wt == 0.0) continue;  // (every non-finite j is here)
+                const double *q = rt + CONS_F64 * j;
+                if (wr > 0.0) sr += wr * mode_kernel(mode_rot_dist<SYM>(a, q), hr);
+                if (wt > 0.0) st += wt * mode_kernel(mode_trans_dist(a, q), ht);
+            }
+            d0 = Wr > 0.0 ? sr / Wr : 0.0;
+            d1 = Wt > 0.0 ? st / Wt : 0.0;
+            if (w[2 * i] > 0.f && d0 > best_r) best_r = d0, ir = i;
+            if (w[2 * i + 1] > 0.f && d1 > best_t) best_t = d1, it = i;
+        }
+        if (density) density[((size_t)b * k + i) * 2 + 0] = (float)d0, density[((size_t)b * k + i) * 2 + 1] = (float)d1;
+    }
+    // start: the highest float64 density among the weighted candidates, the lowest index among equals
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double o_r = __shfl_xor(best_r, m, 64), o_t = __shfl_xor(best_t, m, 64);
+        const int j_r = __shfl_xor(ir, m, 64), j_t = __shfl_xor(it, m, 64);
+        if (j_r >= 0 && (ir < 0 || o_r > best_r || (o_r == best_r && j_r < ir))) best_r = o_r, ir = j_r;
+        if (j_t >= 0 && (it < 0 || o_t > best_t || (o_t == best_t && j_t < it))) best_t = o_t, it = j_t;
+    }
+    if (start && tid == 0) start[(size_t)b * 2 + 0] = ir, start[(size_t)b * 2 + 1] = it;
+    if (!mode_pose && !mode_rt && !mass) return;
+    // the centre in consensus_stage's layout: [0..8] the rotation (SYM: only the y axis, [1], [4], [7], is read), [9..11] the translation
+    double cen[CONS_F64] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}, qc[4] = {1, 0, 0, 0};
+    if (ir >= 0) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) cen[c] = rt[CONS_F64 * ir + c];
+        matrix_to_quat_pos(cen, qc);
+    }
+    if (it >= 0) {
+#pragma unroll
+        for (int c = 9; c < 12; ++c) cen[c] = rt[CONS_F64 * it + c];
+    }
+    double mr = 0.0, mt = 0.0;
+    for (int step = 0; step <= iters; ++step) {  // `iters` shifts, then one more pass for the mass at the final centre
+        double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ta[3] = {0, 0, 0}, sur = 0.0, sut = 0.0;
+        for (int j = tid; j < k; j += 64) {
+            const double wr = (double)w[2 * j], wt = (double)w[2 * j + 1];
+            if (wr == 0.0 && wt == 0.0) continue;
+            const double *q = rt + CONS_F64 * j;
+            if (wr > 0.0) {
+                const double u = wr * mode_kernel(mode_rot_dist<SYM>(cen, q), hr);
+                sur += u;
+                if (SYM) {
+                    acc[0] += u * q[1], acc[1] += u * q[4], acc[2] += u * q[7];
+                } else if (step < iters) {
+                    double qj[4];
+                    matrix_to_quat_pos(q, qj);
+                    acc[0] += u * (qj[0] * qj[0]), acc[1] += u * (qj[0] * qj[1]), acc[2] += u * (qj[0] * qj[2]), acc[3] += u * (qj[0] * qj[3]);
+                    acc[4] += u * (qj[1] * qj[1]), acc[5] += u * (qj[1] * qj[2]), acc[6] += u * (qj[1] * qj[3]);
+                    acc[7] += u * (qj[2] * qj[2]), acc[8] += u * (qj[2] * qj[3]), acc[9] += u * (qj[3] * qj[3]);
+                }
+            }
+            if (wt > 0.0) {
+                const double u = wt * mode_kernel(mode_trans_dist(cen, q), ht);
+                sut += u;
+                ta[0] += u * q[9], ta[1] += u * q[10], ta[2] += u * q[11];
+            }
+        }
+        sur = wave_sum(sur), sut = wave_sum(sut);
+        if (step == iters) {
+            mr = Wr > 0.0 ? sur / Wr : 0.0;
+            mt = Wt > 0.0 ? sut / Wt : 0.0;
+            break;
+        }
+#pragma unroll
+        for (int c = 0; c < (SYM ? 3 : 10); ++c) acc[c] = wave_sum(acc[c]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ta[c] = wave_sum(ta[c]);
+        if (sut > 0.0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cen[9 + c] = ta[c] / sut;
+        }
+        if (sur > 0.0) {
+            if (SYM) {
+                const double n = sqrt((acc[0] * acc[0] + acc[1] * acc[1]) + acc[2] * acc[2]);
+                if (n >= 1e-12) cen[1] = acc[0] / n, cen[4] = acc[1] / n, cen[7] = acc[2] / n;
+            } else {
+                double A[4][4] = {{acc[0] / sur, acc[1] / sur, acc[2] / sur, acc[3] / sur},
+                                  {acc[1] / sur, acc[4] / sur, acc[5] / sur, acc[6] / sur},
+                                  {acc[2] / sur, acc[5] / sur, acc[7] / sur, acc[8] / sur},
+                                  {acc[3] / sur, acc[6] / sur, acc[8] / sur, acc[9] / sur}};
+                double v[4];
+                top_eigvec4(A, v);
+                const double sgn = v[0] < 0 ? -1.0 : 1.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) qc[i] = sgn * v[i];
+                quat_to_matrix(qc, cen);
+            }
+        }
+    }
+    if (SYM && iters > 0 && ir >= 0) {
+        // the start candidate's R turned by the minimal rotation that takes its y axis ys onto the centre's y:
+        // M = I + [v]x + [v]x^2 / (1 + c), v = ys x y, c = ys . y; opposite axes (1 + c < 1e-12): the half turn about R's x axis
+        const double *Rs = rt + CONS_F64 * ir;
+        const double ys[3] = {Rs[1], Rs[4], Rs[7]}, y[3] = {cen[1], cen[4], cen[7]};
+        const double v[3] = {ys[1] * y[2] - ys[2] * y[1], ys[2] * y[0] - ys[0] * y[2], ys[0] * y[1] - ys[1] * y[0]};
+        const double c1 = 1.0 + ((ys[0] * y[0] + ys[1] * y[1]) + ys[2] * y[2]);
+        double M[9];
+        if (c1 < 1e-12) {
+            const double x[3] = {Rs[0], Rs[3], Rs[6]};
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) M[3 * r + c] = 2.0 * x[r] * x[c] - (r == c ? 1.0 : 0.0);
+        } else {
+            const double vv = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) M[3 * r + c] = (v[r] * v[c] - (r == c ? vv : 0.0)) / c1 + (r == c ? 1.0 : 0.0);  // I + [v]x^2 / (1 + c)
+            M[1] -= v[2], M[2] += v[1], M[3] += v[2], M[5] -= v[0], M[6] -= v[1], M[7] += v[0];                        // + [v]x
+        }
+        double R[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) R[3 * r + c] = (M[3 * r] * Rs[c] + M[3 * r + 1] * Rs[3 + c]) + M[3 * r + 2] * Rs[6 + c];
+        matrix_to_quat_pos(R, qc);
+    }
+    if (tid == 0) {
+        float qt[7];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) qt[i] = (float)qc[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) qt[4 + i] = (float)cen[9 + i];
+        if (mode_pose) {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) mode_pose[(size_t)b * 7 + i] = qt[i];
+        }
+        if (mode_rt) quat_trans_to_rt(qt, mode_rt + (size_t)b * 16);
+        if (mass) mass[(size_t)b * 2 + 0] = (float)mr, mass[(size_t)b * 2 + 1] = (float)mt;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void mode_aggregate_kernel(int k, const T *__restrict__ poses, const int8_t *__restrict__ sym,
+                                                            const float *__restrict__ weight, double hr, double ht, int iters,
+                                                            float *__restrict__ density, float *__restrict__ mode_pose,
+                                                            float *__restrict__ mode_rt, float *__restrict__ mass, int32_t *__restrict__ start) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *rt = reinterpret_cast<double *>(smem);          // [k][12]
+    float *w = reinterpret_cast<float *>(rt + CONS_F64 * k);  // [k][2] effective weights
+    int *fin = reinterpret_cast<int *>(w + 2 * k);          // [k]
+    const int b = blockIdx.x;
+    consensus_stage<T>(k, poses + (size_t)b * k * 9, rt, fin);
+    for (int i = threadIdx.x; i < k; i += 64) {  // (the lane that staged candidate i reads its own flag)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float wi = weight ? weight[((size_t)b * k + i) * 2 + c] : 1.f;
+            w[2 * i + c] = (fin[i] && wi > 0.f) ? wi : 0.f;
+        }
+    }
+    __syncthreads();
+    if (sym && sym[b])
+        mode_cloud<true>(b, k, rt, fin, w, hr, ht, iters, density, mode_pose, mode_rt, mass, start);
+    else
+        mode_cloud<false>(b, k, rt, fin, w, hr, ht, iters, density, mode_pose, mode_rt, mass, start);
+}
+
 }  // namespace
 
 // [n][9] poses (two rotation columns + translation) -> [n][4][4] f64 homogeneous matrices (evaluation_single.py:325-332: get_rot_matrix
@@ -446,6 +691,21 @@ int gp_consensus_rank_aggregate_rt(int b, int k, int sel, int is_f64, const void
     else
         hipLaunchKernelGGL(consensus_rank_aggregate_kernel<float>, dim3(b), dim3(64), lds, (hipStream_t)s, k, sel, (const float *)poses, sym,
                            energy_out, (float *)sorted_poses, sorted_energy, order, avg_pose, sorted_rt, avg_rt);
+    return gp_launch_status();
+}
+
+int gp_mode_aggregate(int b, int k, int is_f64, const void *poses, const int8_t *sym, const float *weight, double bw_rot, double bw_trans,
+                      int iters, float *density, float *mode_pose, float *mode_rt, float *mass, int32_t *start, gp_stream_t s) {
+    if (b < 0 || k <= 0 || k > GP_CONSENSUS_MAX_K || !poses || iters < 0 || iters > GP_MODE_MAX_ITERS) return GP_EINVAL;
+    if (!(bw_rot > 0.0 && bw_rot < __builtin_huge_val()) || !(bw_trans > 0.0 && bw_trans < __builtin_huge_val())) return GP_EINVAL;  // (NaN fails both)
+    if (b == 0) return GP_OK;
+    const size_t lds = (size_t)k * MODE_LDS_PER_K;  // at most 108 * GP_CONSENSUS_MAX_K = 55 296 bytes: below the 64 KB default
+    if (is_f64)
+        hipLaunchKernelGGL(mode_aggregate_kernel<double>, dim3(b), dim3(64), lds, (hipStream_t)s, k, (const double *)poses, sym, weight, bw_rot,
+                           bw_trans, iters, density, mode_pose, mode_rt, mass, start);
+    else
+        hipLaunchKernelGGL(mode_aggregate_kernel<float>, dim3(b), dim3(64), lds, (hipStream_t)s, k, (const float *)poses, sym, weight, bw_rot,
+                           bw_trans, iters, density, mode_pose, mode_rt, mass, start);
     return gp_launch_status();
 }
 

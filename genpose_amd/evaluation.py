@@ -12,6 +12,7 @@ Same inputs, same outputs and the same matching / AP rules as the reference:
   sort_sRT, sort_sRT_by_energy utils/sgpa_utils.py:24-51, 897-954  (energy ranker; rotation and translation ranked independently)
   compute_mAP                  utils/sgpa_utils.py:957-1183  (use_matches_for_pose=True, 2-D IoU matching as evaluate() calls it)
   consensus_energy             ours: ranker 'consensus_ranker', the host statement of gp_consensus_energy (include/genpose_hip.h, section D)
+  mode_sRT                     ours: pooling_mode / error_mode 'mode', the host statement of gp_mode_aggregate (include/genpose_hip.h, section D)
 
 Pinned by tests/golden/g10_map.npz, produced by the imported reference (oracle/gen_golden.py).
 """
@@ -26,6 +27,9 @@ from . import rotation
 SYNSET_NAMES = ["BG", "bottle", "bowl", "camera", "can", "laptop", "mug"]
 _Y_SYMMETRIC = ("bottle", "can", "bowl")
 _CONSENSUS_PAIRS = 1 << 22  # candidate pairs consensus_energy holds at once (it works through larger inputs in slices of instances)
+# mode_sRT's defaults (= reward.MODE_*): the bandwidths and iteration count of the synthetic prototype (70 % / 50 % inlier and 30 + 20
+# bimodal clouds of 50 candidates); NOT tuned on the accuracy proxy or on REAL275
+MODE_BW_ROT_DEG, MODE_BW_TRANS, MODE_ITERS = 10.0, 0.02, 8
 
 
 # ---------------------------------------------------------------------------------------------- containers
@@ -132,8 +136,84 @@ def consensus_energy(sRT, sym=None):
     return score
 
 
+def _pose_distances(Rc, tc, R, t, sym):
+    """centre (Rc [3,3], tc [3]) against hypotheses (R [m,3,3], t [m,3]) -> (dR [m] radians, dT [m]), consensus_energy's distances"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = np.sqrt(np.sum((R[:, :, 1] - Rc[:, 1]) ** 2, axis=-1)) / 2.0 if sym else np.sqrt(np.sum((R - Rc) ** 2, axis=(-2, -1))) / (2.0 * np.sqrt(2.0))
+        return 2.0 * np.arcsin(np.minimum(1.0, x)), np.sqrt(np.sum((t - tc) ** 2, axis=-1))
+
+
+def _minimal_turn(R, y):
+    """R [3,3] turned by the minimal rotation that takes its y axis onto the unit vector y (opposite axes: the half turn about R's x axis)"""
+    ys = R[:, 1]
+    v, c1 = np.cross(ys, y), 1.0 + float(ys @ y)
+    if c1 < 1e-12:
+        return (2.0 * np.outer(R[:, 0], R[:, 0]) - np.eye(3)) @ R
+    vx = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return (np.eye(3) + vx + (vx @ vx) / c1) @ R
+
+
+def mode_sRT(selected, sym=None, bw_rot_deg=MODE_BW_ROT_DEG, bw_trans=MODE_BW_TRANS, iters=MODE_ITERS, weight=None):
+    """selected [n,m,4,4] -> (mode [n,4,4], mass [n,2], start [n,2]), float64: the host statement of gp_mode_aggregate (include/genpose_hip.h,
+    section D).  Per instance, rotation (column 0) and translation (column 1) independently: a Gaussian kernel density over the hypotheses
+    in consensus_energy's distances (bandwidths bw_rot_deg degrees and bw_trans metres), `iters` mean-shift steps from the densest weighted
+    hypothesis (the lowest index among equals) - the translation to the kernel-weighted mean, the rotation to the top eigenvector of the
+    kernel-weighted sum of q q^T, for sym[n] != 0 the y axis to the normalised kernel-weighted mean axis, the rotation then being the start
+    hypothesis turned by the minimal rotation onto that axis - and `mass`, the weighted share of the hypotheses under the kernel at the
+    final centre (a confidence in [0, 1]).  weight [n,m,2] (optional; default all ones): a hypothesis counts with its weight where that is
+    > 0 and the hypothesis is finite.  No weight left: the identity / zero translation, mass 0, start -1.  The 3x3 blocks are taken as
+    rotations as they stand; the mode is NOT rounded through float32 (average_sRT's quaternion is)."""
+    selected = np.asarray(selected, dtype=np.float64)
+    n, m = selected.shape[:2]
+    if not (np.isfinite(bw_rot_deg) and bw_rot_deg > 0 and np.isfinite(bw_trans) and bw_trans > 0):
+        raise ValueError(f"mode_sRT: the bandwidths must be finite and > 0, got {bw_rot_deg} deg, {bw_trans} m")
+    if int(iters) != iters or iters < 0:
+        raise ValueError(f"mode_sRT: iters must be an integer >= 0, got {iters}")
+    if weight is not None and np.shape(weight) != (n, m, 2):
+        raise ValueError(f"mode_sRT: weight must be [{n},{m},2], got {np.shape(weight)}")
+    symv = np.zeros(n, dtype=bool) if sym is None else np.broadcast_to(np.asarray(sym).astype(bool), (n,))
+    h = (np.deg2rad(bw_rot_deg), float(bw_trans))
+    kap = lambda d, c: np.exp(-(d * d) / (2.0 * h[c] * h[c]))
+    out, mass, start = np.tile(np.identity(4), (n, 1, 1)), np.zeros((n, 2)), -np.ones((n, 2), dtype=np.int64)
+    for a in range(n):
+        fin = np.isfinite(selected[a, :, :3, :]).all(axis=(1, 2))
+        w = np.ones((m, 2)) if weight is None else np.asarray(weight[a], dtype=np.float64)
+        w = np.where(fin[:, None] & (w > 0), w, 0.0)
+        for c in range(2):
+            on = np.nonzero(w[:, c] > 0)[0]  # everything below runs on the weighted hypotheses alone
+            if len(on) == 0:
+                continue
+            R, t, wc, s = selected[a, on, :3, :3], selected[a, on, :3, 3], w[on, c], bool(symv[a])
+            dist = lambda Rc, tc: _pose_distances(Rc, tc, R, t, s)[c]
+            dens = np.array([np.sum(wc * kap(dist(R[i], t[i]), c)) for i in range(len(on))]) / wc.sum()
+            i0 = int(np.argmax(dens))
+            start[a, c] = on[i0]
+            Rc, tc = R[i0].copy(), t[i0].copy()
+            q = rotation.matrix_to_quaternion(torch.from_numpy(np.ascontiguousarray(R))).numpy() if c == 0 and not s else None
+            for _ in range(int(iters)):
+                u = wc * kap(dist(Rc, tc), c)
+                if not u.sum() > 0:
+                    continue
+                if c == 1:
+                    tc = (u[:, None] * t).sum(axis=0) / u.sum()
+                elif s:
+                    y = (u[:, None] * R[:, :, 1]).sum(axis=0)
+                    if np.sqrt(y @ y) >= 1e-12:
+                        Rc[:, 1] = y / np.sqrt(y @ y)
+                else:
+                    v = np.linalg.eigh(np.einsum("j,ja,jb->ab", u, q, q) / u.sum())[1][:, -1]
+                    Rc = rotation.quaternion_to_matrix(torch.from_numpy(-v if v[0] < 0 else v)).numpy()
+            mass[a, c] = np.sum(wc * kap(dist(Rc, tc), c)) / wc.sum()
+            if c == 1:
+                out[a, :3, 3] = tc
+            else:
+                out[a, :3, :3] = _minimal_turn(R[i0], Rc[:, 1]) if s and iters > 0 else Rc
+    return out, mass, start
+
+
 def sort_sRT_by_energy(sRT, energy=None, RT_overlaps=None, ranker="energy_ranker", ratio=1.0, error_mode="average", sym=None):
-    """sym (ranker 'consensus_ranker' only): per-instance flags, symmetric about the y axis."""
+    """sym: per-instance flags, symmetric about the y axis - read by ranker 'consensus_ranker' and by error_mode 'mode' (ours: the second
+    output is mode_sRT of the selected hypotheses, at its default bandwidths, instead of their average)."""
     n, K = sRT.shape[:2]
     m = max(1, int(K * ratio))
     if n == 0:
@@ -154,6 +234,8 @@ def sort_sRT_by_energy(sRT, energy=None, RT_overlaps=None, ranker="energy_ranker
         return s, average_sRT(s), se
     if error_mode == "nearest":
         return s, None, se
+    if error_mode == "mode":
+        return s, mode_sRT(s, sym)[0], se
     raise NotImplementedError(error_mode)
 
 
@@ -363,7 +445,7 @@ def compute_mAP(pred_results, out_dir=None, degree_thresholds=(180,), shift_thre
                 c_gt_hv = c_gt_hv[keep_g] if len(keep_g) else np.zeros(0)
 
             hyp_overlaps = None
-            c_sym = np.full(len(c_hyp), synset_names[c] in _Y_SYMMETRIC) if ranker == "consensus_ranker" else None
+            c_sym = np.full(len(c_hyp), synset_names[c] in _Y_SYMMETRIC) if ranker == "consensus_ranker" or pooling_mode == "mode" else None
             if ranker == "gt_ranker":
                 per_h = [compute_RT_overlaps(c_gt_ids, c_gt_sRT, c_gt_hv, c_pred_ids, c_hyp[:, i], synset_names) for i in range(c_hyp.shape[1])]
                 hyp_overlaps = np.array(per_h).transpose(1, 2, 0, 3)
@@ -374,6 +456,9 @@ def compute_mAP(pred_results, out_dir=None, degree_thresholds=(180,), shift_thre
             elif pooling_mode == "average":
                 _, avg, _ = sort_sRT_by_energy(c_hyp, c_energy, hyp_overlaps, ranker, ratio, "average", sym=c_sym)
                 RT_overlaps = compute_RT_overlaps(c_gt_ids, c_gt_sRT, c_gt_hv, c_pred_ids, avg, synset_names)
+            elif pooling_mode == "mode":  # (ours) the mode of the selected hypotheses; the symmetry flag is the class's, under every ranker
+                _, mode, _ = sort_sRT_by_energy(c_hyp, c_energy, hyp_overlaps, ranker, ratio, "mode", sym=c_sym)
+                RT_overlaps = compute_RT_overlaps(c_gt_ids, c_gt_sRT, c_gt_hv, c_pred_ids, mode, synset_names)
             else:
                 raise NotImplementedError(pooling_mode)
             pgm, ppm = compute_RT_matches(RT_overlaps, c_pred_ids, c_gt_ids, deg_list, sh_list)

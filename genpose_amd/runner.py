@@ -48,14 +48,24 @@ class SingleFrameRunner:
     sample_from: 'score' (default) or 'energy' (ours; opt-in) - the ENERGY agent (energy_agent; score_agent may be None) draws the
     candidates itself with its pred_func (a posenet_mode='energy' agent: 'ode' / 'pc', or 'heun' / 'dpm2m' under cfg.fixed_step_energy) and
     then ranks them with get_energy(extract_pts_feature=False) on the cloud features pred_func left in the dict: ONE encoder pass per batch,
-    one checkpoint.  ranker 'energy' or 'consensus'; 'likelihood' is refused - likelihoods come from the score model."""
+    one checkpoint.  ranker 'energy' or 'consensus'; 'likelihood' is refused - likelihoods come from the score model.
+
+    aggregate: 'mean' (default: average_sRT is the quaternion mean and mean translation of the ranker's top max(1, int(K ratio)) candidates,
+    as the reference) or 'mode' (ours; opt-in) - the ranking is the same, then reward.mode_aggregate runs on those top candidates per
+    column (reward.selection_weight of the ranking's order, made on the device): average_sRT is the mode's 4x4 (mode_RT as float64) and the
+    dict gains mode_mass [n,2], the share of the selected candidates the mode explains (rotation, translation).  sym then also tells the
+    mode which clouds to compare by their y axis, under every ranker."""
 
     RANKERS = ("energy", "likelihood", "consensus")
     SAMPLE_FROM = ("score", "energy")
+    AGGREGATES = ("mean", "mode")
 
-    def __init__(self, score_agent, energy_agent=None, repeat_num=50, T0=0.55, batch_size=256, ratio=0.6, ranker="energy", sample_from="score"):
+    def __init__(self, score_agent, energy_agent=None, repeat_num=50, T0=0.55, batch_size=256, ratio=0.6, ranker="energy", sample_from="score",
+                 aggregate="mean"):
         if ranker not in self.RANKERS:
             raise NotImplementedError(f"ranker {ranker!r}: one of {self.RANKERS}")
+        if aggregate not in self.AGGREGATES:
+            raise ValueError(f"SingleFrameRunner(aggregate={aggregate!r}): one of {self.AGGREGATES}")
         if sample_from not in self.SAMPLE_FROM:
             raise ValueError(f"SingleFrameRunner(sample_from={sample_from!r}): one of {self.SAMPLE_FROM}")
         if sample_from == "energy":
@@ -66,26 +76,27 @@ class SingleFrameRunner:
                 raise ValueError("SingleFrameRunner(sample_from='energy') needs energy_agent with posenet_mode='energy'"
                                  + ("" if energy_agent is None else f", got {energy_agent.cfg.posenet_mode!r}"))
         self.score_agent, self.energy_agent, self.ranker, self.sample_from = score_agent, energy_agent, ranker, sample_from
-        self.repeat_num, self.T0, self.batch_size, self.ratio = repeat_num, T0, batch_size, ratio
+        self.repeat_num, self.T0, self.batch_size, self.ratio, self.aggregate = repeat_num, T0, batch_size, ratio, aggregate
         self.depth_front_end = None  # infer_depth's preprocess.DepthToClouds (assign one for other intrinsics / crop size / cloud size)
 
     def infer_tensors(self, clouds, sym=None):
         """clouds: device tensor [n,1024,3] -> dict of device tensors with leading dim n (usable under ShardedInference).
-        sym [n] (ranker 'consensus' only): clouds of objects symmetric about their y axis, compared by that axis alone."""
+        sym [n] (ranker 'consensus' or aggregate 'mode' only): clouds of objects symmetric about their y axis, compared by that axis alone."""
         n = clouds.shape[0]
         if sym is not None:
-            if self.ranker != "consensus":
+            if self.ranker != "consensus" and self.aggregate != "mode":
                 raise ValueError(f"sym is the consensus ranker's argument (ranker={self.ranker!r})")
             sym = torch.as_tensor(sym)
             if sym.shape != (n,):
                 raise ValueError(f"sym must hold one flag per cloud ([{n}]), got {tuple(sym.shape)}")
-        out = {"pred_pose": [], "multi_hypothesis_pred_RTs": [], "energy": [], "sorted_RTs": [], "average_sRT": []}
+        out = {"pred_pose": [], "multi_hypothesis_pred_RTs": [], "energy": [], "sorted_RTs": [], "average_sRT": [], "mode_mass": []}
         for s in range(0, n, self.batch_size):  # evaluation_single.py:380-382 batch slicing
             sample = make_batch_sample(clouds[s:s + self.batch_size])
             sampling_agent = self.energy_agent if self.sample_from == "energy" else self.score_agent
             pred = sampling_agent.pred_func(data=sample, repeat_num=self.repeat_num, save_path=None, T0=self.T0)
             out["pred_pose"].append(pred)
             out["multi_hypothesis_pred_RTs"].append(rotation.pose9_to_RT(pred))
+            r = None
             if self.ranker == "consensus":
                 r = reward.consensus_rank_aggregate(pred, None if sym is None else sym[s:s + self.batch_size], ratio=self.ratio)
                 out["energy"].append(r["energy"])
@@ -105,6 +116,11 @@ class SingleFrameRunner:
                 out["energy"].append(energy)
                 out["sorted_RTs"].append(rotation.pose9_to_RT(r["sorted_poses"]))
                 out["average_sRT"].append(rotation.quat_trans_to_RT(r["avg_pose"].double()))
+            if self.aggregate == "mode" and r is not None:  # the same ranking; the mode of its top candidates replaces their mean
+                w = reward.selection_weight(r["order"], max(1, int(pred.shape[1] * self.ratio)))
+                m = reward.mode_aggregate(pred, None if sym is None else sym[s:s + self.batch_size], w, with_rt=True)
+                out["average_sRT"][-1] = m["mode_RT"].double()
+                out["mode_mass"].append(m["mass"])
         return {k: torch.cat(v, dim=0) for k, v in out.items() if v}
 
     def infer(self, clouds, device="cuda", sym=None):

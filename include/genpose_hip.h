@@ -834,6 +834,40 @@ int gp_consensus_energy(int b, int k, int is_f64, const void *poses, const int8_
 int gp_consensus_rank_aggregate_rt(int b, int k, int sel, int is_f64, const void *poses, const int8_t *sym, float *energy_out, void *sorted_poses,
                                    float *sorted_energy, int32_t *order, float *avg_pose, double *sorted_rt, float *avg_rt, gp_stream_t s);
 
+/* Mode-seeking aggregation (ours): a kernel density over a cloud's candidates and a mean shift from the densest one, in place of the mean
+ * over the selected candidates - a mean over two modes is a pose of neither.  Rotation (c = 0) and translation (c = 1) independently, as
+ * the ranking treats them; float64 throughout.  For cloud b:
+ *   R_i, t_i, "finite", dR_ij, dT_ij   exactly gp_consensus_energy's (sym[b] != 0: dR is the angle between the y axes);
+ *   w_j[c] = weight[b][j][c] if it is > 0 and candidate j is finite, else 0 (weight == NULL: 1 for every finite j); W[c] = sum_j w_j[c];
+ *   kappa_c(d) = exp(-d^2 / (2 h_c^2)), h_0 = bw_rot (radians), h_1 = bw_trans (metres);
+ *   density[b][i][c] = (sum over j, ascending, i included, of w_j kappa_c(d_ij)) / W, stored as float32; -inf for a non-finite i.  Every i
+ *                      sums in the same order, so duplicates tie exactly; the array ranks through gp_rank_aggregate like any energy;
+ *   start[b][c]      = the lowest index with w_i > 0 that maximises the float64 density;
+ *   mean shift, `iters` times from the start candidate, u_j = w_j kappa_c(d(centre, x_j)):
+ *     translation     centre <- sum u_j t_j / sum u_j;
+ *     rotation        A = sum u_j q_j q_j^T / sum u_j, q_j = pytorch3d matrix_to_quaternion(R_j); centre <- the eigenvector of A's largest
+ *                     eigenvalue (float64 Jacobi), w >= 0, as a matrix (quaternion_to_matrix);
+ *     symmetric cloud y <- normalize(sum u_j y_j); when iters > 0 the rotation written is the start candidate's R turned by the minimal
+ *                     rotation that takes its y axis onto y (opposite axes, 1 + y_s . y < 1e-12: the half turn about R's x axis);
+ *     sum u_j == 0, or a new axis of norm < 1e-12: the centre stays where it is;
+ *   mass[b][c]       = sum_j w_j kappa_c(d(final centre, x_j)) / W in [0, 1]: the weighted share of the candidates the mode explains.
+ * mode_pose [b,7] f32 = (w, x, y, z, t) with w >= 0, avg_pose's layout; mode_rt [b,4,4] f32 = gp_quat_trans_to_rt(mode_pose) bit for bit;
+ * mass [b,2] f32; start [b,2] i32; density [b,k,2] f32.  W[c] == 0: the identity quaternion (c = 0) / the zero translation (c = 1),
+ * mass 0, start -1, density 0 for the finite candidates.  The weights have to be finite.  Every output is optional (NULL).
+ * Limits: 1 <= k <= GP_CONSENSUS_MAX_K; bw_rot, bw_trans finite and > 0; 0 <= iters <= GP_MODE_MAX_ITERS; b >= 0, b == 0 launches
+ * nothing; poses != NULL.  Anything else returns GP_EINVAL before a launch.  No allocation, no synchronisation: capture-safe; a cloud's
+ * outputs do not depend on the rest of the batch.
+ * One wave per cloud.  LDS: R, t and the flag as gp_consensus_energy stages them and the two effective weights, 108 bytes a candidate,
+ * 55 296 at the cap - within the default 64 KB.  The quaternions are not staged beside the matrices (that passes 64 KB at k = 512): each
+ * iteration recomputes them from the matrices.
+ * Cost per cloud on ONE wave: 2 k^2 float64 distances and exp for the density (lanes over i, serial over j), then (iters + 1) passes of
+ * 2 k distances and exp (lanes over j, a wave reduction) with one 4x4 Jacobi each - measured (profiles/mode_aggregate.txt) 144 - 160 us at
+ * k = 50 with 8 iterations (the density 26 - 29 us, an iteration ~14 us, 12 of them the Jacobi) and 2.0 ms at the cap, whatever b up to the
+ * device's wave slots; gp_rank_aggregate_rt took 23 - 25 us and 0.38 ms in the same session.  Meant for tens of candidates. */
+#define GP_MODE_MAX_ITERS 64
+int gp_mode_aggregate(int b, int k, int is_f64, const void *poses, const int8_t *sym, const float *weight, double bw_rot, double bw_trans,
+                      int iters, float *density, float *mode_pose, float *mode_rt, float *mass, int32_t *start, gp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
