@@ -10,7 +10,8 @@ Bound: rtol = atol = 1e-3 on finished states, the project's own for its fixed-st
 not derived from what these kernels give.  tests/test_fixed_step_energy_host.py shows that fp32 rounding of the network alone takes less
 than a quarter of it on every input used here.  The worst ratio per plan is printed (pytest -s).  Measured on MI355X, max |device - fp64| /
 (1e-3 + 1e-3 |fp64|) (profiles/fixed_step_energy.txt): 5.2e-4 - 7.1e-3 on the 16-row tiles, 4.0e-3 - 4.8e-2 on the chain form (a margin of 20 x or
-more); the bound stays as stated, it is not derived from these figures.
+more); the bound stays as stated, it is not derived from these figures.  It remains as a COARSE check; the accuracy claim of these solves is
+carried by tests/test_gpu_solver_f64.py (float64 at 3x the fp32 restatement's own error, admission by the 2x condition on the reference).
 
 Everything else is exact: row locality, the one-launch solve against its chain, replays, the agent and both runners against their pieces -
 bit for bit."""

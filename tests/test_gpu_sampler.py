@@ -126,6 +126,8 @@ def test_ode_golden(golden, case):
 
 
 def test_pc_agent_golden(golden):
+    """The agent's PC-20 run against the fp32 golden at rtol = atol = 1e-3: a COARSE check (0.48005 for 0.48 in the corrector passes it).
+    The PC step's accuracy claim is carried by tests/test_gpu_solver_f64.py: float64 solves at 3x the fp32 restatement's own error."""
     g = golden("g7_pc.npz")
     agent = make_agent("score", "pc", 20)
     pts = torch.from_numpy(g["pts"]).cuda()
