@@ -28,6 +28,10 @@ class GpScoreNet(ctypes.Structure):
 
 NETP = ctypes.POINTER(GpScoreNet)
 
+# what every gp_rk45_phase* entry point takes behind its geometry: net, cvec, tvec, centre, state, y, ynew, K, partials, traj, traj_cap,
+# t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, x_out
+RK45_SOLVE = [NETP] + [P] * 9 + [c_int] + [ctypes.c_double] * 5 + [c_int, c_int, P]
+
 # name -> argtypes ; every function returns int (0 ok / negative GP_E*), except gp_pack_weight_size (int64)
 SIGNATURES = {
     "gp_version": [],
@@ -118,19 +122,16 @@ SIGNATURES = {
     "gp_rk45_state_bytes": [],
     "gp_rk45_state_layout": [ctypes.POINTER(c_int64), c_int],
     "gp_rk45_set_dense": [P, P, c_int, P, P],
-    "gp_rk45_phase": [c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5 + [c_int, c_int, P, P],
-    "gp_rk45_phase_grouped": [c_int, c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5 + [c_int, c_int, P, P],
+    "gp_rk45_phase": [c_int] * 3 + RK45_SOLVE + [P],
+    "gp_rk45_phase_grouped": [c_int] * 4 + RK45_SOLVE + [P],
     "gp_rk45_plan_rows": [c_int, c_int, c_int, c_int],
     "gp_plan_headsplit_pays": [c_int],
     "gp_rk45_plan_rows_unshared": [c_int, c_int, c_int, c_int],
     "gp_rk45_partials_count": [c_int, c_int, c_int, c_int, c_int],
-    "gp_rk45_phase_model": [c_int, c_int, P, c_int, c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5
-                           + [c_int, c_int, P, P, c_int, P],
-    "gp_rk45_phase_bf16x9": [c_int, c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5
-                            + [c_int, c_int, P, P, c_int] + [P] * 3 + [P],
+    "gp_rk45_phase_model": [c_int, c_int, P] + [c_int] * 4 + RK45_SOLVE + [P, c_int, P],
+    "gp_rk45_phase_bf16x9": [c_int] * 4 + RK45_SOLVE + [P, c_int] + [P] * 3 + [P],
     "gp_rk45_set_dense_grouped": [c_int, P, P, c_int, P, P],
-    "gp_rk45_phase_ragged": [c_int, c_int, P, c_int, P, c_int, c_int, c_int, NETP, P, P, P, P, P, P, P, P, P, c_int] + [ctypes.c_double] * 5
-                            + [c_int, c_int, P, P],
+    "gp_rk45_phase_ragged": [c_int, c_int, P, c_int, P, c_int, c_int, c_int] + RK45_SOLVE + [P],
     "gp_time_embed_strided": [c_int, c_int, c_int64, NETP, P, P, P],
     "gp_rank_aggregate": [c_int, c_int, c_int, c_int, P, P, P, P, P, P, P],
     "gp_rank_aggregate_rt": [c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P],

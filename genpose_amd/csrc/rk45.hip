@@ -4,9 +4,17 @@
 //
 // The reference keeps the f64 state on the HOST and crosses PCIe twice per function evaluation
 // (samplers.py:187,191).  Here state, stage derivatives, t, h and the accept/reject decision all live in HBM:
-//   rk45_init_a / _b / _c : f0, Hairer initial step (two evaluations), first stage times
-//   per attempt           : time_embed(6 stage times) -> 6 fused stage kernels (stage update + score) -> rk45_decide
-//   rk45_finish           : denoise step (samplers.py:209-218), normalize_rotation, + centre
+//   rk45_reset_kernel      : the solver state of every group (phase 0)
+//   stage kernels          : stage update + right-hand side + partial sums of the controller's norms, one stage per launch
+//                            (rk45_stage_kernel on 16 / 32 / 64-row tiles, rk45_stage_chain_kernel[_bf16x9] on 128 rows) or the six
+//                            stages of an attempt in one (rk45_attempt_kernel; rk45_attempt_shared_kernel: the shared-chunk plan).
+//                            Stages 0 and 7 are the two evaluations of Hairer's initial step (phases 1 and 2).
+//   rk45_decide_kernel     : the step controller, one workgroup per group: initial step, accept / reject, next stage times
+//   rk45_embed_kernel      : time embeddings of the stage times the controller just set, for the next stage kernels
+//   rk45_group_sums_kernel : a sharded batch's per-group sums, all-reduced by the caller before the controller
+//   rk45_record_kernel     : accepted (or dense-output) states into the trajectory; rk45_traj_post_kernel finishes them
+//   rk45_finish_kernel     : denoise step (samplers.py:209-218), normalize_rotation, + centre; rk45_copy_final_kernel for the
+//                            likelihood ODE's ten-component state
 // The error norm is the reference's batch-global RMS over all R*9 components: per-tile partial sums, reduced in
 // a fixed order by the single-workgroup decide kernel (deterministic).
 #include "trunk_bf16x9.h"
@@ -935,16 +943,25 @@ struct Rk45Stages {
 
 }  // namespace
 
+// What a phase call carries besides OdeArgs (gp_rk45_phase_model's arguments of the same names; x9: gp_rk45_phase_bf16x9's packs)
+struct Rk45Call {
+    int phase, traj_cap;
+    double t0, t_bound, rtol, atol, denoise_scale;
+    int do_denoise, nstates;
+    double *x_out;
+    hipStream_t stream;
+    const gp_split::SplitNet *x9 = nullptr;
+};
+
 // CHAIN: the stage kernels run in the chain form (a.bpg / a.nblocks count 128-row workgroups); the denoising evaluation of phase 5
 // stays on P-row tiles with its own workgroup count
 // SPLIT: the head-split plan (three workgroups per 16-row tile, one head each; OdeArgs::hsplit == 3): every stage is a launch of its own
 template <int P, int MODEL, bool CHAIN = false, bool SPLIT = false>
-static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double *traj, int traj_cap, double t0, double t_bound, double rtol,
-                           double atol, double denoise_scale, int do_denoise, int nstates, const float *centre, double *x_out, hipStream_t st,
-                           const gp_split::SplitNet *x9 = nullptr) {
+static int rk45_phase_impl(OdeArgs &a, const gp_scorenet *net, const Rk45Call &c) {
     const size_t chain_lds = MODEL == 0 ? gp_chain::Cfg<2>::LDS_BYTES : gp_chain::CfgV<2>::LDS_BYTES;
-    const double *y = a.y;
     const size_t lds = MODEL == 0 ? trunk_lds_bytes<P>() : (MODEL == MODEL_EXACT ? gp_bwd::LDS_BYTES_EXACT : gp_bwd::LDS_BYTES);
+    const hipStream_t st = c.stream;
+    const gp_split::SplitNet *x9 = c.x9;
     // every phase's first call prepares all the kernels any phase of this plan launches
     using Stages = Rk45Stages<0, 1, 2, 3, 4, 5, 6, 7>;
     if constexpr (CHAIN) {
@@ -984,39 +1001,32 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
         else
             hipLaunchKernelGGL((rk45_stage_kernel<P, S, MODEL, SPLIT>), grid, blk, lds, st, a, *net);
     };
-    switch (phase) {
+    // What follows the stage kernels of phase p = 1, 2, 3: the controller in its mode p - 1, the time embeddings of the stage slots it
+    // set and, after an attempt, the record.  With ext_sums (a batch sharded over several GPUs) phase p launches the per-group sums in
+    // the controller's place (sums_only; an attempt ends there) and phase p + 10 runs all of it on the all-reduced sums.
+    auto controller = [&](int p, bool sums_only) {
+        if (sums_only) {
+            hipLaunchKernelGGL(rk45_group_sums_kernel, dim3(a.ngroups), blk1, 0, st, a, p == 1 ? 2 : 1);
+            if (p == 3) return;
+        } else {
+            hipLaunchKernelGGL(rk45_decide_kernel, dim3(a.ngroups), blk1, 0, st, a, p - 1);
+        }
+        embed(p == 1 ? 0 : 1, p == 1 ? 1 : 6);
+        if (p == 3 && a.traj) hipLaunchKernelGGL(rk45_record_kernel, dim3(64, a.ngroups), blk1, 0, st, a);
+    };
+    switch (c.phase) {
         case 0:
-            hipLaunchKernelGGL(rk45_reset_kernel, dim3(a.ngroups), dim3(64), 0, st, a.st, t0, t_bound, rtol, atol, traj_cap);
+            hipLaunchKernelGGL(rk45_reset_kernel, dim3(a.ngroups), dim3(64), 0, st, a.st, c.t0, c.t_bound, c.rtol, c.atol, c.traj_cap);
             embed(0, 1);
-            if (traj && hipMemcpyAsync(traj, y, n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return GP_ELAUNCH;
+            if (a.traj && hipMemcpyAsync(a.traj, a.y, n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return GP_ELAUNCH;
             break;
-        // with ext_sums (a batch sharded over several GPUs) phases 1-3 stop after the per-group sums and phases 11-13 run the
-        // controller on the all-reduced sums
         case 1:
             stage(std::integral_constant<int, 0>{});
-            if (a.ext_sums)
-                hipLaunchKernelGGL(rk45_group_sums_kernel, dim3(a.ngroups), blk1, 0, st, a, 2);
-            else
-                hipLaunchKernelGGL(rk45_decide_kernel, dim3(a.ngroups), blk1, 0, st, a, 0);
-            embed(0, 1);
-            break;
-        case 11:
-            if (!a.ext_sums) return GP_EINVAL;
-            hipLaunchKernelGGL(rk45_decide_kernel, dim3(a.ngroups), blk1, 0, st, a, 0);
-            embed(0, 1);
+            controller(1, a.ext_sums);
             break;
         case 2:
             stage(std::integral_constant<int, 7>{});
-            if (a.ext_sums)
-                hipLaunchKernelGGL(rk45_group_sums_kernel, dim3(a.ngroups), blk1, 0, st, a, 1);
-            else
-                hipLaunchKernelGGL(rk45_decide_kernel, dim3(a.ngroups), blk1, 0, st, a, 1);
-            embed(1, 6);
-            break;
-        case 12:
-            if (!a.ext_sums) return GP_EINVAL;
-            hipLaunchKernelGGL(rk45_decide_kernel, dim3(a.ngroups), blk1, 0, st, a, 1);
-            embed(1, 6);
+            controller(2, a.ext_sums);
             break;
         case 3:
             if constexpr (!CHAIN && !SPLIT && P == 16) {
@@ -1030,34 +1040,28 @@ static int rk45_phase_impl(int phase, OdeArgs &a, const gp_scorenet *net, double
                 stage(std::integral_constant<int, 5>{});
                 stage(std::integral_constant<int, 6>{});
             }
-            if (a.ext_sums) {
-                hipLaunchKernelGGL(rk45_group_sums_kernel, dim3(a.ngroups), blk1, 0, st, a, 1);
-                break;
-            }
-            hipLaunchKernelGGL(rk45_decide_kernel, dim3(a.ngroups), blk1, 0, st, a, 2);
-            embed(1, 6);
-            if (traj) hipLaunchKernelGGL(rk45_record_kernel, dim3(64, a.ngroups), blk1, 0, st, a);
+            controller(3, a.ext_sums);
             break;
+        case 11:
+        case 12:
         case 13:
             if (!a.ext_sums) return GP_EINVAL;
-            hipLaunchKernelGGL(rk45_decide_kernel, dim3(a.ngroups), blk1, 0, st, a, 2);
-            embed(1, 6);
-            if (traj) hipLaunchKernelGGL(rk45_record_kernel, dim3(64, a.ngroups), blk1, 0, st, a);
+            controller(c.phase - 10, false);
             break;
         case 4:
-            hipLaunchKernelGGL(rk45_set_slot0_kernel, dim3(a.ngroups), dim3(64), 0, st, a.st, t0);
+            hipLaunchKernelGGL(rk45_set_slot0_kernel, dim3(a.ngroups), dim3(64), 0, st, a.st, c.t0);
             embed(0, 1);
             break;
         case 5:
-            if (!x_out) return GP_EINVAL;
+            if (!c.x_out) return GP_EINVAL;
             if constexpr (OdeModel<MODEL>::NC != POSE) {
-                hipLaunchKernelGGL(rk45_copy_final_kernel, dim3(32, a.ngroups), blk1, 0, st, a, x_out);
+                hipLaunchKernelGGL(rk45_copy_final_kernel, dim3(32, a.ngroups), blk1, 0, st, a, c.x_out);
             } else {
                 OdeArgs af = a;  // (the denoising evaluation runs on whole tiles, one workgroup each, under every plan)
                 if constexpr (CHAIN) af.bpg = (a.rows_per_group + P - 1) / P, af.nblocks = af.bpg * a.ngroups;
-                hipLaunchKernelGGL((rk45_finish_kernel<P, MODEL>), dim3(af.nblocks), blk, lds, st, af, *net, denoise_scale, do_denoise, x_out);
-                if (traj && nstates > 0)
-                    hipLaunchKernelGGL(rk45_traj_post_kernel, dim3(128), blk1, 0, st, a.nrows, a.kcand, nstates, centre, traj);
+                hipLaunchKernelGGL((rk45_finish_kernel<P, MODEL>), dim3(af.nblocks), blk, lds, st, af, *net, c.denoise_scale, c.do_denoise, c.x_out);
+                if (a.traj && c.nstates > 0)
+                    hipLaunchKernelGGL(rk45_traj_post_kernel, dim3(128), blk1, 0, st, a.nrows, a.kcand, c.nstates, a.centre, a.traj);
             }
             break;
         default:
@@ -1092,6 +1096,27 @@ static int rk45_attempt_shared(const OdeArgs &a0, const SharedPlan &sp, const gp
     hipLaunchKernelGGL((rk45_embed_kernel<64, 1>), dim3(6, 1, 3), dim3(256), 0, st, a.st, 1, *net, a.tvec);
     if (traj) hipLaunchKernelGGL(rk45_record_kernel, dim3(64, 1), dim3(256), 0, st, ad);
     return gp_launch_status();
+}
+
+// A GP_PLAN_SHARED plan resolved to its geometry and to the whole-tile plan of the same launch size (`base`), or refused: it serves the
+// score model, one group, and the tile size shared_plan() names
+static bool shared_resolve(int model, int plan, int ngroups, int nclouds_per_group, int k, SharedPlan *sp, int *base) {
+    if (model != 0 || ngroups != 1 || nclouds_per_group <= 0 || k <= 0 || !shared_plan(nclouds_per_group * k, k, sp) || (plan & ~GP_PLAN_SHARED) != sp->pw)
+        return false;
+    *base = score_plan_rows(nclouds_per_group * k, 0, k);
+    return *base >= 0;
+}
+
+// The one table from (model, rows per workgroup P, OdeArgs::hsplit) to the instantiation that serves it.  Models 1, 2 and 4 run on 16-row
+// tiles or in the chain form (P = 128; not model 4); the chain form's denoising evaluation runs on 32-row tiles for the score model.
+static int rk45_dispatch(OdeArgs &a, int P, int model, const gp_scorenet *net, const Rk45Call &c) {
+    const bool chain = P == 128;
+    if (model == 1) return chain ? rk45_phase_impl<16, 1, true>(a, net, c) : rk45_phase_impl<16, 1>(a, net, c);
+    if (model == 2) return chain ? rk45_phase_impl<16, 2, true>(a, net, c) : rk45_phase_impl<16, 2>(a, net, c);
+    if (model == MODEL_EXACT) return rk45_phase_impl<16, MODEL_EXACT>(a, net, c);
+    if (chain) return rk45_phase_impl<32, 0, true>(a, net, c);
+    if (a.hsplit == 3) return rk45_phase_impl<16, 0, false, true>(a, net, c);
+    return gp_with_tile(P, [&](auto tile_rows) { return rk45_phase_impl<decltype(tile_rows)::value, 0>(a, net, c); });
 }
 
 extern "C" {
@@ -1135,16 +1160,35 @@ int gp_rk45_state_layout(int64_t *out, int n) {
 }
 
 // plan 0 of a model: a whole-tile plan (score_trunk.h); the exact-divergence likelihood runs on 16-row tiles only
-static int ode_plan_auto(int model, int ngroups, int rg, int k) {
+// `latency`: the score model's plan may be 16 | GP_PLAN_HEADSPLIT (the plan queries; never plan 0, see gp_rk45_phase_model)
+static int ode_plan_auto(int model, int ngroups, int rg, int k, bool latency = false) {
     if (model == MODEL_EXACT) return (ngroups > 1 && rg % 16 != 0) ? -1 : 16;
-    return model == 0 ? score_plan_rows(ngroups * rg, ngroups > 1 ? rg : 0, k) : score_plan_rows_vjp(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    const int nrows = ngroups * rg, stride = ngroups > 1 ? rg : 0;
+    if (model != 0) return score_plan_rows_vjp(nrows, stride, k);
+    return latency ? score_plan_latency(nrows, stride, k) : score_plan_rows(nrows, stride, k);
 }
 
-static int ode_args(OdeArgs *a, int *tile, int plan, int model, const float *probe, int ngroups, int nclouds_per_group, int k, const float *cvec, float *tvec,
-                    const float *centre, void *state, double *y, double *ynew, double *K, double *partials, double *traj, float *x32) {
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !cvec || !tvec || !centre || !state || !y || !ynew || !K || !partials) return GP_EINVAL;
-    if (!ode_model_known(model) || (model == 2 && !probe) || (model == MODEL_EXACT && probe)) return GP_EINVAL;
-    const int rg = nclouds_per_group * k;
+// The argument check every entry point and plan query of equal groups shares: rows per group, 0 = refused
+static int ode_rows_per_group(int model, int ngroups, int nclouds_per_group, int k) {
+    return (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !ode_model_known(model)) ? 0 : nclouds_per_group * k;
+}
+
+// The buffers of a solve, and the defaults of what its geometry sets on top: equal groups (ode_args) or the ragged tables
+static int ode_fill(OdeArgs *a, const float *probe, const float *cvec, float *tvec, const float *centre, void *state, double *y, double *ynew, double *K,
+                    double *partials, double *traj) {
+    if (!cvec || !tvec || !centre || !state || !y || !ynew || !K || !partials) return GP_EINVAL;
+    a->blk_info = nullptr, a->grp_info = nullptr;
+    a->cvec = cvec, a->tvec = tvec, a->centre = centre, a->st = (Rk45State *)state;
+    a->y = y, a->ynew = ynew, a->K = K, a->partials = partials, a->traj = traj, a->x32 = nullptr;
+    a->probe = probe, a->ncomp = 9;
+    a->ext_sums = nullptr, a->ext_rows = 0;
+    return GP_OK;
+}
+
+// Shape and plan check of equal groups behind ode_fill: their geometry, the model's state width, the sharded batch's sums
+static int ode_args(OdeArgs *a, int *tile, int plan, int model, int ngroups, int nclouds_per_group, int k, double *ext_sums, int ext_rows_per_group) {
+    const int rg = ode_rows_per_group(model, ngroups, nclouds_per_group, k);
+    if (!rg || (model == 2 && !a->probe) || (model == MODEL_EXACT && a->probe)) return GP_EINVAL;
     // launch plan of the stage kernels (score_trunk.h: score_plan_rows): 16 / 32-row tiles or the 128-row chain form; plan != 0 forces one
     // plan = 0: a WHOLE-tile plan (one partial sum per tile).  The head-split and shared-chunk plans keep more partial sums and are taken
     // only when the caller asks for them by name - gp_rk45_plan_rows() recommends, gp_rk45_partials_count() sizes the buffer.
@@ -1160,11 +1204,9 @@ static int ode_args(OdeArgs *a, int *tile, int plan, int model, const float *pro
     if (ngroups > 1 && rg % P != 0) return GP_EINVAL;  // workgroups must not straddle groups
     a->nrows = ngroups * rg, a->kcand = k;
     a->ngroups = ngroups, a->rows_per_group = rg, a->bpg = (rg + P - 1) / P, a->nblocks = a->bpg * ngroups;
-    a->blk_info = nullptr, a->grp_info = nullptr;
-    a->cvec = cvec, a->tvec = tvec, a->centre = centre, a->st = (Rk45State *)state;
-    a->y = y, a->ynew = ynew, a->K = K, a->partials = partials, a->traj = traj, a->x32 = x32;
-    a->probe = probe, a->ncomp = (model == 2 || model == MODEL_EXACT) ? 10 : 9;
-    a->ext_sums = nullptr, a->ext_rows = 0;
+    if (model == 2 || model == MODEL_EXACT) a->ncomp = 10;
+    if (ext_sums && ext_rows_per_group < rg) return GP_EINVAL;
+    a->ext_sums = ext_sums, a->ext_rows = ext_rows_per_group;
     *tile = P;
     return GP_OK;
 }
@@ -1191,44 +1233,19 @@ int gp_rk45_phase_model(int model, int plan, const float *probe, int phase, int 
                         int traj_cap, double t0, double t_bound, double rtol, double atol, double denoise_scale, int do_denoise, int nstates,
                         double *x_out, double *ext_sums, int ext_rows_per_group, gp_stream_t s) {
     OdeArgs a;
+    SharedPlan sp;
     int P = 0;
-    if (plan > 0 && (plan & GP_PLAN_SHARED)) {
-        // shared-chunk plan: the attempts run on it; the two initial evaluations, the denoising evaluation and the bookkeeping phases
-        // run on the whole-tile plan of the same launch size
-        SharedPlan sp;
-        if (model != 0 || ngroups != 1 || ext_sums || nclouds_per_group <= 0 || k <= 0 || !shared_plan(nclouds_per_group * k, k, &sp) ||
-            (plan & ~GP_PLAN_SHARED) != sp.pw)
-            return GP_EINVAL;
-        const int base = score_plan_rows(nclouds_per_group * k, 0, k);
-        if (base < 0) return GP_EINVAL;
-        if (phase != 3)
-            return gp_rk45_phase_model(model, base, probe, phase, ngroups, nclouds_per_group, k, net, cvec, tvec, centre, state, y, ynew, K, partials, traj, traj_cap,
-                                       t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, x_out, ext_sums, ext_rows_per_group, s);
-        if (ode_args(&a, &P, base, model, probe, ngroups, nclouds_per_group, k, cvec, tvec, centre, state, y, ynew, K, partials, traj, nullptr) != GP_OK || !net)
-            return GP_EINVAL;
+    // shared-chunk plan: the attempts run on it; the two initial evaluations, the denoising evaluation and the bookkeeping phases
+    // run on the whole-tile plan of the same launch size
+    const bool shared = plan > 0 && (plan & GP_PLAN_SHARED);
+    if (shared && (ext_sums || !shared_resolve(model, plan, ngroups, nclouds_per_group, k, &sp, &plan))) return GP_EINVAL;
+    if (ode_fill(&a, probe, cvec, tvec, centre, state, y, ynew, K, partials, traj) != GP_OK ||
+        ode_args(&a, &P, plan, model, ngroups, nclouds_per_group, k, ext_sums, ext_rows_per_group) != GP_OK || !net)
+        return GP_EINVAL;
+    if (shared && phase == 3)
         return sp.pw == 48 ? rk45_attempt_shared<48>(a, sp, net, traj, (hipStream_t)s) : rk45_attempt_shared<16>(a, sp, net, traj, (hipStream_t)s);
-    }
-    int rc = ode_args(&a, &P, plan, model, probe, ngroups, nclouds_per_group, k, cvec, tvec, centre, state, y, ynew, K, partials, traj, nullptr);
-    if (rc != GP_OK || !net) return GP_EINVAL;
-    if (ext_sums && ext_rows_per_group < a.rows_per_group) return GP_EINVAL;
-    a.ext_sums = ext_sums, a.ext_rows = ext_rows_per_group;
     if (model != 0 && (!net->w_headx_t || !net->w_pose2_t || !net->w_pose0_t)) return GP_EINVAL;
-#define GP_RK45_CALL(PP, MM) \
-    rk45_phase_impl<PP, MM>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out, (hipStream_t)s)
-#define GP_RK45_CHAIN(MM) \
-    rk45_phase_impl<16, MM, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out, (hipStream_t)s)
-    if (model == 1) return P == 128 ? GP_RK45_CHAIN(1) : GP_RK45_CALL(16, 1);
-    if (model == 2) return P == 128 ? GP_RK45_CHAIN(2) : GP_RK45_CALL(16, 2);
-    if (model == MODEL_EXACT) return GP_RK45_CALL(16, MODEL_EXACT);
-#undef GP_RK45_CHAIN
-    if (P == 128)
-        return rk45_phase_impl<32, 0, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out,
-                                            (hipStream_t)s);
-    if (a.hsplit == 3)
-        return rk45_phase_impl<16, 0, false, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out,
-                                                   (hipStream_t)s);
-    return P == 16 ? GP_RK45_CALL(16, 0) : (P == 64 ? GP_RK45_CALL(64, 0) : GP_RK45_CALL(32, 0));
-#undef GP_RK45_CALL
+    return rk45_dispatch(a, P, model, net, {phase, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, x_out, (hipStream_t)s});
 }
 
 /* gp_rk45_phase_model(model 0, plan 128) with the stage kernels' score trunk as exact-product split bf16 on the BF16 matrix pipe
@@ -1243,43 +1260,37 @@ int gp_rk45_phase_bf16x9(int phase, int ngroups, int nclouds_per_group, int k, c
     if (!net || !w_pose0_x9 || !w_pose2_x9 || !w_headx_x9) return GP_EINVAL;
     OdeArgs a;
     int P = 0;
-    if (ode_args(&a, &P, 128, 0, nullptr, ngroups, nclouds_per_group, k, cvec, tvec, centre, state, y, ynew, K, partials, traj, nullptr) != GP_OK || P != 128)
+    if (ode_fill(&a, nullptr, cvec, tvec, centre, state, y, ynew, K, partials, traj) != GP_OK ||
+        ode_args(&a, &P, 128, 0, ngroups, nclouds_per_group, k, ext_sums, ext_rows_per_group) != GP_OK)
         return GP_EINVAL;
-    if (ext_sums && ext_rows_per_group < a.rows_per_group) return GP_EINVAL;
-    a.ext_sums = ext_sums, a.ext_rows = ext_rows_per_group;
     const gp_split::SplitNet w = gp_split::split_net(net, w_pose0_x9, w_pose2_x9, w_headx_x9);
-    return rk45_phase_impl<32, 0, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out, (hipStream_t)s,
-                                        &w);
-}
-
-int gp_rk45_plan_rows(int model, int ngroups, int nclouds_per_group, int k) {
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !ode_model_known(model)) return GP_EINVAL;
-    const int rg = nclouds_per_group * k;
-    if (model != 0) return ode_plan_auto(model, ngroups, rg, k);
-    SharedPlan sp;
-    if (ngroups == 1 && shared_plan(rg, k, &sp)) return sp.pw | GP_PLAN_SHARED;  // a few chunks more than whole rounds of the CUs
-    return score_plan_latency(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    return rk45_dispatch(a, P, 0, net, {phase, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, x_out, (hipStream_t)s, &w});
 }
 
 /* gp_rk45_plan_rows without the shared-chunk plan (a batch sharded over several GPUs: its controller runs on all-reduced per-group sums) */
 int gp_rk45_plan_rows_unshared(int model, int ngroups, int nclouds_per_group, int k) {
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !ode_model_known(model)) return GP_EINVAL;
-    const int rg = nclouds_per_group * k;
-    if (model != 0) return ode_plan_auto(model, ngroups, rg, k);
-    return score_plan_latency(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    const int rg = ode_rows_per_group(model, ngroups, nclouds_per_group, k);
+    return rg ? ode_plan_auto(model, ngroups, rg, k, true) : GP_EINVAL;
+}
+
+int gp_rk45_plan_rows(int model, int ngroups, int nclouds_per_group, int k) {
+    const int rg = ode_rows_per_group(model, ngroups, nclouds_per_group, k);
+    SharedPlan sp;
+    if (rg && model == 0 && ngroups == 1 && shared_plan(rg, k, &sp)) return sp.pw | GP_PLAN_SHARED;  // a few chunks more than whole rounds of the CUs
+    return gp_rk45_plan_rows_unshared(model, ngroups, nclouds_per_group, k);
 }
 
 /* Doubles the `partials` buffer of gp_rk45_phase_model must hold under `plan` (0 = what plan 0 resolves to), every phase included. */
 int gp_rk45_partials_count(int model, int plan, int ngroups, int nclouds_per_group, int k) {
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0 || !ode_model_known(model)) return GP_EINVAL;
-    const int rg = nclouds_per_group * k;
+    const int rg = ode_rows_per_group(model, ngroups, nclouds_per_group, k);
+    if (!rg) return GP_EINVAL;
     auto whole = [&](int p) { return 3 * ngroups * ((rg + p - 1) / p); };
     if (plan == 0) plan = ode_plan_auto(model, ngroups, rg, k);
     if (plan < 0) return GP_EINVAL;
     if (plan & GP_PLAN_SHARED) {
         SharedPlan sp;
-        if (model != 0 || ngroups != 1 || !shared_plan(rg, k, &sp) || (plan & ~GP_PLAN_SHARED) != sp.pw) return GP_EINVAL;
-        const int base = score_plan_rows(rg, 0, k);
+        int base;
+        if (!shared_resolve(model, plan, ngroups, nclouds_per_group, k, &sp, &base)) return GP_EINVAL;
         const int a = whole(base), b = 3 * (sp.nwg + sp.nshared);
         return a > b ? a : b;
     }
@@ -1296,8 +1307,7 @@ int gp_rk45_phase_grouped(int phase, int ngroups, int nclouds_per_group, int k, 
                           gp_stream_t s) {
     // the entry points that predate the plan argument keep the partials size their contract states ([3][ngroups * ceil(rows per group /
     // tile)]): whole tiles - the head-split plan (three partial sums per tile) is reached through gp_rk45_phase_model only
-    if (ngroups <= 0 || nclouds_per_group <= 0 || k <= 0) return GP_EINVAL;
-    const int rg = nclouds_per_group * k, legacy_plan = score_plan_rows(ngroups * rg, ngroups > 1 ? rg : 0, k);
+    const int rg = ode_rows_per_group(0, ngroups, nclouds_per_group, k), legacy_plan = rg ? ode_plan_auto(0, ngroups, rg, k) : -1;
     if (legacy_plan < 0) return GP_EINVAL;
     return gp_rk45_phase_model(0, legacy_plan, nullptr, phase, ngroups, nclouds_per_group, k, net, cvec, tvec, centre, state, y, ynew, K, partials, traj, traj_cap, t0,
                                t_bound, rtol, atol, denoise_scale, do_denoise, nstates, x_out, nullptr, 0, s);
@@ -1307,25 +1317,16 @@ int gp_rk45_phase_ragged(int phase, int ngroups, const int32_t *grp_info, int nb
                          const gp_scorenet *net, const float *cvec, float *tvec, const float *centre, void *state, double *y, double *ynew,
                          double *K, double *partials, double *traj, int traj_cap, double t0, double t_bound, double rtol, double atol,
                          double denoise_scale, int do_denoise, int nstates, double *x_out, gp_stream_t s) {
-    if (ngroups <= 0 || nblocks <= 0 || !grp_info || !blk_info || (tile != 16 && tile != 32 && tile != (16 | GP_PLAN_HEADSPLIT)) || nclouds_total <= 0 ||
-        k <= 0 || !net || !cvec || !tvec || !centre || !state || !y || !ynew || !K || !partials)
-        return GP_EINVAL;
     OdeArgs a;
+    if (ngroups <= 0 || nblocks <= 0 || !grp_info || !blk_info || (tile != 16 && tile != 32 && tile != (16 | GP_PLAN_HEADSPLIT)) || nclouds_total <= 0 ||
+        k <= 0 || !net || ode_fill(&a, nullptr, cvec, tvec, centre, state, y, ynew, K, partials, traj) != GP_OK)
+        return GP_EINVAL;
     a.hsplit = (tile & GP_PLAN_HEADSPLIT) ? 3 : 1;
     a.nrows = nclouds_total * k, a.kcand = k, a.nblocks = nblocks;
     a.ngroups = ngroups, a.bpg = 1, a.rows_per_group = 0;
     a.blk_info = blk_info, a.grp_info = grp_info;
-    a.cvec = cvec, a.tvec = tvec, a.centre = centre, a.st = (Rk45State *)state;
-    a.y = y, a.ynew = ynew, a.K = K, a.partials = partials, a.traj = traj, a.x32 = nullptr;
-    a.probe = nullptr, a.ncomp = 9;
-    a.ext_sums = nullptr, a.ext_rows = 0;
-    if (a.hsplit == 3)
-        return rk45_phase_impl<16, 0, false, true>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out,
-                                                   (hipStream_t)s);
-    return tile == 16 ? rk45_phase_impl<16, 0>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out,
-                                               (hipStream_t)s)
-                      : rk45_phase_impl<32, 0>(phase, a, net, traj, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, centre, x_out,
-                                               (hipStream_t)s);
+    return rk45_dispatch(a, tile & ~GP_PLAN_HEADSPLIT, 0, net,
+                         {phase, traj_cap, t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, x_out, (hipStream_t)s});
 }
 
 int gp_rk45_phase(int phase, int nclouds, int k, const gp_scorenet *net, const float *cvec, float *tvec, const float *centre, void *state,

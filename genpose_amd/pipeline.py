@@ -7,7 +7,7 @@ tests/test_gpu_pipeline.py):
                         encoder of the next group runs on a second HIP stream under the sampler graph of the current one
                         (`overlap`), and its furthest point sampling and ball queries always run ahead on a side stream (`fps_ahead`).
   GroupedODEPredictor   encoder + PF-ODE sampler, several batches per launch of the device-resident RK45 driver, one step
-                        controller per batch (gp_rk45_phase_grouped).
+                        controller per batch (gp_rk45_phase_model).
   (runner.MultiSequenceTracker does the same for tracking, with ragged groups.)
 
 Host code in these loops is allocation-free and keeps its CPU tensor ops single-threaded (see _randn_1t).
@@ -194,7 +194,7 @@ class PipelinedPCPredictor:
 class GroupedODEPredictor:
     """pred_func(encoder + PF-ODE sampler) for a stream of equally-shaped batches, `batches_per_launch` of them sharing every encoder
     pass and every launch of the device-resident RK45 driver.  Each batch keeps its own adaptive step control
-    (gp_rk45_phase_grouped), i.e. gets what `PoseNet.pred_func` returns for it alone; the host only polls the per-batch status
+    (gp_rk45_phase_model), i.e. gets what `PoseNet.pred_func` returns for it alone; the host only polls the per-batch status
     words between replays of the captured attempts."""
 
     def __init__(self, score_agent, B, K, T0=None, batches_per_launch=5):

@@ -777,7 +777,7 @@ class ODESampler:
                  trunk=None):
         """B clouds in `groups` independent batches of B/groups clouds laid out back to back: every batch keeps its own adaptive
         step control (error norm over ITS rows, accept / reject, step size - what separate cond_ode_sampler calls would do) while
-        all of them share each launch (gp_rk45_phase_grouped).
+        all of them share each launch (gp_rk45_phase_model).
 
         model: what the driver integrates (gp_rk45_phase_model) - 'score' the probability-flow ODE of the score network; 'energy' the
         same ODE with the ENERGY network's score (`net` holds its weights; forward + vector-Jacobian product inside the stage
@@ -930,28 +930,24 @@ class ODESampler:
     def _phase(self, phase, traj=None, t0=0.0, t_bound=0.0, rtol=1e-5, atol=1e-5, dscale=0.0, do_denoise=1, nstates=0):
         import ctypes
         cd = ctypes.c_double
-        tail = (ptr(self.cvec), ptr(self.tvec), ptr(self.centre), ptr(self.state), ptr(self.y), ptr(self.ynew), ptr(self.Kbuf), ptr(self.partials),
-                ptr(traj), 0 if traj is None else traj.shape[0], cd(t0), cd(t_bound), cd(rtol), cd(atol), cd(dscale), do_denoise, nstates,
-                ptr(self.x_out), stream_ptr())
+        # every entry point takes: its own head, the phase, its geometry, the solver's buffers (_lib.RK45_SOLVE), its own tail, the stream
+        fn, head, tail = "gp_rk45_phase_ragged", (), ()
         if self.ragged:
-            _lib.call("gp_rk45_phase_ragged", phase, self.groups, ptr(self.grp_info), self.nblocks, ptr(self.blk_info), self.plan, self.B, self.K,
-                      self.net.w.ref(), *tail)
-        elif self.trunk == "bf16x9":
-            x9 = tuple(ptr(w) for w in self._x9)
-            _lib.call("gp_rk45_phase_bf16x9", phase, self.groups, self.B // self.groups, self.K, self.net.w.ref(), *tail[:-1], ptr(self.ext_sums), self.ext_rows,
-                      *x9, tail[-1])
-            if self.ext_sums is not None and phase in (1, 2, 3):
-                self._dist.all_reduce(self.ext_sums, op=self._dist.ReduceOp.SUM, group=self.coupling_group)
-                _lib.call("gp_rk45_phase_bf16x9", phase + 10, self.groups, self.B // self.groups, self.K, self.net.w.ref(), *tail[:-1], ptr(self.ext_sums),
-                          self.ext_rows, *x9, tail[-1])
+            geom = (self.groups, ptr(self.grp_info), self.nblocks, ptr(self.blk_info), self.plan, self.B, self.K)
         else:
-            _lib.call("gp_rk45_phase_model", self.model, self.plan, ptr(self.probe), phase, self.groups, self.B // self.groups, self.K, self.net.w.ref(), *tail[:-1],
-                      ptr(self.ext_sums), self.ext_rows, tail[-1])
-            if self.ext_sums is not None and phase in (1, 2, 3):
-                # sharded batch: the controller decides on the sums of squares over ALL shards
-                self._dist.all_reduce(self.ext_sums, op=self._dist.ReduceOp.SUM, group=self.coupling_group)
-                _lib.call("gp_rk45_phase_model", self.model, self.plan, ptr(self.probe), phase + 10, self.groups, self.B // self.groups, self.K, self.net.w.ref(),
-                          *tail[:-1], ptr(self.ext_sums), self.ext_rows, tail[-1])
+            geom, tail = (self.groups, self.B // self.groups, self.K), (ptr(self.ext_sums), self.ext_rows)
+            if self.trunk == "bf16x9":
+                fn, tail = "gp_rk45_phase_bf16x9", tail + tuple(ptr(w) for w in self._x9)
+            else:
+                fn, head = "gp_rk45_phase_model", (self.model, self.plan, ptr(self.probe))
+        solve = (*geom, self.net.w.ref(), ptr(self.cvec), ptr(self.tvec), ptr(self.centre), ptr(self.state), ptr(self.y), ptr(self.ynew), ptr(self.Kbuf),
+                 ptr(self.partials), ptr(traj), 0 if traj is None else traj.shape[0], cd(t0), cd(t_bound), cd(rtol), cd(atol), cd(dscale), do_denoise,
+                 nstates, ptr(self.x_out), *tail, stream_ptr())
+        _lib.call(fn, *head, phase, *solve)
+        if self.ext_sums is not None and not self.ragged and phase in (1, 2, 3):
+            # sharded batch: the controller decides on the sums of squares over ALL shards
+            self._dist.all_reduce(self.ext_sums, op=self._dist.ReduceOp.SUM, group=self.coupling_group)
+            _lib.call(fn, *head, phase + 10, *solve)
 
     def _attempt(self, traj):
         # the step controller at the end of phase 3 (and of phase 2 before the first attempt) also writes the time embeddings of the

@@ -193,7 +193,55 @@ def test_against_fp32_chain_and_graph_replay(B, K, groups):
     np.testing.assert_allclose(out["bf16x9"], out["f32mfma"], rtol=0, atol=2e-5 * float(np.abs(out["f32mfma"]).max()))
 
 
-# ----------------------------------------------------------------------------- 7. agent pass-through
+# ----------------------------------------------------------------------------- 7. sharded controller on the chain plan
+class _OneRank:
+    """torch.distributed as a world of one rank sees it: the sum of a buffer over the ranks is the buffer."""
+
+    class ReduceOp:
+        SUM = "sum"
+
+    @staticmethod
+    def all_reduce(t, op=None, group=None):
+        pass
+
+
+@pytest.mark.parametrize("trunk", [None, "bf16x9"])
+def test_sharded_controller_on_the_chain_plan(trunk):
+    """Phases 11-13 (a sharded batch: per-group sums, the caller's all-reduce, the controller on the reduced sums) through plan 128 and through
+    gp_rk45_phase_bf16x9, in a world of one rank and no process group: the sums the controller reads are the sums it forms itself, added in
+    another place.  Same attempt count, poses within the bound test_gpu_coupled.py holds this identity to on RCCL."""
+    from genpose_amd import _lib
+    from genpose_amd.samplers import ODESampler
+    net = x9._net()
+    B, K, groups, T0 = 4, 50, 1, 0.4
+    feat, centre, x0, _, _ = x9._inputs(B, K, 1, B + K)
+    x0 = x0 / 50.0 * float(go.ve_sigma(T0))
+    cvec = net.cloud_embed(feat.cuda())
+    smp = ODESampler(net, B, K, "cuda", use_graph=False, groups=groups, tile=128, trunk=trunk)
+    assert smp.plan == 128 and smp.kernel_name == (X9_KERNEL if trunk == "bf16x9" else "rk45_stage_chain_kernel<2>")
+    alone = smp.run(cvec, centre.cuda(), x0.cuda(), T0)[1].cpu().numpy()
+    n_alone = int(smp.group_stats[0]["n_attempts"])
+    smp.ext_sums = torch.zeros(2, groups, dtype=torch.float64, device="cuda")
+    smp.ext_rows = smp.R // groups
+    smp._dist = _OneRank
+    sharded = smp.run(cvec, centre.cuda(), x0.cuda(), T0)[1].cpu().numpy()
+    n_sharded = int(smp.group_stats[0]["n_attempts"])
+    print(f"trunk {trunk}: attempts {n_alone} / {n_sharded}, max |sharded - alone| {np.abs(sharded - alone).max():.2e}")
+    assert n_sharded == n_alone
+    np.testing.assert_allclose(sharded, alone, rtol=0, atol=1e-9 * max(1.0, np.abs(alone).max()))
+    # the entry points themselves: the controller phases need the sums, the bf16x9 one needs every pack
+    ptr, cd = (lambda t: ctypes.c_void_p(t.data_ptr())), ctypes.c_double
+    solve = (net.w.ref(), ptr(smp.cvec), ptr(smp.tvec), ptr(smp.centre), ptr(smp.state), ptr(smp.y), ptr(smp.ynew), ptr(smp.Kbuf), ptr(smp.partials),
+             None, 0, cd(T0), cd(rr.EPS), cd(1e-5), cd(1e-5), cd(0.0), 1, 0, ptr(smp.x_out))
+    packs = [ptr(w) for w in net.w.bf16x9_packs()]
+    lib = _lib.lib()
+    assert lib.gp_rk45_phase_model(0, 128, None, 11, groups, B, K, *solve, None, 0, None) == -1
+    assert lib.gp_rk45_phase_bf16x9(11, groups, B, K, *solve, None, 0, *packs, None) == -1
+    assert lib.gp_rk45_phase_bf16x9(0, groups, B, K, *solve, None, 0, packs[0], None, packs[2], None) == -1
+    torch.cuda.synchronize()
+
+
+# ----------------------------------------------------------------------------- 8. agent pass-through
 def test_config_flag_reaches_the_sampler():
     """get_config(ode_trunk='bf16x9'): GFObjectPose.sample builds the ODE sampler with it (part of its cache key); at a chain-plan shape
     (640 clouds x 50) the poses are those of a directly built ODESampler(trunk='bf16x9') on the same prior draw."""
