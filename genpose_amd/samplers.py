@@ -1109,6 +1109,7 @@ class ODESampler:
         self._phase(4, traj, t0=eps)
         nstates = (num_steps if dense else int(st["n_accepted"]) + 1) if traj is not None else 0
         if traj is not None and not dense and nstates > self.TRAJ_CAP:
+            self._attempt_hist.pop((gname, round(float(T0), 3)), None)  # a failed solve leaves no attempt-count expectation behind
             raise RuntimeError(f"ODE sampler: {nstates} accepted states exceed the trajectory capacity {self.TRAJ_CAP}")
         dscale = (1 - eps) / (1000 if num_steps is None else num_steps)
         self._phase(5, traj, dscale=dscale, do_denoise=1 if denoise else 0, nstates=nstates)
