@@ -16,7 +16,8 @@ PLAN_SHARED = 0x200     # GP_PLAN_SHARED: the RK45 driver's shared-chunk plan (1
 PLAN_FLAGS = 0x300
 RK45_MODEL_LIKELIHOOD_EXACT = 4  # GP_RK45_MODEL_LIKELIHOOD_EXACT: the likelihood ODE with the exact divergence (3 stays an unknown model)
 CONSENSUS_MAX_K = 512   # GP_CONSENSUS_MAX_K: the largest candidate count the consensus ranker's LDS layout serves
-MODE_MAX_ITERS = 64     # GP_MODE_MAX_ITERS: the most mean-shift iterations gp_mode_aggregate runs
+EXTENT_MAX_N = 4096    # GP_EXTENT_MAX_N: the largest cloud gp_cloud_extent keeps in a wave's registers
+MODE_MAX_ITERS = 64    # GP_MODE_MAX_ITERS: the most mean-shift iterations gp_mode_aggregate runs
 PLAN_HEADSPLIT = 0x100  # GP_PLAN_HEADSPLIT (include/genpose_hip.h): OR-ed onto a 16-row tile plan = three workgroups per tile, one head each
 
 
@@ -78,6 +79,9 @@ SIGNATURES = {
     "gp_cloud_sample": [c_int, c_int, c_int, P, P, P, P, P],
     "gp_roi_sample_seeded": [c_int] * 5 + [P, P, P] + [c_float] * 4 + [P] * 5 + [P],
     "gp_roi_sample_frames": [c_int] * 6 + [P, P, c_int64] + [P] * 4 + [c_float] * 4 + [P] * 5 + [P],
+    "gp_cloud_extent": [c_int, c_int, P, P, c_int, P, P, P],
+    "gp_box_sample_max_segments": [],
+    "gp_box_sample": [c_int] * 5 + [P] * 4 + [c_float, c_float, c_int] + [c_float] * 4 + [P] * 5 + [P],
     "gp_score_div": [c_int, c_int, NETP, P, P, P, P, P, P, P, P],
     "gp_energy_score": [c_int, c_int, NETP, P, P, P, P, P, P, P],
     "gp_score_div_exact": [c_int, c_int, NETP, P, P, P, P, P, P, P],

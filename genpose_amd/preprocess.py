@@ -230,6 +230,33 @@ def check_frame_tables(t):
     return t
 
 
+def check_box_inputs(depth, rt, half, frame_of, inflate, pad, min_count):
+    """device_clouds_boxes' argument rules, device-free: -> (depth, rt, half, frame_of as tensors where they were arrays, F, H, W, n).
+    ValueError / RuntimeError (depth that is not uint16, as device_clouds) before anything touches a device."""
+    depth = torch.as_tensor(np.ascontiguousarray(depth)) if not torch.is_tensor(depth) else depth
+    if depth.dim() == 3:
+        if depth.shape[0] < 1:
+            raise ValueError("device_clouds_boxes: at least one frame")
+        H, W = _depth_hw(depth[0], 0)
+    else:
+        H, W = _depth_hw(depth, 0)
+    F = depth.shape[0] if depth.dim() == 3 else 1
+    as_f32 = lambda t: (t if torch.is_tensor(t) else torch.as_tensor(np.ascontiguousarray(t, dtype=np.float32)))
+    rt, half = as_f32(rt), as_f32(half)
+    n = rt.shape[0] if rt.dim() == 3 else -1
+    if n < 0 or tuple(rt.shape) != (n, 4, 4) or tuple(half.shape) != (n, 3) or rt.dtype != torch.float32 or half.dtype != torch.float32:
+        raise ValueError(f"device_clouds_boxes: rt float32 [n,4,4] and half float32 [n,3], got {rt.dtype} {tuple(rt.shape)} and {half.dtype} {tuple(half.shape)}")
+    if frame_of is not None:
+        frame_of = frame_of if torch.is_tensor(frame_of) else torch.as_tensor(np.ascontiguousarray(frame_of))
+        if tuple(frame_of.shape) != (n,) or frame_of.dtype.is_floating_point:
+            raise ValueError(f"device_clouds_boxes: frame_of holds one frame index per object ([{n}]), got {frame_of.dtype} {tuple(frame_of.shape)}")
+    if not (np.isfinite(inflate) and inflate > 0 and np.isfinite(pad) and pad >= 0):
+        raise ValueError(f"device_clouds_boxes: inflate finite > 0 and pad finite >= 0, got {inflate} and {pad}")
+    if int(min_count) != min_count or min_count < 0:
+        raise ValueError(f"device_clouds_boxes: min_count an integer >= 0, got {min_count}")
+    return depth, rt, half, frame_of, F, H, W, n
+
+
 def assemble_detect_result(keys, results, class_ids, frame, inst, valid, points):
     """Host arrays of a batched front end -> the reference's `detect_result` dict (evaluation_single.py:241-253):
     keys[f] -> {'result': results[f], 'valid_pts': [n_pts,3] float32 per kept instance, 'cat_id': class_id - 1 per kept instance,
@@ -403,6 +430,87 @@ class DepthToClouds:
         st["pin_minv"][slot].send(st["minv"], lambda h: h.copy_(torch.from_numpy(minv_h)))
         st["pin_seed"][slot].send(st["seed"], lambda h: h.copy_(torch.from_numpy(words.view(np.int32))))
         return self.launch_seeded(depth.contiguous(), masks.contiguous(), st["minv"], st["seed"], out)
+
+    # ------------------------------------------------------------------ mask-free (ours): clouds from depth and oriented boxes
+    def empty_outputs_boxes(self, n):
+        """The output dict of device_clouds_boxes for n objects (pass it as `out` and the call allocates nothing)."""
+        return {"points": torch.empty(n, self.n_pts, 3, device=self.dev), "count": torch.zeros(n, dtype=torch.int32, device=self.dev),
+                "valid": torch.zeros(n, dtype=torch.uint8, device=self.dev)}
+
+    def launch_boxes(self, depth, frame_of, rt, half, inflate, pad, min_count, seed_state, out):
+        """gp_box_sample on device tensors alone: depth [F,H,W] uint16 / int16, frame_of [n] int32 or None (frame 0), rt [n,4,4] f32, half
+        [n,3] f32, seed_state [8] int32 (word 2 = run, word 4 = the slot of object 0), out as empty_outputs_boxes(n).  One launch, nothing
+        else: capturable after a first call outside the capture."""
+        if depth.dim() != 3 or depth.dtype not in (torch.uint16, torch.int16):
+            raise ValueError(f"launch_boxes: depth uint16 [F,H,W], got {depth.dtype} {tuple(depth.shape)}")
+        F, H, W = depth.shape
+        n = rt.shape[0]
+        if tuple(rt.shape) != (n, 4, 4) or rt.dtype != torch.float32 or tuple(half.shape) != (n, 3) or half.dtype != torch.float32:
+            raise ValueError(f"launch_boxes: rt float32 [n,4,4] and half float32 [n,3], got {rt.dtype} {tuple(rt.shape)} and {half.dtype} {tuple(half.shape)}")
+        if frame_of is not None and (tuple(frame_of.shape) != (n,) or frame_of.dtype != torch.int32):
+            raise ValueError(f"launch_boxes: frame_of int32 [{n}], got {frame_of.dtype} {tuple(frame_of.shape)}")
+        if seed_state.dtype != torch.int32 or seed_state.numel() != 8:
+            raise ValueError("launch_boxes: seed_state int32 [8]")
+        if not (1 <= H <= 32767 and 1 <= W <= 32767 and F >= 1):
+            raise ValueError(f"launch_boxes: {F} frames of {H} x {W}; at least one, sides in 1..32767")
+        if not (np.isfinite(inflate) and inflate > 0 and np.isfinite(pad) and pad >= 0):
+            raise ValueError(f"launch_boxes: inflate finite > 0 and pad finite >= 0, got {inflate} and {pad}")
+        if int(min_count) != min_count or min_count < 0:
+            raise ValueError(f"launch_boxes: min_count an integer >= 0, got {min_count}")
+        for name, shape, dtype in (("points", (n, self.n_pts, 3), torch.float32), ("count", (n,), torch.int32), ("valid", (n,), torch.uint8)):
+            if tuple(out[name].shape) != shape or out[name].dtype != dtype or out[name].device.type != "cuda":
+                raise ValueError(f"out[{name!r}]: a device tensor {shape} {dtype}, got {tuple(out[name].shape)} {out[name].dtype} on {out[name].device}")
+        if any(t is not None and t.device.type != "cuda" for t in (depth, frame_of, rt, half, seed_state)):
+            raise ValueError("launch_boxes: device tensors only")
+        if n == 0:
+            return out
+        _lib.call("gp_box_sample", H, W, F, n, self.n_pts, ptr(depth), ptr(frame_of), ptr(rt), ptr(half), float(inflate), float(pad), int(min_count),
+                  self.fx, self.fy, self.cx, self.cy, ptr(seed_state), None, ptr(out["points"]), ptr(out["count"]), ptr(out["valid"]), stream_ptr())
+        return out
+
+    def device_clouds_boxes(self, depth, rt, half, seed, run=0, *, frame_of=None, inflate=1.15, pad=0.01, min_count=2, slot_base=0, out=None):
+        """Depth + one oriented box per object -> dict(points [n,n_pts,3] f32, count [n] i32, valid [n] u8) on the device, one launch
+        (gp_box_sample), NO mask and nothing read back: what a tracker that already holds the objects' poses needs in place of a
+        segmentation.  Ours - the reference has no counterpart (its tracking loop reads ground-truth masks) and no parity is claimed; the
+        clouds are the frame's NATIVE pixels, not the 256 x 256 crop-and-resize of device_clouds.
+        rt [n,4,4] f32: object -> camera poses (average_sRT's layout); half [n,3] f32: half-extents in the object frame (reward.cloud_extent);
+        object i's box is |q_j| <= half[i][j] * inflate + pad, q = R^T (p - t) in the float32 order of include/genpose_hip.h.  count = the
+        pixels with depth whose point lies inside (-1: the box's pixel rectangle has more 64-pixel segments than gp_box_sample_max_segments);
+        valid = count >= max(2, min_count) with finite rt and a box of positive size; the others' rows are zero.  More than n_pts inside:
+        the n_pts rows are drawn as in device_clouds - points[i] == (the inside pixels in raster order)[seeded_ranks(count[i], n_pts, seed,
+        run, slot_base + i)].
+        depth: [H,W] or [F,H,W] uint16 millimetres, a host array (copied through a pinned block into a static device buffer) or a device
+        tensor (used as it is); frame_of [n] (optional): each object's frame, default frame 0.  rt, half, frame_of: device tensors are used
+        as they are, host arrays are uploaded.  out: empty_outputs_boxes(n) of an earlier call - then nothing is allocated."""
+        from .graphs import PinnedBlock
+        depth, rt, half, frame_of, F, H, W, n = check_box_inputs(depth, rt, half, frame_of, inflate, pad, min_count)
+        if out is None:
+            out = self.empty_outputs_boxes(n)
+        if n == 0:
+            return out
+        key = ("boxes", F, H, W)
+        st = self._staging.get(key)
+        if st is None:
+            if len(self._staging) >= 8:
+                self._staging.pop(next(iter(self._staging)))
+            st = self._staging[key] = {"seed": torch.zeros(8, dtype=torch.int32, device=self.dev),
+                                       "pin_seed": [PinnedBlock((8,), torch.int32) for _ in range(self.RING)], "ring": 0}
+        slot = st["ring"] = (st["ring"] + 1) % self.RING
+        if depth.device.type != "cuda":
+            if "pin_depth" not in st:
+                st["depth"] = torch.empty(F, H, W, dtype=torch.int16, device=self.dev)
+                st["pin_depth"] = [PinnedBlock((F, H, W), torch.int16) for _ in range(self.RING)]
+            depth16 = depth.view(torch.int16).reshape(F, H, W)
+            depth = st["pin_depth"][slot].send(st["depth"], lambda h: h.copy_(depth16))
+        else:
+            depth = depth.contiguous().view(F, H, W)
+        rt, half = rt.to(self.dev).contiguous(), half.to(self.dev).contiguous()
+        if frame_of is not None:
+            frame_of = frame_of.to(device=self.dev, dtype=torch.int32).contiguous()
+        seed = int(seed) % (1 << 64)
+        words = np.array([seed & 0xFFFFFFFF, seed >> 32, int(run) & 0xFFFFFFFF, 0, int(slot_base) & 0xFFFFFFFF, 0, 0, 0], dtype=np.uint32)
+        st["pin_seed"][slot].send(st["seed"], lambda h: h.copy_(torch.from_numpy(words.view(np.int32))))
+        return self.launch_boxes(depth, frame_of, rt, half, inflate, pad, min_count, st["seed"], out)
 
     # ------------------------------------------------------------------ many frames in one launch
     def empty_outputs_frames(self, n):

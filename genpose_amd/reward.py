@@ -149,6 +149,32 @@ def mode_aggregate(poses, sym=None, weight=None, bw_rot_deg=MODE_BW_ROT_DEG, bw_
     return out
 
 
+def cloud_extent(pts, rt, trim=0, sym=None):
+    """pts [B,n,3] f32 (device), rt [B,4,4] f32 (object -> camera: avg_RT's layout) -> half [B,3] f32 (gp_cloud_extent; ours, no counterpart
+    in the reference): per cloud and object axis j the (trim + 1)-th largest |q_j| over its points, q = R^T (p - t) in the float32 operation
+    order of include/genpose_hip.h - exactly a value of the array, np.sort's bits.  trim = 0: the maximum.  sym [B] (optional): objects
+    symmetric about their y axis measure the radius sqrt(q_0^2 + q_2^2) into columns 0 and 2.  2 * half is the object's size in a frame
+    centred on it.  One launch, nothing read back."""
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.dtype != torch.float32:
+        raise ValueError(f"pts must be float32 [B,n,3], got {pts.dtype} {tuple(pts.shape)}")
+    B, n, _ = pts.shape
+    if tuple(rt.shape) != (B, 4, 4) or rt.dtype != torch.float32:
+        raise ValueError(f"rt must be float32 [{B},4,4], got {rt.dtype} {tuple(rt.shape)}")
+    if not 1 <= n <= _lib.EXTENT_MAX_N:
+        raise ValueError(f"cloud_extent serves clouds of 1..{_lib.EXTENT_MAX_N} points, got {n}")
+    if int(trim) != trim or not 0 <= trim < n:
+        raise ValueError(f"trim must be an integer in 0..{n - 1}, got {trim}")
+    sym = _sym_arg(sym, B, pts.device)
+    if pts.device.type != "cuda" or rt.device != pts.device:
+        raise ValueError(f"pts and rt must be on one GPU, got {pts.device} and {rt.device}")
+    pts, rt = pts.contiguous(), rt.contiguous()
+    _lib.check_device()
+    out = torch.empty(B, 3, device=pts.device)
+    if B:
+        _lib.call("gp_cloud_extent", B, n, ptr(pts), ptr(rt), int(trim), ptr(sym), ptr(out), stream_ptr())
+    return out
+
+
 def sort_poses_by_energy(poses, energy):
     """Same contract as networks/reward.py:131-155 -> (sorted_poses [B,K,9], sorted_energy [B,K,2])."""
     r = rank_aggregate(poses, energy)

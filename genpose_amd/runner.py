@@ -654,6 +654,14 @@ class FixedStepTracker:
         for i in (range(len(self.buffers)) if seq is None else [seq]):
             self.buffers[i], self.frame_index[i] = [], 0
 
+    def pose_slots(self, seq, n):
+        """The warm-start slots of sequence `seq`'s first n objects: a [n,4,4] f32 VIEW of the tensor the captured graphs read (where an
+        object continues from) and write (its aggregated pose) - a caller that decides on the device whether an object keeps its new pose
+        (DepthTracker: a lost object does not) overwrites it in stream order.  After the sequence's first step."""
+        if self._prev is None or not 0 <= seq < len(self.buffers) or not 0 <= n <= self.max_objects:
+            raise ValueError(f"pose_slots(seq={seq}, n={n}): a sequence that has had a step, at most max_objects_per_frame = {self.max_objects} objects")
+        return self._prev[seq * self.max_objects: seq * self.max_objects + n]
+
     # ------------------------------------------------------------------ host side
     def _grow(self, nseq, dev):
         while len(self.buffers) < nseq:
@@ -863,4 +871,71 @@ class FixedStepTracker:
             self.frame_index[i] += 1
             out[i] = {"init_x": init_x[sl], "pred_pose": pred[sl], "energy": energy[sl], "sorted_RTs": sorted_RTs[sl], "average_sRT": average_sRT[sl].clone(),
                       "nfev": smp.nlaunch - 1}
+        return out
+
+
+class DepthTracker:
+    """Mask-free tracking of ONE sequence (ours; opt-in; the reference has no counterpart - its tracking loop cuts every frame's clouds out
+    with the dataset's ground-truth masks, evaluation_tracking.py:262-337 - and no parity with it is claimed).  Around a
+    FixedStepTracker(init='prior') that the caller constructs: after an object has been acquired once from a mask, its last pose and its
+    size say where it is in the next depth frame, so a frame needs the depth image alone -
+        acquire(depth, masks, rois, names)   clouds from the mask front end (DepthToClouds.device_clouds), one tracker step from the prior,
+                                             then half = reward.cloud_extent(clouds, poses): the objects' sizes, fixed from here on;
+        track(depth)                         clouds from depth and the stored boxes (DepthToClouds.device_clouds_boxes, draw run = the
+                                             sequence's frame count), one tracker step, and the stored pose replaced only where the box
+                                             gave a valid cloud: a LOST object keeps its previous pose, here and in the tracker's warm-start
+                                             slot - a select on the device, in stream order.
+    Both return the tracker's dict for the sequence plus points [n,n_pts,3], count [n] i32, valid [n] u8 (the front end's), half [n,3] and
+    pose [n,4,4] (the stored poses after the select); between the depth upload and these device tensors nothing is read back.  The clouds
+    of track() are the frame's native pixels inside the boxes, not the 256 x 256 crop-and-resize of the mask front end.  Sizes are not
+    re-estimated, boxes do not reason about each other's occlusion, and a lost object is not re-acquired: call acquire again.
+    trim: cloud_extent's (the trim + 1 largest |q_j| is the half-extent: 0 = the maximum); inflate, pad, min_count: device_clouds_boxes'."""
+
+    def __init__(self, tracker, front_end=None, trim=0, inflate=1.15, pad=0.01, min_count=2):
+        if getattr(tracker, "init", None) != "prior":
+            raise ValueError("DepthTracker wraps a FixedStepTracker(init='prior'): it has no ground truth to start an object from")
+        if int(trim) != trim or trim < 0:
+            raise ValueError(f"DepthTracker(trim={trim}): an integer >= 0")
+        if not (np.isfinite(inflate) and inflate > 0 and np.isfinite(pad) and pad >= 0):
+            raise ValueError(f"DepthTracker(inflate={inflate}, pad={pad}): inflate finite > 0, pad finite >= 0")
+        if int(min_count) != min_count or min_count < 0:
+            raise ValueError(f"DepthTracker(min_count={min_count}): an integer >= 0")
+        if front_end is None:
+            from .preprocess import DepthToClouds
+            front_end = DepthToClouds()
+        self.tracker, self.fe = tracker, front_end
+        self.trim, self.inflate, self.pad, self.min_count = int(trim), float(inflate), float(pad), int(min_count)
+        self.names = self.rt = self.half = self.valid = None
+
+    def acquire(self, depth, masks, rois, names, symmetric=None):
+        """symmetric: None (the tracker's own `symmetric` callable, if it has one), a callable model_name -> bool or one flag per object -
+        objects symmetric about their y axis measure one radius for x and z."""
+        tr = self.tracker
+        names = list(names)
+        if not 1 <= len(names) <= tr.max_objects or len(names) != len(rois):
+            raise ValueError(f"acquire: {len(names)} names for {len(rois)} rois; 1..max_objects_per_frame = {tr.max_objects} objects")
+        if symmetric is None:
+            symmetric = getattr(tr, "symmetric", None)
+        sym = [bool(symmetric(nm)) for nm in names] if callable(symmetric) else symmetric
+        tr.reset()
+        fe = self.fe.device_clouds(depth, masks, rois, tr.seed, run=0)
+        out = dict(tr.step([(fe["points"], names, None)])[0])
+        half = reward.cloud_extent(fe["points"], out["average_sRT"], min(self.trim, fe["points"].shape[1] - 1), sym)
+        self.names, self.rt, self.half, self.valid = names, out["average_sRT"].clone(), half, fe["valid"].clone()
+        out.update(points=fe["points"], count=fe["count"], valid=fe["valid"], half=half, pose=self.rt)
+        return out
+
+    def track(self, depth):
+        if self.names is None:
+            raise RuntimeError("DepthTracker.track before acquire: there is no object to look for")
+        tr = self.tracker
+        n = len(self.names)
+        fe = self.fe.device_clouds_boxes(depth, self.rt, self.half, tr.seed, run=tr.frame_index[0], inflate=self.inflate, pad=self.pad,
+                                         min_count=self.min_count)
+        out = dict(tr.step([(fe["points"], self.names, None)])[0])
+        # a lost object keeps the pose it had: in this object's copy and in the slot the next frame's warm start reads
+        self.rt = torch.where((fe["valid"] != 0).view(n, 1, 1), out["average_sRT"], self.rt)
+        tr.pose_slots(0, n).copy_(self.rt)
+        self.valid = fe["valid"]
+        out.update(points=fe["points"], count=fe["count"], valid=fe["valid"], half=self.half, pose=self.rt)
         return out

@@ -100,6 +100,47 @@ int gp_roi_sample_seeded(int h, int w, int ninst, int img, int npts, const uint1
 int gp_roi_sample_frames(int h, int w, int nframes, int ndet, int img, int npts, const uint16_t *depth, const uint8_t *masks, int64_t mask_bytes,
                          const int64_t *mask_off, const int32_t *det, const uint32_t *draw, const double *minv, float fx, float fy, float cx, float cy,
                          const uint32_t *seed_state, float *out, int32_t *count, int32_t *depth_count, uint8_t *valid, gp_stream_t s);
+/* MASK-FREE TRACKING (ours; opt-in; NO counterpart in the reference, whose tracking loop takes its clouds from the dataset's ground-truth
+ * masks, evaluation_tracking.py:262-337): once an object has a pose, its pose and size say where its cloud is in the next depth frame.
+ * THE OBJECT-FRAME EXPRESSION both entry points share (one device function): camera-frame point p, pose rt (float32 [4][4] row major,
+ * object -> camera: the layout of gp_rank_aggregate_rt's avg_rt), R = rt[:3][:3], t = rt[:3][3]:
+ *     u_j = p_j - t_j      q_j = ((u_0 * R[0][j]) + (u_1 * R[1][j])) + (u_2 * R[2][j])      j = 0, 1, 2
+ *   every product and every sum rounded to float32 on its own (numpy float32 restates the bits: tests/box_front_end_reference.py).
+ * gp_cloud_extent: half-extents of a cloud in its object frame.  pts [b][n][3], rt [b][4][4], half_out [b][3].  For cloud i,
+ *   a_j[k] = |q_j(pts[i][k])| and half_out[i][j] = the (trim + 1)-th LARGEST of a_j[0..n-1] (trim = 0: the maximum; duplicated points count
+ *   as often as they occur) - EXACT: a value of the array, the bits np.sort gives.  sym [b] int8 or NULL (gp_consensus_energy's
+ *   convention): sym[i] != 0 = symmetric about the y axis, then half_out[i][0] = half_out[i][2] = that order statistic of
+ *   sqrt_rn(add_rn(mul_rn(q_0, q_0), mul_rn(q_2, q_2))).  The frame is centred on the object, so 2 * half is its size also when only the
+ *   camera-facing side was seen.  One wave per cloud, the values in registers, a bisection over the 31 value bits with wave-wide counts:
+ *   no sort, no barrier, the same trip count on every bit pattern; non-finite input neither faults nor hangs (its result is unspecified).
+ *   1 <= n <= GP_EXTENT_MAX_N, 0 <= trim < n, b >= 0, pts / rt / half_out non-NULL - else GP_EINVAL, nothing written; b == 0: GP_OK.  A
+ *   cloud's row does not depend on the rest of the batch.  No allocation, no synchronisation: capturable.
+ * gp_box_sample: depth + oriented boxes -> the sampled clouds, one launch, no mask.  depth [nframes][h][w] uint16 mm; frame_of [nobj] =
+ *   each object's frame (NULL: frame 0); rt [nobj][4][4], half [nobj][3]; points [nobj][npts][3], count / valid [nobj].  For object i on
+ *   its frame, hh_j = add_rn(mul_rn(half[i][j], inflate), pad); pixel (sx, sy) with depth word dv is INSIDE when dv > 0 and
+ *   |q_j(p)| <= hh_j for j = 0, 1, 2, p = gp_roi_to_cloud's float32 back-projection ((sx - cx) * d / fx) / 1000, ((sy - cy) * d / fy) /
+ *   1000, d / 1000.  count[i] = c = the inside pixels of the WHOLE image; valid[i] = c >= max(2, min_count) and every entry of rt[i] and
+ *   hh finite and every hh_j > 0; a valid object's row k is the inside pixel of rank r in the image's raster order, c < npts: r = k % c,
+ *   c == npts: r = k, c > npts: r = gp_roi_sample_seeded's seeded walk sigma(k) under (seed, run, slot) - draw [nobj][2] = {run, slot},
+ *   or NULL: seed_state words [2] and [4] + i as gp_roi_sample_seeded; seed_state: its 8 uint32 words.  valid[i] == 0: all-zero rows.
+ *   The kernel scans only the pixel rectangle of the box's eight projected corners, widened by two pixels and clipped - the whole image
+ *   where a corner lies nearer than 0.05 m, projects to something non-finite or rt[i] is no rotation (|R^T R - I| > 1e-5): the rectangle
+ *   is an accelerator, membership is the inside test alone, the result is the whole-image definition bit for bit.  The rectangle's
+ *   (row, 64-column segment) table lives in LDS, 12 bytes a segment: a clipped rectangle of more than gp_box_sample_max_segments()
+ *   segments (a whole 640 x 480 frame has 4 800) gets count = -1, valid = 0 and zero rows, never a truncated scan.  A frame_of entry
+ *   outside [0, nframes) is an object without a cloud (count = 0, valid = 0, zero rows), decided before anything is read through it.
+ *   1 <= h, w <= 32767, nframes >= 1, nobj >= 0, npts >= 1, inflate finite > 0, pad finite >= 0, min_count >= 0, depth / rt / half /
+ *   seed_state / points / count / valid non-NULL - else GP_EINVAL, nothing written; nobj == 0: GP_OK.  One 16-wave workgroup per object
+ *   running gp_roi_sample_seeded's ballot / scan / select code (one template, two pixel sources); an object's outputs do not depend on
+ *   what shares its launch.  The first call raises the kernel's dynamic-LDS limit (make it outside a stream capture); then capturable. */
+#define GP_EXTENT_MAX_N 4096
+int gp_cloud_extent(int b, int n, const float *pts /*[b,n,3]*/, const float *rt /*[b,4,4]*/, int trim, const int8_t *sym /*[b] or NULL*/,
+                    float *half_out /*[b,3]*/, gp_stream_t s);
+int gp_box_sample_max_segments(void);
+int gp_box_sample(int h, int w, int nframes, int nobj, int npts, const uint16_t *depth /*[nframes,h,w] mm*/, const int32_t *frame_of /*[nobj] or NULL*/,
+                  const float *rt /*[nobj,4,4]*/, const float *half /*[nobj,3]*/, float inflate, float pad, int min_count, float fx, float fy, float cx,
+                  float cy, const void *seed_state, const uint32_t *draw /*[nobj][2] run, slot; or NULL*/, float *points /*[nobj,npts,3]*/,
+                  int32_t *count /*[nobj]*/, uint8_t *valid /*[nobj]*/, gp_stream_t s);
 
 /* Library / device identification: returns ABI version; writes gcnArchName of the current device. */
 int gp_version(void);
