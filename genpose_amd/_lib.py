@@ -6,6 +6,8 @@ There is NO CPU fallback: if the library is missing or a call fails, the caller 
 import ctypes
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GENPOSE_HIP_LIB: tuning only (a variant built with GP_BUILD_TAG=<tag> beside the shipped library, genpose_amd/build.py)
 SO_PATH = os.environ.get("GENPOSE_HIP_LIB") or os.path.join(_HERE, "lib", "libgenpose_hip.so")
@@ -28,6 +30,17 @@ class GpScoreNet(ctypes.Structure):
 
 
 NETP = ctypes.POINTER(GpScoreNet)
+
+
+def seed_words(seed, run=0, base=0):
+    """The Philox seed state the kernels read (csrc/philox.h) -> np.uint32 [8]: seed lo, seed hi, run, 0, row base lo, row base hi, 0, 0 -
+    the little-endian words of the uint64s [seed mod 2^64, run, base, 0], so .view(np.int64) is the same state for an int64 [4] tensor."""
+    seed, run, base = int(seed) % (1 << 64), int(run), int(base)
+    if not 0 <= run < (1 << 32):
+        raise ValueError(f"run_index {run}: 32 bits")
+    if not 0 <= base < (1 << 63):
+        raise ValueError(f"row_base {base}")
+    return np.array([seed, run, base, 0], dtype="<u8").view(np.uint32)
 
 # what every gp_rk45_phase* entry point takes behind its geometry: net, cvec, tvec, centre, state, y, ynew, K, partials, traj, traj_cap,
 # t0, t_bound, rtol, atol, denoise_scale, do_denoise, nstates, x_out

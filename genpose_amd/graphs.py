@@ -1,5 +1,6 @@
 """The host layer's two small protocols, written once: capture a launch sequence once per shape, then replay it (`capture`,
-`Captured.replay`, `release`, `CapturedPasses`), and upload a small host block in stream order through one pinned buffer (`PinnedBlock`).
+`Captured.replay`, `release`, `CapturedPasses`), and upload a small host block in stream order through one pinned buffer (`PinnedBlock`;
+`UploadRing`: a rotation of such blocks, for an owner that uploads on every call and must not wait for the call before).
 
 A pin is a count on a workspace dict (`_pins`): a workspace with a count above zero stays out of its cache's eviction order
 (`unpinned`).  Its buffers were allocated outside the capture and nothing but that cache holds them, so it must outlive every graph that
@@ -130,7 +131,7 @@ class PinnedBlock:
         """fill(block) writes the host block.  dst: the device tensor to overwrite, or a device - then a fresh tensor there.  The copy
         is in stream order on the current stream of dst's device; returns the device tensor.  rows: only the block's first `rows`
         entries along dim 0 travel (a block sized by capacity, a dst at least as long: its rest keeps what it held)."""
-        self._ev.synchronize()  # the previous copy out of the pinned block has completed
+        self.wait()
         fill(self.host)
         src = self.host if rows is None else self.host[:rows]
         if torch.is_tensor(dst):
@@ -139,3 +140,34 @@ class PinnedBlock:
             dst = src.to(dst, non_blocking=True)
         self._ev.record(torch.cuda.current_stream(dst.device))
         return dst
+
+    def wait(self):
+        self._ev.synchronize()  # the last copy out of the block has completed: the host may rewrite it, or let it go
+
+
+class UploadRing:
+    """`depth` slots of pinned blocks in rotation, for an owner that uploads the same few buffers on every call: advance() once per call,
+    then send(name, ...) through the current slot's block of that name.  The host rewrites a block only `depth` calls after the copy out of
+    it was issued, so the wait inside PinnedBlock.send finds that copy long completed and the host runs ahead of the device."""
+
+    def __init__(self, depth, block=PinnedBlock):
+        self.depth, self.slot, self._block, self._blocks = int(depth), 0, block, {}
+
+    def advance(self):
+        self.slot = (self.slot + 1) % self.depth
+
+    def send(self, name, dst, fill, rows=None):
+        """PinnedBlock.send through the block of (current slot, name): made on first use with dst's shape and dtype, and again when dst
+        has been reallocated to another shape.  dst a device: through the block a send to a tensor has made (a device gives no shape)."""
+        key = (self.slot, name)
+        blk = self._blocks.get(key)
+        if torch.is_tensor(dst) and (blk is None or blk.host.shape != dst.shape or blk.host.dtype != dst.dtype):
+            if blk is not None:
+                blk.wait()
+            blk = self._blocks[key] = self._block(tuple(dst.shape), dst.dtype)
+        return blk.send(dst, fill, rows)
+
+    def drop(self, name):
+        """Forgets every slot's block of `name` once the last copy out of each has completed (the device buffer is being reallocated)."""
+        for key in [k for k in self._blocks if k[1] == name]:
+            self._blocks.pop(key).wait()

@@ -15,6 +15,7 @@ Host code in these loops is allocation-free and keeps its CPU tensor ops single-
 import torch
 
 from . import _lib
+from .graphs import PinnedBlock
 from .samplers import PCSampler
 from .sde import SIGMA_MAX, SIGMA_MIN
 
@@ -77,8 +78,7 @@ class PipelinedPCPredictor:
         self.x0 = [torch.empty(R, 9, device=self.dev) for _ in range(depth)]
         self.ev_enc = [torch.cuda.Event() for _ in range(depth)]
         self.ev_free = [torch.cuda.Event() for _ in range(depth)]
-        self.prior_host = [torch.empty(R, 9).pin_memory() for _ in range(depth)]
-        self.ev_h2d = [torch.cuda.Event() for _ in range(depth)]  # the async H2D copy out of prior_host[slot] has completed
+        self.prior_host = [PinnedBlock((R, 9)) for _ in range(depth)]
         for e in self.ev_free:
             e.record(self.s_smp[0])
 
@@ -146,11 +146,9 @@ class PipelinedPCPredictor:
                 self.centre[slot][:nb].copy_(pts.mean(dim=1))
                 x0 = self.x0[slot][:nr]
                 if prior_noise is None:
-                    self.ev_h2d[slot].synchronize()  # host may run `depth` launches ahead, not further (pinned buffer reuse)
-                    host = self.prior_host[slot][:nr]
-                    _randn_1t(host)  # CPU generator, as sde.py:28
-                    x0.copy_(host, non_blocking=True)
-                    self.ev_h2d[slot].record(self.s_enc)
+                    # CPU generator, as sde.py:28.  (The slot's block waits for its previous copy: the host may run `depth` launches ahead,
+                    # not further; the copy and its event go onto the current stream, s_enc)
+                    self.prior_host[slot].send(self.x0[slot], lambda h: _randn_1t(h[:nr]), rows=nr)
                 else:
                     x0.copy_(torch.cat([prior_noise[i0 + q].reshape(B1 * K, 9) for q in range(g)], dim=0))
                 x0.mul_(SIGMA_MAX)  # prior std at T = 1 (cond_pc_sampler always starts from T = 1)
@@ -229,7 +227,7 @@ class GroupedODEPredictor:
             N = batches[0].shape[1]
             self._pts = torch.empty(G * B1, N, 3, device=self.dev)
             self._x0 = torch.empty(G * B1 * K, 9, device=self.dev)
-            self._prior_host = torch.empty(G * B1 * K, 9).pin_memory()
+            self._prior_host = PinnedBlock((G * B1 * K, 9))
         for i0 in range(0, n, G):
             g = min(G, n - i0)
             pts = self._pts[: g * B1]
@@ -238,9 +236,8 @@ class GroupedODEPredictor:
             cvec = self.net.pose_score_net.cloud_embed(self.net.pts_encoder(pts))
             x0 = self._x0[: g * B1 * K]
             if prior_noise is None:
-                host = self._prior_host[: g * B1 * K]
-                _randn_1t(host)  # CPU generator, as sde.py:28
-                x0.copy_(host, non_blocking=True)
+                # CPU generator, as sde.py:28; the block waits for the previous group's copy before the draw overwrites it
+                self._prior_host.send(self._x0, lambda h: _randn_1t(h[: g * B1 * K]), rows=g * B1 * K)
             else:
                 for q in range(g):
                     x0[q * B1 * K:(q + 1) * B1 * K].copy_(prior_noise[i0 + q].reshape(B1 * K, 9))
@@ -285,11 +282,9 @@ class FullPipelinePredictor:
         self.share_grouping = self.snet.pts_encoder.grouping_key() == self.enet.pts_encoder.grouping_key()
         self.side = torch.cuda.Stream(self.dev, priority=0) if overlap else None
         self._smp = {}
-        self.ev_h2d = torch.cuda.Event()
-        self.ev_h2d.record()
         self.ev_side = torch.cuda.Event()
         R = self.G * B * K
-        self.prior_host = torch.empty(R, 9).pin_memory()
+        self.prior_host = PinnedBlock((R, 9))
         self.x0 = torch.empty(R, 9, device=self.dev)
         self.pose_e = torch.empty(R, 9, device=self.dev)
         t = torch.full((1,), float(T_energy), device=self.dev)
@@ -349,11 +344,7 @@ class FullPipelinePredictor:
         cvec = self.snet.pose_score_net.cloud_embed(enc_s.forward(pts, grouping=grouping))
         x0 = self.x0[: B * K]
         if prior_noise is None:
-            self.ev_h2d.synchronize()
-            host = self.prior_host[: B * K]
-            _randn_1t(host)  # CPU generator, as sde.py:28
-            x0.copy_(host, non_blocking=True)
-            self.ev_h2d.record(cur)
+            self.prior_host.send(self.x0, lambda h: _randn_1t(h[: B * K]), rows=B * K)  # CPU generator, as sde.py:28; the copy goes onto `cur`
         else:
             x0.copy_(prior_noise.reshape(B * K, 9))
         x0.mul_(SIGMA_MAX)

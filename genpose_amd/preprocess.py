@@ -12,6 +12,8 @@ import torch
 
 from . import _lib
 from ._lib import ptr, stream_ptr
+from .graphs import UploadRing
+from .lru import ShapeCache
 
 REAL_INTRINSICS = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]], dtype=np.float32)   # evaluation_single.py:54
 CAMERA_INTRINSICS = np.array([[577.5, 0, 319.5], [0, 577.5, 239.5], [0, 0, 1]], dtype=np.float32)            # evaluation_single.py:50
@@ -230,10 +232,39 @@ def check_frame_tables(t):
     return t
 
 
+def _as_tensor(x):
+    """A host array as a (contiguous) tensor; a tensor, on any device, as it is."""
+    return x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x))
+
+
+def _check_frame(depth, masks, rois):
+    """One frame's inputs as tensors -> (depth, masks, n).  RuntimeError: depth that is not uint16; ValueError: not one mask per roi."""
+    depth, masks = _as_tensor(depth), _as_tensor(masks)
+    if depth.dtype not in (torch.uint16, torch.int16):
+        raise RuntimeError("depth must be uint16 millimetres")
+    n = masks.shape[2] if masks.dim() == 3 else 0
+    if n != len(rois):
+        raise ValueError(f"{n} masks for {len(rois)} rois")
+    return depth, masks, n
+
+
+def _check_out(out, fields):
+    """The `out` dict of a launch_* method: every (name, shape, dtype) of `fields` a device tensor of that shape and dtype.  ValueError."""
+    for name, shape, dtype in fields:
+        if tuple(out[name].shape) != shape or out[name].dtype != dtype or out[name].device.type != "cuda":
+            raise ValueError(f"out[{name!r}]: a device tensor {shape} {dtype}, got {tuple(out[name].shape)} {out[name].dtype} on {out[name].device}")
+
+
+def _seed_fill(seed, run=0, slot_base=0):
+    """The fill of a pinned int32 [8] block with the front ends' seed state: the low 32 bits of run and slot_base travel (word 5 stays 0)."""
+    words = _lib.seed_words(seed, int(run) % (1 << 32), int(slot_base) & 0xFFFFFFFF)
+    return lambda h: h.copy_(torch.from_numpy(words.view(np.int32)))
+
+
 def check_box_inputs(depth, rt, half, frame_of, inflate, pad, min_count):
     """device_clouds_boxes' argument rules, device-free: -> (depth, rt, half, frame_of as tensors where they were arrays, F, H, W, n).
     ValueError / RuntimeError (depth that is not uint16, as device_clouds) before anything touches a device."""
-    depth = torch.as_tensor(np.ascontiguousarray(depth)) if not torch.is_tensor(depth) else depth
+    depth = _as_tensor(depth)
     if depth.dim() == 3:
         if depth.shape[0] < 1:
             raise ValueError("device_clouds_boxes: at least one frame")
@@ -247,7 +278,7 @@ def check_box_inputs(depth, rt, half, frame_of, inflate, pad, min_count):
     if n < 0 or tuple(rt.shape) != (n, 4, 4) or tuple(half.shape) != (n, 3) or rt.dtype != torch.float32 or half.dtype != torch.float32:
         raise ValueError(f"device_clouds_boxes: rt float32 [n,4,4] and half float32 [n,3], got {rt.dtype} {tuple(rt.shape)} and {half.dtype} {tuple(half.shape)}")
     if frame_of is not None:
-        frame_of = frame_of if torch.is_tensor(frame_of) else torch.as_tensor(np.ascontiguousarray(frame_of))
+        frame_of = _as_tensor(frame_of)
         if tuple(frame_of.shape) != (n,) or frame_of.dtype.is_floating_point:
             raise ValueError(f"device_clouds_boxes: frame_of holds one frame index per object ([{n}]), got {frame_of.dtype} {tuple(frame_of.shape)}")
     if not (np.isfinite(inflate) and inflate > 0 and np.isfinite(pad) and pad >= 0):
@@ -305,19 +336,37 @@ class DepthToClouds:
         K = np.asarray(intrinsics, dtype=np.float32).reshape(-1)
         self.fx, self.fy, self.cx, self.cy = float(K[0]), float(K[4]), float(K[2]), float(K[5])
         self.n_pts, self.img, self.dev = n_pts, img_size, torch.device(device)
-        self._staging = {}  # device_clouds: (H, W, n) -> static device inputs and their pinned blocks
-        self._staging_frames = {}  # device_clouds_frames: (H, W) -> device buffers sized by capacity and their pinned blocks
+        self._staging = ShapeCache(8)  # device_clouds: (H, W, n), device_clouds_boxes: ("boxes", F, H, W) -> _stage's entry
+        self._staging_frames = ShapeCache(4)  # device_clouds_frames: (H, W) -> the same, its buffers sized by capacity
+
+    def _stage(self, cache, key, depth):
+        """-> (the staging entry of `key`: device buffers by name (_reserve) and the ring their pinned blocks rotate in, that ring), the ring
+        advanced: once per call of a front end."""
+        st = cache.get(key)
+        if st is None:
+            st = cache[key] = {"ring": UploadRing(depth)}
+        st["ring"].advance()
+        return st, st["ring"]
+
+    def _reserve(self, st, name, need, tail, dtype):
+        """st[name]: a device buffer [capacity, *tail] with capacity >= need - sized by capacity, it only grows (by half at least), so a
+        ragged sequence of batches does not reallocate on every call; its pinned blocks go with it."""
+        cap = st[name].shape[0] if name in st else 0
+        if cap < need:
+            st["ring"].drop(name)  # (each block after the last copy out of it has completed)
+            st[name] = torch.empty((max(need, cap + cap // 2),) + tail, dtype=dtype, device=self.dev)
+        return st[name]
+
+    def _out_fields(self, n, depth_count=True):
+        """What _check_out holds an `out` dict to: empty_outputs(n)'s tensors, or (depth_count=False) empty_outputs_boxes(n)'s."""
+        f = [("points", (n, self.n_pts, 3), torch.float32), ("count", (n,), torch.int32), ("depth_count", (n,), torch.int32),
+             ("valid", (n,), torch.uint8)]
+        return f if depth_count else f[:2] + f[3:]
 
     def full_clouds(self, depth, masks, rois):
         """All valid points of every detection, raster order of the crop: (pcl [n,img*img,3] f32, count [n], depth_count [n])."""
-        depth = torch.as_tensor(np.ascontiguousarray(depth)) if not torch.is_tensor(depth) else depth
-        if depth.dtype not in (torch.uint16, torch.int16):
-            raise RuntimeError("depth must be uint16 millimetres")
+        depth, masks, n = _check_frame(depth, masks, rois)
         H, W = depth.shape
-        masks = torch.as_tensor(np.ascontiguousarray(masks)) if not torch.is_tensor(masks) else masks
-        n = masks.shape[2] if masks.dim() == 3 else 0
-        if n != len(rois):
-            raise ValueError(f"{n} masks for {len(rois)} rois")
         depth = depth.to(self.dev).contiguous()
         masks = masks.to(self.dev).to(torch.uint8).contiguous()
         minv = np.stack([inverse_crop_map(get_bbox(r, H, W), self.img, H, W) for r in rois]).reshape(n, 6) if n else np.zeros((0, 6))
@@ -361,10 +410,7 @@ class DepthToClouds:
         int32 (csrc/philox.h's seed state; word 4 = the slot of detection 0), out as empty_outputs(n).  One launch, nothing else: capturable."""
         H, W = depth.shape
         n = masks.shape[2]
-        for name, shape, dtype in (("points", (n, self.n_pts, 3), torch.float32), ("count", (n,), torch.int32),
-                                   ("depth_count", (n,), torch.int32), ("valid", (n,), torch.uint8)):
-            if tuple(out[name].shape) != shape or out[name].dtype != dtype or out[name].device.type != "cuda":
-                raise ValueError(f"out[{name!r}]: a device tensor {shape} {dtype}, got {tuple(out[name].shape)} {out[name].dtype} on {out[name].device}")
+        _check_out(out, self._out_fields(n))
         if masks.dtype != torch.uint8 or depth.dtype not in (torch.uint16, torch.int16) or minv.dtype != torch.float64 or tuple(minv.shape) != (n, 6) \
                 or seed_state.dtype != torch.int32 or seed_state.numel() != 8:
             raise ValueError("launch_seeded: depth uint16 [H,W], masks uint8 [H,W,n], minv float64 [n,6], seed_state int32 [8]")
@@ -384,52 +430,29 @@ class DepthToClouds:
         minv (from rois, on the host as in full_clouds) and the seed words go up through pinned blocks in stream order; depth / masks may be
         host arrays (copied through pinned blocks into static device buffers) or device tensors (uint16 / uint8: used as they are).  out: empty_outputs(n) of an
         earlier call - then nothing is allocated."""
-        from .graphs import PinnedBlock
-        depth = torch.as_tensor(np.ascontiguousarray(depth)) if not torch.is_tensor(depth) else depth
-        if depth.dtype not in (torch.uint16, torch.int16):
-            raise RuntimeError("depth must be uint16 millimetres")
+        depth, masks, n = _check_frame(depth, masks, rois)
         H, W = depth.shape
-        masks = torch.as_tensor(np.ascontiguousarray(masks)) if not torch.is_tensor(masks) else masks
-        n = masks.shape[2] if masks.dim() == 3 else 0
-        if n != len(rois):
-            raise ValueError(f"{n} masks for {len(rois)} rois")
         if self.img > MAX_IMG_SEEDED:
             raise ValueError(f"device_clouds: img_size {self.img} > {MAX_IMG_SEEDED} (the kernel keeps the crop's ballots in LDS); use __call__")
         if out is None:
             out = self.empty_outputs(n)
         if n == 0:
             return out
-        st = self._staging.get((H, W, n))
-        if st is None:
-            if len(self._staging) >= 8:
-                self._staging.pop(next(iter(self._staging)))
-            st = self._staging[(H, W, n)] = {
-                "depth": torch.empty(H, W, dtype=torch.int16, device=self.dev), "masks": torch.empty(H, W, n, dtype=torch.uint8, device=self.dev),
-                "minv": torch.empty(n, 6, dtype=torch.float64, device=self.dev), "seed": torch.zeros(8, dtype=torch.int32, device=self.dev),
-                "pin_minv": [PinnedBlock((n, 6), torch.float64) for _ in range(self.RING)],
-                "pin_seed": [PinnedBlock((8,), torch.int32) for _ in range(self.RING)], "ring": 0}
-        slot = st["ring"] = (st["ring"] + 1) % self.RING
+        st, ring = self._stage(self._staging, (H, W, n), self.RING)
         # host images go up through pinned blocks like everything else: a non-blocking copy out of pageable memory (and, for bool masks, out
         # of the temporary of the dtype conversion, freed on return) leaves the runtime reading host memory the caller may already have freed
         if depth.device.type != "cuda":
-            if "pin_depth" not in st:
-                st["pin_depth"] = [PinnedBlock((H, W), torch.int16) for _ in range(self.RING)]
             depth16 = depth.view(torch.int16)
-            depth = st["pin_depth"][slot].send(st["depth"], lambda h: h.copy_(depth16))
+            depth = ring.send("depth", self._reserve(st, "depth", H, (W,), torch.int16), lambda h: h.copy_(depth16))
         if masks.device.type != "cuda":
-            if "pin_masks" not in st:
-                st["pin_masks"] = [PinnedBlock((H, W, n), torch.uint8) for _ in range(self.RING)]
             masks_h = masks
-            masks = st["pin_masks"][slot].send(st["masks"], lambda h: h.copy_(masks_h))  # (bool -> uint8: 0 / 1, on the host)
+            masks = ring.send("masks", self._reserve(st, "masks", H, (W, n), torch.uint8), lambda h: h.copy_(masks_h))  # (bool -> uint8: 0 / 1, on the host)
         elif masks.dtype != torch.uint8:
-            st["masks"].copy_(masks)
-            masks = st["masks"]
+            masks = self._reserve(st, "masks", H, (W, n), torch.uint8).copy_(masks)
         minv_h = np.stack([inverse_crop_map(get_bbox(r, H, W), self.img, H, W) for r in rois]).reshape(n, 6)
-        seed = int(seed) % (1 << 64)
-        words = np.array([seed & 0xFFFFFFFF, seed >> 32, int(run) & 0xFFFFFFFF, 0, int(slot_base) & 0xFFFFFFFF, 0, 0, 0], dtype=np.uint32)
-        st["pin_minv"][slot].send(st["minv"], lambda h: h.copy_(torch.from_numpy(minv_h)))
-        st["pin_seed"][slot].send(st["seed"], lambda h: h.copy_(torch.from_numpy(words.view(np.int32))))
-        return self.launch_seeded(depth.contiguous(), masks.contiguous(), st["minv"], st["seed"], out)
+        minv = ring.send("minv", self._reserve(st, "minv", n, (6,), torch.float64), lambda h: h.copy_(torch.from_numpy(minv_h)))
+        seed_state = ring.send("seed", self._reserve(st, "seed", 8, (), torch.int32), _seed_fill(seed, run, slot_base))
+        return self.launch_seeded(depth.contiguous(), masks.contiguous(), minv, seed_state, out)
 
     # ------------------------------------------------------------------ mask-free (ours): clouds from depth and oriented boxes
     def empty_outputs_boxes(self, n):
@@ -457,9 +480,7 @@ class DepthToClouds:
             raise ValueError(f"launch_boxes: inflate finite > 0 and pad finite >= 0, got {inflate} and {pad}")
         if int(min_count) != min_count or min_count < 0:
             raise ValueError(f"launch_boxes: min_count an integer >= 0, got {min_count}")
-        for name, shape, dtype in (("points", (n, self.n_pts, 3), torch.float32), ("count", (n,), torch.int32), ("valid", (n,), torch.uint8)):
-            if tuple(out[name].shape) != shape or out[name].dtype != dtype or out[name].device.type != "cuda":
-                raise ValueError(f"out[{name!r}]: a device tensor {shape} {dtype}, got {tuple(out[name].shape)} {out[name].dtype} on {out[name].device}")
+        _check_out(out, self._out_fields(n, depth_count=False))
         if any(t is not None and t.device.type != "cuda" for t in (depth, frame_of, rt, half, seed_state)):
             raise ValueError("launch_boxes: device tensors only")
         if n == 0:
@@ -482,35 +503,22 @@ class DepthToClouds:
         depth: [H,W] or [F,H,W] uint16 millimetres, a host array (copied through a pinned block into a static device buffer) or a device
         tensor (used as it is); frame_of [n] (optional): each object's frame, default frame 0.  rt, half, frame_of: device tensors are used
         as they are, host arrays are uploaded.  out: empty_outputs_boxes(n) of an earlier call - then nothing is allocated."""
-        from .graphs import PinnedBlock
         depth, rt, half, frame_of, F, H, W, n = check_box_inputs(depth, rt, half, frame_of, inflate, pad, min_count)
         if out is None:
             out = self.empty_outputs_boxes(n)
         if n == 0:
             return out
-        key = ("boxes", F, H, W)
-        st = self._staging.get(key)
-        if st is None:
-            if len(self._staging) >= 8:
-                self._staging.pop(next(iter(self._staging)))
-            st = self._staging[key] = {"seed": torch.zeros(8, dtype=torch.int32, device=self.dev),
-                                       "pin_seed": [PinnedBlock((8,), torch.int32) for _ in range(self.RING)], "ring": 0}
-        slot = st["ring"] = (st["ring"] + 1) % self.RING
+        st, ring = self._stage(self._staging, ("boxes", F, H, W), self.RING)
         if depth.device.type != "cuda":
-            if "pin_depth" not in st:
-                st["depth"] = torch.empty(F, H, W, dtype=torch.int16, device=self.dev)
-                st["pin_depth"] = [PinnedBlock((F, H, W), torch.int16) for _ in range(self.RING)]
             depth16 = depth.view(torch.int16).reshape(F, H, W)
-            depth = st["pin_depth"][slot].send(st["depth"], lambda h: h.copy_(depth16))
+            depth = ring.send("depth", self._reserve(st, "depth", F, (H, W), torch.int16), lambda h: h.copy_(depth16))
         else:
             depth = depth.contiguous().view(F, H, W)
         rt, half = rt.to(self.dev).contiguous(), half.to(self.dev).contiguous()
         if frame_of is not None:
             frame_of = frame_of.to(device=self.dev, dtype=torch.int32).contiguous()
-        seed = int(seed) % (1 << 64)
-        words = np.array([seed & 0xFFFFFFFF, seed >> 32, int(run) & 0xFFFFFFFF, 0, int(slot_base) & 0xFFFFFFFF, 0, 0, 0], dtype=np.uint32)
-        st["pin_seed"][slot].send(st["seed"], lambda h: h.copy_(torch.from_numpy(words.view(np.int32))))
-        return self.launch_boxes(depth, frame_of, rt, half, inflate, pad, min_count, st["seed"], out)
+        seed_state = ring.send("seed", self._reserve(st, "seed", 8, (), torch.int32), _seed_fill(seed, run, slot_base))
+        return self.launch_boxes(depth, frame_of, rt, half, inflate, pad, min_count, seed_state, out)
 
     # ------------------------------------------------------------------ many frames in one launch
     def empty_outputs_frames(self, n):
@@ -529,10 +537,7 @@ class DepthToClouds:
             raise ValueError("launch_frames: depth [F,H,W], det [n,3]")
         F, H, W = depth.shape
         n = det.shape[0]
-        for name, shape, dtype in (("points", (n, self.n_pts, 3), torch.float32), ("count", (n,), torch.int32),
-                                   ("depth_count", (n,), torch.int32), ("valid", (n,), torch.uint8)):
-            if tuple(out[name].shape) != shape or out[name].dtype != dtype or out[name].device.type != "cuda":
-                raise ValueError(f"out[{name!r}]: a device tensor {shape} {dtype}, got {tuple(out[name].shape)} {out[name].dtype} on {out[name].device}")
+        _check_out(out, self._out_fields(n))
         if depth.dtype not in (torch.uint16, torch.int16) or masks.dtype != torch.uint8 or masks.dim() != 1 or mask_off.dtype != torch.int64 \
                 or tuple(mask_off.shape) != (F,) or det.dtype != torch.int32 or tuple(det.shape) != (n, 3) or draw.dtype != torch.int32 \
                 or tuple(draw.shape) != (n, 2) or minv.dtype != torch.float64 or tuple(minv.shape) != (n, 6) or seed_state.dtype != torch.int32 \
@@ -548,25 +553,6 @@ class DepthToClouds:
                   ptr(out["valid"]), stream_ptr())
         return out
 
-    def _reserve(self, st, name, need, tail, dtype):
-        """st[name]: a device buffer [capacity, *tail] with capacity >= need - sized by capacity, it only grows (by half at least), so a
-        ragged sequence of batches does not reallocate on every call; its pinned blocks are rebuilt with it."""
-        cap = st["cap"].get(name, 0)
-        if cap < need:
-            cap = max(need, cap + cap // 2)
-            st[name] = torch.empty((cap,) + tail, dtype=dtype, device=self.dev)
-            for blk in st["pin"].pop(name, ()):
-                blk._ev.synchronize()  # (the last copy out of a block that goes away has completed)
-            st["cap"][name] = cap
-        return st[name]
-
-    def _pinned(self, st, name, slot):
-        from .graphs import PinnedBlock
-        ring = st["pin"].get(name)
-        if ring is None:
-            ring = st["pin"][name] = [PinnedBlock(tuple(st[name].shape), st[name].dtype) for _ in range(self.FRAMES_RING)]
-        return ring[slot]
-
     def _clouds_frames(self, frames, seed, first_run, slot_base, runs, slots, out):
         """device_clouds_frames -> (its dict, the host tables)."""
         frames = [tuple(fr[:3]) for fr in frames]
@@ -576,15 +562,10 @@ class DepthToClouds:
             out = self.empty_outputs_frames(n)
         if n == 0:
             return out, t
-        st = self._staging_frames.get((H, W))
-        if st is None:
-            if len(self._staging_frames) >= 4:
-                self._staging_frames.pop(next(iter(self._staging_frames)))
-            st = self._staging_frames[(H, W)] = {"cap": {}, "pin": {}, "ring": 0}
-        slot = st["ring"] = (st["ring"] + 1) % self.FRAMES_RING
+        st, ring = self._stage(self._staging_frames, (H, W), self.FRAMES_RING)
         # ---- depth: device images that are one block already are used as they are; others are gathered by device copies; host images go up
         # through one pinned block, the frames side by side
-        depths = [torch.as_tensor(np.ascontiguousarray(fr[0])) if not torch.is_tensor(fr[0]) else fr[0] for fr in frames]
+        depths = [_as_tensor(fr[0]) for fr in frames]
         on_dev = [d.device.type == "cuda" for d in depths]
         depth = _as_one_block(depths, H, W) if all(on_dev) else None
         if depth is None:
@@ -597,13 +578,12 @@ class DepthToClouds:
                 def fill_depth(h):
                     for f in range(F):
                         h[f].copy_(i16[f])
-                self._pinned(st, "depth", slot).send(buf, fill_depth, rows=F)
+                ring.send("depth", buf, fill_depth, rows=F)
             else:
                 raise ValueError("device_clouds_frames: the frames' depth images are all host arrays or all device tensors")
             depth = buf[:F]
         # ---- masks: packed at mask_off - on the host into one pinned block (bool -> 0 / 1 there), from the device by one copy per frame
-        blocks = [(f, int(t["mask_off"][f]), torch.as_tensor(np.ascontiguousarray(fr[1])) if not torch.is_tensor(fr[1]) else fr[1])
-                  for f, fr in enumerate(frames) if len(fr[2])]
+        blocks = [(f, int(t["mask_off"][f]), _as_tensor(fr[1])) for f, fr in enumerate(frames) if len(fr[2])]
         on_dev = [m.device.type == "cuda" for _, _, m in blocks]
         nbytes = t["mask_bytes"]
         if len(blocks) == 1 and on_dev[0] and blocks[0][2].dtype == torch.uint8 and blocks[0][2].is_contiguous():
@@ -617,16 +597,14 @@ class DepthToClouds:
                 def fill_masks(h):
                     for f, off, m in blocks:
                         h[off:off + m.numel()].view(m.shape).copy_(m)
-                self._pinned(st, "masks", slot).send(buf, fill_masks, rows=nbytes)
+                ring.send("masks", buf, fill_masks, rows=nbytes)
             else:
                 raise ValueError("device_clouds_frames: the frames' masks are all host arrays or all device tensors")
             masks = buf[:nbytes]
         # ---- the tables and the seed: ONE pinned block, one copy - int64 mask_off [F] | float64 minv [n,6] | int64 frame, inst [2,n] |
         # int32 det [n,3] | uint32 draw [n,2] | the 8 seed words (run and slot words unused: they come from draw)
-        seed = int(seed) % (1 << 64)
-        words = np.array([seed & 0xFFFFFFFF, seed >> 32, 0, 0, 0, 0, 0, 0], dtype=np.uint32)
         parts = [("mask_off", t["mask_off"]), ("minv", t["minv"]), ("fi", np.stack([t["frame"], t["inst"]])), ("det", t["det"]),
-                 ("draw", t["draw"]), ("seed", words)]
+                 ("draw", t["draw"]), ("seed", _lib.seed_words(seed))]
         total = sum(a.nbytes for _, a in parts)
         buf = self._reserve(st, "tables", total, (), torch.uint8)
 
@@ -635,7 +613,7 @@ class DepthToClouds:
             for _, a in parts:
                 hn[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
                 o += a.nbytes
-        self._pinned(st, "tables", slot).send(buf, fill_tables, rows=total)
+        ring.send("tables", buf, fill_tables, rows=total)
         as_torch = {"int64": torch.int64, "float64": torch.float64, "int32": torch.int32, "uint32": torch.int32}
         dev, o = {}, 0
         for name, a in parts:  # (8-byte entries first: every view starts at a multiple of its item size)

@@ -12,8 +12,8 @@ import math
 import numpy as np
 import torch
 
-from . import reward, rotation
-from .graphs import capture, holding, release
+from . import _lib, reward, rotation
+from .graphs import UploadRing, capture, holding, release
 from .lru import ShapeCache
 
 
@@ -134,16 +134,23 @@ class SingleFrameRunner:
         DepthToClouds.device_clouds (self.depth_front_end; a default one on first use): one launch, the sampled pixels a function of
         (seed, frame, detection index), no count read back.  A detection the reference skips (valid = 0: its cloud is all zeros) runs through
         the networks with the rest and gets the identity as average_sRT, the reference's f_sRT[i] = identity - by a device-side select."""
+        return self._infer_front_end(lambda fe: fe.device_clouds(depth, masks, rois, seed, frame), np.asarray(class_ids))
+
+    def _infer_front_end(self, clouds, class_ids):
+        """clouds(front end) -> its dict; class_ids: host array, one per detection.  infer_tensors on the dict's points, the identity as
+        average_sRT where valid = 0, the front end's other fields carried along, cat_id = class_ids - 1."""
         from .preprocess import DepthToClouds
         if self.depth_front_end is None:
             self.depth_front_end = DepthToClouds()
-        fe = self.depth_front_end.device_clouds(depth, masks, rois, seed, frame)
+        fe = clouds(self.depth_front_end)
+        if len(class_ids) != fe["valid"].shape[0]:
+            raise ValueError(f"{len(class_ids)} class_ids for {fe['valid'].shape[0]} detections")
         out = self.infer_tensors(fe["points"])
         if "average_sRT" in out:
             avg = out["average_sRT"]
             out["average_sRT"] = torch.where(fe["valid"].bool().view(-1, 1, 1), avg, torch.eye(4, dtype=avg.dtype, device=avg.device))
-        out["valid"], out["count"], out["depth_count"] = fe["valid"], fe["count"], fe["depth_count"]
-        out["cat_id"] = torch.as_tensor(np.asarray(class_ids), dtype=torch.int64).to(fe["valid"].device) - 1
+        out.update((k, v) for k, v in fe.items() if k != "points")
+        out["cat_id"] = torch.as_tensor(class_ids, dtype=torch.int64).to(fe["valid"].device) - 1
         return out
 
     def infer_depth_frames(self, frames, seed=0, first_frame=0):
@@ -152,22 +159,9 @@ class SingleFrameRunner:
         launch (DepthToClouds.device_clouds_frames; frame f draws as (seed, first_frame + f, instance), so its rows are what
         infer_depth(*frames[f], seed, frame=first_frame + f) feeds the networks), then infer_tensors on all n clouds - sliced by batch_size,
         so the networks see full batches instead of one frame's five clouds - and the identity for the detections without a cloud."""
-        from .preprocess import DepthToClouds
-        if self.depth_front_end is None:
-            self.depth_front_end = DepthToClouds()
         frames = list(frames)
-        fe = self.depth_front_end.device_clouds_frames([fr[:3] for fr in frames], seed, first_run=first_frame)
-        out = self.infer_tensors(fe["points"])
-        if "average_sRT" in out:
-            avg = out["average_sRT"]
-            out["average_sRT"] = torch.where(fe["valid"].bool().view(-1, 1, 1), avg, torch.eye(4, dtype=avg.dtype, device=avg.device))
-        for k in ("valid", "count", "depth_count", "frame", "inst"):
-            out[k] = fe[k]
         cls = np.concatenate([np.asarray(fr[3], dtype=np.int64).reshape(-1) for fr in frames]) if frames else np.zeros(0, dtype=np.int64)
-        if len(cls) != fe["valid"].shape[0]:
-            raise ValueError(f"{len(cls)} class_ids for {fe['valid'].shape[0]} detections")
-        out["cat_id"] = torch.from_numpy(cls).to(fe["valid"].device) - 1
-        return out
+        return self._infer_front_end(lambda fe: fe.device_clouds_frames([fr[:3] for fr in frames], seed, first_run=first_frame), cls)
 
     def evaluate(self, detect_result, out_dir=None, degree_thresholds=tuple(range(0, 46)), shift_thresholds=tuple(i / 2 for i in range(21)),
                  iou_thresholds=tuple(i / 100 for i in range(101)), pooling_mode="average", ranker="energy_ranker"):
@@ -693,7 +687,6 @@ class FixedStepTracker:
 
     # ------------------------------------------------------------------ the frame's second graph
     def _body(self, ent):
-        from . import _lib
         from ._lib import ptr, stream_ptr
         from .likelihood import global_prior_likelihood
         from .sde import SIGMA_MAX
@@ -764,17 +757,12 @@ class FixedStepTracker:
                "src": torch.full((n,), -1, dtype=torch.int32, device=dev), "fallback": torch.zeros(n, 4, 4, device=dev),
                "seed": torch.zeros(len(key), 8, dtype=torch.int32, device=dev), "pts": pts.clone(),
                "dst": torch.tensor([i * self.max_objects + j for i, c in key for j in range(c)], dtype=torch.int64, device=dev),
-               "src_host": None, "ring": 0,
-               "pin_seed": [torch.zeros(len(key), 8, dtype=torch.int32).pin_memory() for _ in range(self.RING)],
-               "pin_src": [torch.zeros(n, dtype=torch.int32).pin_memory() for _ in range(self.RING)],
-               "pin_fb": [torch.zeros(n, 4, 4).pin_memory() for _ in range(self.RING)],
-               "ev": [None] * self.RING}
+               "src_host": None, "ring": UploadRing(self.RING)}
         smp._write_schedule((self.T0, self.acquire_T0) if self.init == "prior" else self.T0, net.sampling_eps)
         if self.ranker == "consensus":  # the symmetry flags: static, read by the captured launch; NULL (no object symmetric) without `symmetric`
             ent["sym"] = ent["sym_host"] = None
             if self.symmetric is not None:
                 ent["sym"], ent["sym_host"] = torch.zeros(n, dtype=torch.int8, device=dev), [0] * n
-                ent["pin_sym"] = [torch.zeros(n, dtype=torch.int8).pin_memory() for _ in range(self.RING)]
         if self.ranker == "likelihood":
             lsteps = getattr(net.cfg, "likelihood_steps", None) or self.steps
             lk = ent["lik"] = HeunLikelihood(net.pose_score_net, n, K, dev, int(lsteps), grid=getattr(net.cfg, "likelihood_grid", "geometric"), use_graph=False)
@@ -825,36 +813,24 @@ class FixedStepTracker:
                 src.append(i * self.max_objects + names.index(name) if name in names else -1)
                 fresh = fresh or (src[-1] < 0 and self.init == "gt")  # init 'prior': no fallback pose, nothing drawn or uploaded for it
         ent["pts"].copy_(pts)
-        slot = ent["ring"] = (ent["ring"] + 1) % self.RING
-        if ent["ev"][slot] is not None:
-            ent["ev"][slot].synchronize()  # the copies issued RING steps ago out of these pinned blocks (long completed)
-        else:
-            ent["ev"][slot] = torch.cuda.Event()
+        ring = ent["ring"]
+        ring.advance()  # (each block is rewritten RING steps after the copy out of it was issued: long completed)
         with _one_cpu_thread():
             if fresh:
-                ent["pin_fb"][slot].copy_(torch.cat([self._jitter(i, frames[i][2]) for i in live], dim=0))
-                ent["fallback"].copy_(ent["pin_fb"][slot], non_blocking=True)
+                ring.send("fallback", ent["fallback"], lambda h: h.copy_(torch.cat([self._jitter(i, frames[i][2]) for i in live], dim=0)))
             uploaded = src != ent["src_host"]
             if uploaded:
-                ent["pin_src"][slot].copy_(torch.tensor(src, dtype=torch.int32))
-                ent["src"].copy_(ent["pin_src"][slot], non_blocking=True)
+                ring.send("src", ent["src"], lambda h: h.copy_(torch.tensor(src, dtype=torch.int32)))
                 ent["src_host"] = src
             if self.symmetric is not None:
                 sym = [int(bool(self.symmetric(name))) for i in live for name in frames[i][1]]
                 if sym != ent["sym_host"]:
-                    ent["pin_sym"][slot].copy_(torch.tensor(sym, dtype=torch.int8))
-                    ent["sym"].copy_(ent["pin_sym"][slot], non_blocking=True)
+                    ring.send("sym", ent["sym"], lambda h: h.copy_(torch.tensor(sym, dtype=torch.int8)))
                     ent["sym_host"] = sym
-            words = np.zeros((len(live), 8), dtype=np.uint32)
-            for q, i in enumerate(live):
-                base = i * self.max_objects * K
-                words[q] = (self.seed & 0xFFFFFFFF, self.seed >> 32, self.frame_index[i] & 0xFFFFFFFF, 0, base & 0xFFFFFFFF, base >> 32, 0, 0)
-            ent["pin_seed"][slot].copy_(torch.from_numpy(words.view(np.int32)))
-            ent["seed"].copy_(ent["pin_seed"][slot], non_blocking=True)
-        cur = torch.cuda.current_stream(dev)
-        ent["ev"][slot].record(cur)
+            words = np.stack([_lib.seed_words(self.seed, self.frame_index[i] % (1 << 32), i * self.max_objects * K) for i in live])
+            ring.send("seed", ent["seed"], lambda h: h.copy_(torch.from_numpy(words.view(np.int32))))
         if self._two_nets:
-            cur.wait_event(self._embed.ev_e)  # the energy model's embedding (side stream)
+            torch.cuda.current_stream(dev).wait_event(self._embed.ev_e)  # the energy model's embedding (side stream)
         replays += 1
         init_x, pred, energy, sorted_RTs, average_sRT = (t.clone() for t in captured.replay())
         smp = ent["smp"]

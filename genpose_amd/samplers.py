@@ -162,17 +162,9 @@ class PCSampler:
         if run_index is None:
             run_index = self.next_run_index
             self.next_run_index = (run_index + 1) % (1 << 32)
-        if not 0 <= int(run_index) < (1 << 32):
-            raise ValueError(f"run_index {run_index}: 32 bits")
-        base = self.row_base if row_base is None else int(row_base)
-        if not 0 <= base < (1 << 63):
-            raise ValueError(f"row_base {base}")
+        words = _lib.seed_words(self.seed, run_index, self.row_base if row_base is None else row_base)  # (ValueError: run or base out of range)
         self.last_run_index = int(run_index)
-
-        def fill(h):
-            h[0] = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
-            h[1], h[2], h[3] = int(run_index), base, 0
-        self._seed_host.send(self.seed_state, fill)
+        self._seed_host.send(self.seed_state, lambda h: h.copy_(torch.from_numpy(words.view(np.int64))))
 
     def launch_step(self, i):
         """Launch i of the chain (0 <= i <= n) on the current stream: finishes step i-1 and, for i < n, evaluates the score at t_i."""
@@ -284,16 +276,15 @@ def pc_noise_fill(seed, run_index, num_steps, nrows, device, row_base=0, step0=0
     [num_steps, nrows, 9] each, for steps step0 .. and rows row0 .. of a launch whose first row is global row `row_base`.  Feeding them to
     an unseeded sampler's run(z_langevin=, z_predictor=) reproduces the seeded run bit for bit."""
     dev = torch.device(device)
-    seed = int(seed) % (1 << 64)
-    st = torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, int(run_index), int(row_base), 0], dtype=torch.int64).to(dev)
+    st = _seed_state(seed, run_index, row_base, dev)
     z1, z2 = torch.empty(num_steps, nrows, 9, device=dev), torch.empty(num_steps, nrows, 9, device=dev)
     _lib.call("gp_pc_noise_fill", ptr(st), int(step0), int(num_steps), int(row0), int(nrows), ptr(z1), ptr(z2), stream_ptr())
     return z1, z2
 
 
 def _seed_state(seed, run_index, row_base, device):
-    seed = int(seed) % (1 << 64)
-    return torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, int(run_index), int(row_base), 0], dtype=torch.int64).to(device)
+    """_lib.seed_words as the int64 [4] tensor the seeded entry points take, on `device`."""
+    return torch.from_numpy(_lib.seed_words(seed, run_index, row_base).view(np.int64)).to(device)
 
 
 def track_prior_fill(seed, frame_index, nrows, device, row_base=0, row0=0):
