@@ -16,7 +16,8 @@
 // instructions at the chunk ends of pose_encoder.2's last step, 124 before the first head chunk), the head loop's short runs, the last
 // head's last chunk.
 // run<KSIDE, NPROD>: NPROD = 9 is all of the above; NPROD = 6 (the PC step's six-product kernels, trunk_bf16x9.hip) issues six of the nine
-// products of every multiply (bf16x9.h) - 6 336 MFMAs per wave instead of 9 504, the same ring, packs, orders and side pieces.
+// products of every multiply (bf16x9.h) - 6 336 MFMAs per wave instead of 9 504, the same ring, packs, orders and side pieces, the
+// pieces in fewer instructions (DIET in run: one-instruction ReLU, the head outputs as fma chains, LDS addresses as register + immediate).
 //   request : slices 0 and 1 into registers - the caller places it among its own loads (memory returns in order)
 //   stage_request : the staged fp32 operands (w_out, b0, b2, cvec[cloud] + tvec) into registers, for a caller that has work of its own
 //             before run() - issued BEFORE request, they arrive under that work instead of behind the 24 weight loads
@@ -45,12 +46,34 @@ __device__ __forceinline__ float plain(float v) {
     asm("" : "+v"(v));
     return v;
 }
+// relu_plain<BITS>(s) = fmaxf(s, 0) of a pinned sum.  Behind the pin the compiler no longer knows that s is canonical and puts a
+// v_max_f32 s, s, s in front of the maximum: two instructions per ReLU.  BITS (the six-product kernels): the maximum of the BITS as
+// signed integers, one v_max_i32 - a float with its sign set is a negative integer and gives +0, any other keeps its bits.  For every s
+// that is not a NaN that is fmaxf(s, 0) to the bit (a NaN with a clear sign stays a NaN where fmaxf gives 0).
+template <bool BITS>
+__device__ __forceinline__ float relu_plain(float s) {
+    s = plain(s);
+    if constexpr (BITS) {
+        const int b = __builtin_bit_cast(int, s);
+        return __builtin_bit_cast(float, b > 0 ? b : 0);
+    } else
+        return fmaxf(s, 0.f);
+}
+template <bool BITS = false>
 __device__ __forceinline__ f32x4 relu_sum4(const f32x4 a, const f32x4 b) {  // relu4(a + b)
-    return f32x4{fmaxf(plain(a.x + b.x), 0.f), fmaxf(plain(a.y + b.y), 0.f), fmaxf(plain(a.z + b.z), 0.f), fmaxf(plain(a.w + b.w), 0.f)};
+    return f32x4{relu_plain<BITS>(a.x + b.x), relu_plain<BITS>(a.y + b.y), relu_plain<BITS>(a.z + b.z), relu_plain<BITS>(a.w + b.w)};
 }
 __device__ __forceinline__ float dot4_plain(const f32x4 v, const f32x4 w) {  // v.x * w.x + v.y * w.y + v.z * w.z + v.w * w.w
     const float m0 = plain(v.x * w.x), m1 = plain(v.y * w.y), m2 = plain(v.z * w.z), m3 = plain(v.w * w.w);
     return plain(plain(plain(m0 + m1) + m2) + m3);
+}
+// o + v . w as one chain of four fused multiply-adds (the six-product kernels): 4 instructions where dot4_plain and its accumulate take
+// 8, the same four products, each added unrounded - and pinned like the rest (the two tiles' chains side by side would be packed)
+__device__ __forceinline__ float dot4_fma(const f32x4 v, const f32x4 w, float o) {
+    o = plain(__builtin_fmaf(v.x, w.x, o));
+    o = plain(__builtin_fmaf(v.y, w.y, o));
+    o = plain(__builtin_fmaf(v.z, w.z, o));
+    return plain(__builtin_fmaf(v.w, w.w, o));
 }
 // operands of a head chunk's epilogue in flight between the sub-blocks of the next chunk
 struct HeadEpi {
@@ -80,8 +103,9 @@ __device__ __forceinline__ void stage_request(X9Staged &sg, const SplitNet &w, c
 // 1 (the Heun step): all but pose_encoder.2's tail - with it that kernel parks 117 values in AGPRs instead of 76 and loses what the
 // rest gains.  2 (the PC kernels): all of it.  (profiles/x9_kmajor_under_mfma.txt)
 // NPROD: the products per multiply (bf16x9.h), forwarded to both ring functions - 9 (the default: every kernel whose bits are recorded) or
-// 6 (the PC step's six-product kernels).  With six, a chunk's or sub-block's 12 MFMAs take THREE other instructions behind each: the side
-// pieces above were cut for 18 MFMAs x 2 and find the same 36 places.
+// 6 (the PC step's six-product kernels).  With six, the side pieces above are issued in fewer instructions (DIET, in run) and a chunk's or
+// sub-block's 12 MFMAs take two other instructions behind each like nine products' 18: 24 places where the pieces were cut for 36 - three
+// behind each, which the kernels had before the pieces shrank, measures 1.8 us per launch slower (profiles/x6_issue_budget.txt).
 template <int KSIDE = 0, int NPROD = 9, class Emit, class Staged = std::nullptr_t>
 __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *cvec, const float *tvec, int wg_row0, int nrows, int kcand,
                                     const bf16x8 (&first)[X9_PER_T], bf16x8 (&hold)[X9_PER_T], const float (&xv)[X9_RT][POSE],
@@ -89,7 +113,22 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
     bf16x8 *ring = reinterpret_cast<bf16x8 *>(lds);
     const float *woutl = lds + X9Lds::OFF_WOUT, *b0l = lds + X9Lds::OFF_B0, *b2l = lds + X9Lds::OFF_B2, *cvtl = lds + X9Lds::OFF_CVT;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
-    constexpr int OTHERS = NPROD == 6 ? 3 : 2;
+    // DIET (the six-product kernels; profiles/x6_issue_budget.txt): fewer instructions for the same side work - relu_plain<true>, dot4_fma,
+    // and LDS addresses as one register + an immediate.  A ds_read's 16-bit offset does not reach the second ring slot (48 KB up) from the
+    // first slot's lane address, nor the staged fp32 operands (from byte 96 K), and the compiler forms each such address with an add of
+    // its own or parks it in an AGPR.  lane1 is the lane's element index IN SLOT 1 counted from slot 0, pinned: through (ring, lane1)
+    // every fragment of slot 1 is a base register + an immediate, as slot 0's are.  g4 is the lane group's 4 g carried as the pinned
+    // sum OFF_WOUT + 4 g: the staged operands' addresses are that register (+ what moves with the head and the cloud) + an immediate.
+    constexpr bool DIET = NPROD == 6;
+    int lane1 = lane + X9_SLICE, g4 = 4 * g;
+    if constexpr (DIET) {
+        asm("" : "+v"(lane1));
+        g4 += X9Lds::OFF_WOUT;
+        asm("" : "+v"(g4));
+        g4 -= X9Lds::OFF_WOUT;
+    }
+    auto slot_of = [&](int gs) { return DIET ? ring : ring + (gs & 1) * X9_SLICE; };
+    auto lane_of = [&](int gs) { return DIET && (gs & 1) ? lane1 : lane; };
     // ---- staged epilogue operands and slot 0
     if constexpr (std::is_same<Staged, X9Staged>::value) split_stage_store<X9_NT, X9Lds>(lds, sg);
     else split_stage<X9_NT, X9Lds>(lds, w, cvec, tvec, wg_row0, nrows, kcand);
@@ -103,7 +142,7 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
         // the plain form (the text rk45.hip's resource table was taken with): bias + ReLU between the layers, each k-block split before its step
         auto step = [&](const Split8 (&xs)[X9_RT], bool first) {
             const int gs = gstep++;
-            ring_step<X9_NT, X9_PER_T, false, 0, 16, NPROD, OTHERS>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
+            ring_step<X9_NT, X9_PER_T, false, 0, 16, NPROD>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
                                                      tid, lane, first);
         };
         auto hidden = [&](const float *bias) {
@@ -143,12 +182,12 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
     // + 1) of xs_all[m] = split8(relu4(acc[.][2m] + ba), relu4(acc[.][2m + 1] + bb))
     f32x4 tb[2][2];
     auto tail_read = [&](int m) {
-        tb[m & 1][0] = *reinterpret_cast<const f32x4 *>(b2l + 32 * m + 4 * g), tb[m & 1][1] = *reinterpret_cast<const f32x4 *>(b2l + 32 * m + 16 + 4 * g);
+        tb[m & 1][0] = *reinterpret_cast<const f32x4 *>(b2l + 32 * m + g4), tb[m & 1][1] = *reinterpret_cast<const f32x4 *>(b2l + 32 * m + 16 + g4);
     };
     auto tail_piece = [&](int m, int q) {
         const int p = q >> 2, i = 2 * (q & 3), j = i & 3;
         const f32x4 a = acc[p][2 * m + (i >> 2)], b = tb[m & 1][i >> 2];
-        split8_pair(xs_all[m][p], i, fmaxf(plain(a[j] + b[j]), 0.f), fmaxf(plain(a[j + 1] + b[j + 1]), 0.f));
+        split8_pair(xs_all[m][p], i, relu_plain<DIET>(a[j] + b[j]), relu_plain<DIET>(a[j + 1] + b[j + 1]));
     };
     if constexpr (KSIDE == 0) {  // (written out in place, after the layers: the order rk45.hip's resource table was taken with)
 #pragma unroll
@@ -164,8 +203,8 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
         // the accumulators (no zeroing pass)
         auto step = [&](const Split8 (&xs)[X9_RT], bool first, auto side) {
             const int gs = gstep++;
-            ring_step<X9_NT, X9_PER_T, false, 0, 16, NPROD, OTHERS>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
-                                                     tid, lane, first, side);
+            ring_step<X9_NT, X9_PER_T, false, 0, 16, NPROD>(slot_of(gs), ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, xs, acc,
+                                                     tid, lane_of(gs), first, side);
         };
         // The k-major layers keep their 256-wide input in fp32 (act) and split it one k-block at a time.  Nothing of that is issued between two
         // layers or two steps: every piece rides beside the MFMAs of a chunk that does not need it yet (one wave per SIMD - what is not placed
@@ -178,10 +217,10 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
         // The expressions and their order per value are those of relu4(acc + b) and split8: the bits do not move.
         f32x4 bv;
         Split8 xs[2][X9_RT];
-        auto bias_read = [&](const float *bias, int n) { bv = *reinterpret_cast<const f32x4 *>(bias + 16 * n + 4 * g); };
+        auto bias_read = [&](const float *bias, int n) { bv = *reinterpret_cast<const f32x4 *>(bias + 16 * n + g4); };
         auto bias0 = [&](int n) {
 #pragma unroll
-            for (int p = 0; p < X9_RT; ++p) act[p][n] = relu_sum4(acc[p][n], bv);
+            for (int p = 0; p < X9_RT; ++p) act[p][n] = relu_sum4<DIET>(acc[p][n], bv);
         };
         auto split_piece = [&](Split8 (&x)[X9_RT], int kb, int q) {
             const int p = q >> 2, i = 2 * (q & 3);
@@ -243,7 +282,7 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
     bf16x8 w1[3];
     // piece k of the epilogue of chunk n of head hp (one piece per sub-block of the next chunk: the reads, bias + ReLU, three dot products)
     auto epi = [&](int k, int hp, int n) {
-        const int ch = 16 * n + 4 * g;
+        const int ch = 16 * n + g4;
         if (k == 0) {
 #pragma unroll
             for (int p = 0; p < X9_RT; ++p) e.cv[p] = *reinterpret_cast<const f32x4 *>(cvtl + cl[p] * HEADS + 256 * hp + ch);
@@ -251,10 +290,13 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
             for (int c = 0; c < 3; ++c) e.w[c] = *reinterpret_cast<const f32x4 *>(woutl + (3 * hp + c) * HID + ch);
         } else if (k == 1) {
 #pragma unroll
-            for (int p = 0; p < X9_RT; ++p) e.v[p] = relu_sum4(pend[p], e.cv[p]);
+            for (int p = 0; p < X9_RT; ++p) e.v[p] = relu_sum4<DIET>(pend[p], e.cv[p]);
         } else if (k <= 4) {
 #pragma unroll
-            for (int p = 0; p < X9_RT; ++p) o[p][k - 2] = plain(o[p][k - 2] + dot4_plain(e.v[p], e.w[k - 2]));
+            for (int p = 0; p < X9_RT; ++p) {
+                if constexpr (DIET) o[p][k - 2] = dot4_fma(e.v[p], e.w[k - 2], o[p][k - 2]);
+                else o[p][k - 2] = plain(o[p][k - 2] + dot4_plain(e.v[p], e.w[k - 2]));
+            }
         }
     };
     auto finish = [&](int hp) {
@@ -272,8 +314,8 @@ __device__ __forceinline__ void run(float *lds, const SplitNet &w, const float *
         if (C == 1) ++gstep;
 #pragma unroll
         for (int p = 0; p < X9_RT; ++p) pend[p] = fin[p];
-        ring_half_step<X9_NT, X9_PER_T, 8, C, NPROD, OTHERS>(ring + (gs & 1) * X9_SLICE, ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, w1, xs_all,
-                                              fin, tid, lane, side);
+        ring_half_step<X9_NT, X9_PER_T, 8, C, NPROD>(slot_of(gs), ring + ((gs + 1) & 1) * X9_SLICE, split_slice<3>(w, gs + 2), hold, w1, xs_all,
+                                              fin, tid, lane_of(gs), side);
     };
     constexpr std::integral_constant<int, 0> c0{};
     constexpr std::integral_constant<int, 1> c1{};

@@ -38,11 +38,22 @@
 // below the fp32 accumulation's own rounding); the weight packs are unchanged (the lo terms are still read for lo.hi and hi.lo).
 //   MFMA                33 x 16 chunks x 6 products x 2 tiles = 6 336 per wave x 16 cycles = 101 k cycles per SIMD (42 us at 2.4 GHz, 53 us
 //                       at 1.9 GHz); SQ_VALU_MFMA_BUSY_CYCLES 101 376 000 per launch against 152 064 000
-// The side pieces keep their places: a chunk's 12 MFMAs take three other instructions behind each where 18 took two (36 places either
-// way).  256 + 255 registers, 22 (seeded: 26) values parked in AGPRs, 0 B of scratch.  Measured (profiles/x6_products.txt): 75.0-75.2 us
-// per launch against 95.6-95.7 us in one alternating session (HIP events around the PC-100 graph, 32 000 rows); MFMA-busy over
-// 4 x busy-CU cycles 0.57 against 0.65 - more of the launch is now the exposed part listed above, which did not shrink.  The Heun, DPM-Solver
-// and RK45 kernels and the nine-product PC kernels keep nine products and their device code: their bits are recorded.
+// Measured with the nine-product side work and three other instructions behind each of a chunk's 12 MFMAs (profiles/x6_products.txt):
+// 75.0-75.2 us per launch against 95.6-95.7 us in one alternating session (HIP events around the PC-100 graph, 32 000 rows); MFMA-busy
+// over 4 x busy-CU cycles 0.57 against 0.65 - one wave per SIMD issues every instruction itself, an MFMA holds the vector issue for 8 of
+// its 16 cycles and a VALU instruction for 4, and 6 336 MFMAs + 16 100 other instructions per wave are more issue than the matrix pipe's
+// 101 k cycles.  So the six-product kernels issue FEWER instructions for the same side work (trunk_bf16x9.h, DIET;
+// profiles/x6_issue_budget.txt): the ReLU behind a pinned sum as one v_max_i32 on the bits (the pin cost a v_max_f32 v, v, v each),
+// the heads' Linear(256, 3) epilogue as one fma chain per output (4 instructions for 8, one rounding fewer per product), the second ring
+// slot and the staged fp32 operands read through a pinned base register + an immediate (no add per address, no addresses parked in
+// AGPRs), and two other instructions behind each MFMA again, as nine products have it.  Per wave and launch 16 125 -> 13 703 instructions
+// that are not MFMAs (VALU 8 562 -> 6 405; SQ_INSTS_VALU 15.36 M -> 13.10 M per launch, MFMA-busy 101 376 000 unchanged), 256 + 231
+// registers, 18 values parked in AGPRs, 0 B of scratch, both kernels.  70.8-71.0 us per launch against 75.6-75.8 us in one alternating
+// session (-6.4 %; 2.3 us the instructions, 1.8 us the two-per-MFMA placement), MFMA-busy over 4 x busy-CU 0.63; headline blocks
+// 25.67-25.84 ms against 26.68-26.90 ms (-3.8 %).  Left: the pins' own s_nop pads, the 64-bit adds of the ring's global loads, 173 packed
+// fp32 instructions of the splits (unpacking them raised the count and gained nothing), and the exposed parts listed above.  The clock
+// inside the kernel has not been measured.  The Heun, DPM-Solver and RK45 kernels and the nine-product PC kernels keep nine products and
+// their device code, instruction for instruction: their bits are recorded.
 #include "pc_rows.h"
 #include "trunk_bf16x9.h"
 #include "trunk_chain.h"
